@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- driver contract.
 
-  python bench.py --gpus N --steps K --warmup W [--workload mcts|board|train|feature|boundary|games|both]
+  python bench.py --gpus N --steps K --warmup W [--workload mcts|board|train|feature|boundary|games|both] [--full] [--dump-outputs DIR]
+
+A plain run (no --full) measures the headline only: it sets up, runs the untimed prologue and W warm-up steps, times K steps and
+prints the line (no CPU baseline, no in-run parity check, no sub-results).  --full adds everything else listed below, as one run.
+--dump-outputs DIR writes what the headline's timed path computed in its last step as DIR/<name>.npy (dump_mcts_outputs); the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 --gpus N > 1 without a launcher environment: the script re-executes itself under `python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1`, one process per GPU (under the driver's own torchrun launch RANK / WORLD_SIZE are
@@ -21,7 +26,7 @@ group (node pools of 1.5 x rollouts ids per game = 167 GB; --groups 2 pipelines 
 instead of the conv net) to the point where the timed steps run at the depth of a search in progress and CROSS A MOVE BOUNDARY
 (root statistics down, move choice, forward, treeAdvance, Dirichlet draws, next search).
 
-At N = 1 the full report carries sub-results measured in the same run (each with its own roofline; the line has their numbers):
+With --full at N = 1 the full report carries sub-results measured in the same run (each with its own roofline; the line has their numbers):
   search_only     the search kernels without the conv net: 9216 games in three groups on a shared node pool of 4096 ids per game
                   (250 GB; fewer where less HBM is free), 2048-rollout moves; kernel durations from the same games as one group
   board_step      configs[1]: 4096 boards 19x19 played to the end by the config-2 policy in one k_playout launch, EVERY final
@@ -42,6 +47,8 @@ import os
 import socket
 import sys
 import time
+
+T_PROCESS = time.time()   # setup_seconds: the interpreter, torch and the library load before the headline starts
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -331,6 +338,23 @@ def self_spawn(n):
 
 
 DIST_INFO = {}
+MIOPEN_DB = os.path.join(ROOT, "elf_amd", "data", "miopen_db")
+
+
+def seed_miopen_db():
+    """The benchmark net's MIOpen find and perf database entries, recorded on an MI355X (elf_amd/data/miopen_db/: MIOpen's own text
+    files, named by device and MIOpen version) are copied into the user database directory (MIOPEN_USER_DB_PATH, else MIOpen's
+    default ~/.config/miopen) where no file of that name is there yet: on a fresh home the first net call looks its convolutions
+    up instead of searching (its kernels are still compiled then).  Files of another MIOpen version are never read by it."""
+    import shutil
+    dst = os.environ.get("MIOPEN_USER_DB_PATH") or os.path.join(os.path.expanduser("~"), ".config", "miopen")
+    try:
+        for name in sorted(os.listdir(MIOPEN_DB)):
+            if not os.path.exists(os.path.join(dst, name)):
+                os.makedirs(dst, exist_ok=True)
+                shutil.copyfile(os.path.join(MIOPEN_DB, name), os.path.join(dst, name))
+    except OSError as e:      # an unwritable home: the first net call searches, as it would without the files
+        sys.stderr.write("bench: MIOpen database not seeded (%r)\n" % (e,))
 
 
 def init_dist(args):
@@ -682,11 +706,53 @@ def net_flops_per_position(args, n):
         + 2.0 * d * args.net_dim * 3 + 2.0 * (2 * d * (d + 1) + d * 256 + 256)
 
 
-def run_mcts(args, rank, local_rank, world, dist, steps, warmup, with_cpu):
+DUMP_ROWS = 1024        # batch rows sampled by --dump-outputs: 1024 x 18 x 19 x 19 fp32 features = 26.6 MB
+DUMP_SEED = 20250101    # fixed: the same rows are sampled in every run
+
+
+def dump_mcts_outputs(path, sp, replies):
+    """--dump-outputs: what a caller of the headline's timed path holds after its last step, as float32 / float64 .npy files.
+    The batch tensors have a fixed shape (max_rows per group, groups concatenated): the same seeded sample of DUMP_ROWS row
+    indices is taken from the leaf features the last step's select wrote (the next net call's input) and from the last net
+    reply (pi, V); leaf_rows says how many rows of each group are valid.  Per game: the move the last finished search forwarded
+    and the score of the last finished game; and the context's cumulative counters (rollouts, tree nodes visited, ...)."""
+    os.makedirs(path, exist_ok=True)
+    sp.synchronize()
+    groups = sp.groups
+    max_rows = groups[0].max_rows
+    total = max_rows * len(groups)
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=min(DUMP_ROWS, total), replace=False))
+    feat, pi, v = [], [], []
+    for i, g in enumerate(groups):
+        local = rows[(rows >= i * max_rows) & (rows < (i + 1) * max_rows)] - i * max_rows
+        if not len(local):
+            continue
+        idx = torch.from_numpy(local).to(g.device)
+        feat.append(g.s.index_select(0, idx).float().contiguous().cpu().numpy())
+        r_pi, r_v = replies[g.s.data_ptr()]
+        pi.append(r_pi.index_select(0, idx).float().cpu().numpy())
+        v.append(r_v.reshape(-1).index_select(0, idx).float().cpu().numpy())
+    counters = ("moves", "games", "rollouts", "rows", "steps", "node_visits", "boundaries")
+    st = [g.stats() for g in groups]
+    out = {"leaf_features": np.concatenate(feat).astype(np.float32),
+           "sample_rows": rows.astype(np.float64),
+           "leaf_rows": np.array([g.last_rows() for g in groups], np.float64),
+           "net_policy": np.concatenate(pi).astype(np.float32),
+           "net_value": np.concatenate(v).astype(np.float32),
+           "last_moves": np.concatenate([g.last_moves() for g in groups]).astype(np.float64),
+           "last_score": np.concatenate([g.last_score() for g in groups]).astype(np.float32),
+           "selfplay_counters": np.array([[s_[k] for k in counters] for s_ in st], np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(out)
+
+
+def run_mcts(args, rank, local_rank, world, dist, steps, warmup, with_cpu, dump_dir=None):
     import elf_amd  # noqa: F401
     from elf_amd.pipeline import PipelinedSelfPlay
     n, G, K = args.board_size, args.games, args.rollouts_per_batch
     dev = torch.device("cuda", local_rank)
+    ts = [("start", time.time())]      # setup_seconds: where the run's time outside the timed steps goes
     net, dtype = build_net(args, n, dev)
     feat_fmt = "f16_nhwc" if (args.features == "f16" or (args.features == "auto" and net is not None and dtype == torch.float16)) else "f32_nchw"
     groups = max(1, args.groups)
@@ -720,6 +786,7 @@ def run_mcts(args, rank, local_rank, world, dist, steps, warmup, with_cpu):
                            mcts_virtual_loss=1, mcts_persistent_tree=True, mcts_epsilon=0.25, mcts_alpha=0.03, komi=7.5,
                            ply_pass_enabled=0, policy_distri_cutoff=30, nodes_per_game=npg_arg, feature_format=feat_fmt,
                            mcts_threads=args.mcts_threads)
+    ts.append(("contexts", time.time()))
     na = n * n + 1
     rows_max = sp.groups[0].max_rows
     rnd = RandomReplies(rows_max, na, dev, 99 + rank)
@@ -731,6 +798,7 @@ def run_mcts(args, rank, local_rank, world, dist, steps, warmup, with_cpu):
         with torch.no_grad():
             chunked_forward(net, sp.groups[0].s)
         torch.cuda.synchronize()
+    ts.append(("net_first_call", time.time()))
     graphs = {}
     if net is not None and args.net_graph:
         # one HIP graph per game group (PyTorch's CUDAGraph on ROCm): the ~85 kernel launches of a net call become one graph launch;
@@ -768,12 +836,15 @@ def run_mcts(args, rank, local_rank, world, dist, steps, warmup, with_cpu):
         pregrow = max(0, spm - warmup - max(1, steps // 2)) if steps + warmup < spm else 0
     else:
         pregrow = args.pregrow
+    ts.append(("graph_capture", time.time()))
     for _ in range(pregrow):
         sp.step(lambda s, rows: rnd())
     sp.synchronize()
+    ts.append(("pregrow", time.time()))
     for i in range(warmup):
         sp.step(net_fn)
     sp.synchronize()
+    ts.append(("warmup", time.time()))
     barrier()
     st0 = sp.stats()
     sp.timing = True
@@ -782,10 +853,16 @@ def run_mcts(args, rank, local_rank, world, dist, steps, warmup, with_cpu):
         import cProfile
         prof = cProfile.Profile()
         prof.enable()
+    timed_fn = net_fn
+    replies = {}
+    if dump_dir:
+        def timed_fn(s, rows):     # --dump-outputs: keep each group's last reply
+            replies[s.data_ptr()] = net_fn(s, rows)
+            return replies[s.data_ptr()]
     t0 = time.perf_counter()
     t_host = 0.0
     for i in range(steps):
-        sp.step(net_fn)   # every group: net -> expand -> backup -> select -> leaf features
+        sp.step(timed_fn)   # every group: net -> expand -> backup -> select -> leaf features
     t_host = time.perf_counter() - t0     # the host has ENQUEUED every step: if this is the wall time, the launches are the bottleneck
     sp.synchronize()
     barrier()
@@ -819,7 +896,11 @@ def run_mcts(args, rank, local_rank, world, dist, steps, warmup, with_cpu):
     per_rank = gather_per_rank(dist, dev, my_rollouts / dt, world)
     npg = int(sp.groups[0].opt.nodes_per_game)
     pinfo = [g_.pool_info() for g_ in sp.groups]
+    ts.append(("timed_steps", time.time()))
+    dumped = dump_mcts_outputs(dump_dir, sp, replies) if (dump_dir and rank == 0) else None
+    ts.append(("dump_outputs", time.time()))
     sp.close()
+    ts.append(("close", time.time()))
     if rank != 0:
         return None
     import elf_amd as _ea
@@ -893,7 +974,8 @@ def run_mcts(args, rank, local_rank, world, dist, steps, warmup, with_cpu):
                    "parity_note": PARITY_NOTE,
                    "pregrow_note": "the untimed tree-growing steps answer the leaves with random priors (not the net): the window's mean depth "
                                    "is that of trees shaped by noise priors plus the timed net steps; the search kernels are ~2 %% of the step either way",
-                   "parallelism": "independent games per GPU, no collective"},
+                   "parallelism": "independent games per GPU, no collective",
+                   "setup_seconds": dict([("before_headline", ts[0][1] - T_PROCESS)] + [(k, ts[i + 1][1] - ts[i][1]) for i, (k, _) in enumerate(ts[1:])])},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
                      "traffic": ((load_profile_json("pmc_traffic.json").get("k_mcts_search<%d>" % n, {}).get("hbm_bytes_per_rollout") or 0) * G * K * T or None)
@@ -1003,7 +1085,9 @@ def run_mcts(args, rank, local_rank, world, dist, steps, warmup, with_cpu):
             res["net_roofline"]["variants_note"] = "eager launches (no HIP graph), same fused epilogue; compare ms_per_2048_rows with avg_call_ms"
         except Exception as e:
             res["net_roofline"]["variants"] = "unavailable: %r" % (e,)
-    if world == 1 and n == 19:
+    if dumped:
+        res["dumped_outputs"] = {"dir": dump_dir, "files": dumped}
+    if world == 1 and n == 19 and args.full:
         res["parity"] = mcts_parity_check(local_rank)
         if res["parity"]["mismatches"]:
             raise SystemExit("bench: the search kernels differ from the reference fixture (%r) -- results are invalid" % (res["parity"],))
@@ -1777,7 +1861,7 @@ def main():
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--workload", choices=["mcts", "board", "train", "feature", "boundary", "games", "client", "single", "both", "stub"], default="both",
-                    help="both (default) = mcts headline + every sub-result at N = 1")
+                    help="both (default) = mcts headline (+ every sub-result at N = 1 with --full)")
     ap.add_argument("--train-batch", type=int, default=2048)
     ap.add_argument("--train-prefetch", type=int, default=16, help="train batches drawn + extracted per launch (1 = one batch per launch)")
     ap.add_argument("--train-records", type=int, default=256)
@@ -1829,27 +1913,36 @@ def main():
     ap.add_argument("--length-games", type=int, default=32, help="games played to their natural end to measure the game length; 0 = off")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sub", action="store_true", help="headline only (no sub-results)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the sub-results (other workloads, sizes and "
+                    "configurations), the CPU baselines, the in-run parity check against the reference fixtures and, at N > 1, the games/s "
+                    "leg.  Off (default): set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the headline's timed path "
+                    "computed in its last step as DIR/<name>.npy (float32 / float64; fixed seeded samples of the large tensors, < 64 MB)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload not in ("mcts", "both"):
+        ap.error("--dump-outputs writes the outputs of the headline workload (--workload mcts or both)")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         self_spawn(args.gpus)      # does not return
 
     rank, local_rank, world, dist = init_dist(args)
+    if torch.cuda.is_available():
+        seed_miopen_db()     # after init_dist: at N > 1 every rank has its own MIOPEN_USER_DB_PATH
     legs, t_leg = {}, [time.time()]
 
     def leg(name):     # wall seconds per leg of the run (full report): what a default run spends where
         now = time.time()
         legs[name] = round(now - t_leg[0], 2)
         t_leg[0] = now
-    with_cpu = (not args.no_cpu_baseline) and world == 1
-    sub = args.workload == "both" and world == 1 and not args.no_sub
+    with_cpu = args.full and (not args.no_cpu_baseline) and world == 1
+    sub = args.full and args.workload == "both" and world == 1 and not args.no_sub
     res = None
     if args.workload == "stub":
         res = run_stub(args, rank, local_rank, world, dist, args.steps or 5, args.warmup or 0)
     if args.workload in ("mcts", "both"):
         steps = args.steps if args.steps is not None else 40
         warmup = args.warmup if args.warmup is not None else 8
-        res = run_mcts(args, rank, local_rank, world, dist, steps, warmup, with_cpu)
+        res = run_mcts(args, rank, local_rank, world, dist, steps, warmup, with_cpu, dump_dir=args.dump_outputs)
         leg("headline")
 
     if torch.cuda.is_available():
@@ -1940,7 +2033,7 @@ def main():
         elif rank == 0:
             res["boundary"] = bd
     leg("boundary")
-    if args.workload == "games" or sub or (args.workload == "both" and world > 1 and not args.no_sub):
+    if args.workload == "games" or sub or (args.full and args.workload == "both" and world > 1 and not args.no_sub):
         # N > 1: the measured games/s of the shortened configuration rides with the headline, so that one `bench.py --gpus N` line
         # per N yields the games/sec scaling curve BASELINE.json names (measured, not the 250-moves-per-game estimate)
         gm = run_games(sargs, rank, local_rank, world, dist)

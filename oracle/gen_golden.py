@@ -10,6 +10,10 @@ Fixtures
   ladder_suite.npz every SGF in ladder_suite/ladder that replays legally: move list, final hash/ply,
                    final legal mask, final AGZ planes (code 3).
   playout_19.npz / playout_9.npz   config 2/5 protocol: seeds -> (final hash, ply, steps) per board.
+  sgf_ladder_texts.npz  the first 60 SGF files of ladder_suite/ladder (their text, latin-1) with what the reference's loader
+                   makes of them: Sgf::load (moves, players, header) for all, the replayed main line (ref_sgf_moves) for the
+                   first 25 -- the SGF readers' differentials run on these without the reference tree.
+                   (python oracle/gen_golden.py sgf_texts regenerates this file alone.)
   gtest_9x9.npz    positions from base/test/*.cc known-answer tests are ported by hand in
                    tests/test_reference_known_answers.py (not generated here).
 """
@@ -90,5 +94,34 @@ def main():
         print("playout_%d: %d boards, %d steps, mean ply %.1f" % (n, boards, tot, out[:, 2].mean()))
 
 
+def sgf_texts(n_files=60, n_main_line=25):
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    from elf_amd.train import parse_sgf
+    R = Ref(19)
+    names, blob, t_off, mv, pl, p_off, head, ml, m_off = [], [], [0], [], [], [0], [], [], [0]
+    for i, path in enumerate(sorted(glob.glob(os.path.join(SUITE, "*.sgf")))[:n_files]):
+        text = open(path, encoding="latin-1").read()
+        wm, wp, wh = R.sgf_parse(text)
+        # an entry without a move (a trailing node: player 0 in this library's reader, which the tests mask) is uninitialised
+        # memory in the reference: stored as 0, so that the file is the same every time it is generated
+        no_move = parse_sgf(19, text)[0] == 0
+        wm, wp = np.where(no_move, 0, wm), np.where(no_move, 0, wp)
+        names.append(os.path.basename(path)); blob.append(np.frombuffer(text.encode("latin-1"), np.uint8)); t_off.append(t_off[-1] + len(blob[-1]))
+        mv.append(wm.astype(np.int32)); pl.append(wp.astype(np.int32)); p_off.append(p_off[-1] + len(wm))
+        head.append([wh["size"], wh["komi"], wh["handi"], wh["winner"], wh["win_margin"]])
+        if i < n_main_line:
+            m, _ = R.sgf_moves(path)
+            ml.append(m.astype(np.int32)); m_off.append(m_off[-1] + len(m))
+    np.savez_compressed(os.path.join(OUT, "sgf_ladder_texts.npz"), names=np.array(names), text=np.concatenate(blob),
+                        text_offsets=np.array(t_off, np.int64), parse_moves=np.concatenate(mv), parse_players=np.concatenate(pl),
+                        parse_offsets=np.array(p_off, np.int64), parse_header=np.array(head, np.float64),
+                        main_line=np.concatenate(ml), main_line_offsets=np.array(m_off, np.int64))
+    print("sgf_ladder_texts: %d texts, %d main lines" % (len(names), len(ml)))
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["sgf_texts"]:
+        sgf_texts()
+    else:
+        main()
+        sgf_texts()

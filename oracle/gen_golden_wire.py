@@ -1,6 +1,8 @@
 """Generates tests/golden/wire_formats.json from the REAL reference objects (oracle/_ref/libelfsp9.so: Records, ThreadState,
 MsgRequestSeq of src_cpp/elfgames/go/common/record.h): the texts a self-play client exchanges with the training server
 (train/distri_client.h).  Run in the build container only:  python oracle/gen_golden_wire.py
+(`python oracle/gen_golden_wire.py gcwrapper` writes gcwrapper_reference_calls.json alone: the reference's GCWrapper on the recording
+mock of tests/test_pybind_boundary.py)
   requests: what the server writes for a request (MsgRequestSeq::dumpJsonString) + variants with fields removed and what
             MsgRequestSeq::createFromJson makes of them (round-tripped text, or null = it throws)
   sessions: GuardedRecords sessions -- operations (state updates, finished games, dumps) and the message text of every dump
@@ -85,5 +87,21 @@ def main():
         print([(v["removed"], v["roundtrip"] is not None) for v in r["variants"]])
 
 
+def gcwrapper_calls():
+    """tests/golden/gcwrapper_reference_calls.json: what the reference's unmodified src_py/elf/utils_elf.py GCWrapper does on the
+    recording mock of tests/test_pybind_boundary.py (its calls, batch layout, name2idx, idx2name)"""
+    sys.path.insert(0, os.path.join(HERE, "..", "tests"))
+    import test_pybind_boundary as t
+    ref = t.load_reference_utils()
+    assert ref is not None, t.REF_UTILS
+    with open(os.path.join(OUT, "gcwrapper_reference_calls.json"), "w") as f:
+        json.dump(t.canonical_calls(t.wrapper_calls(ref, True)), f, indent=0)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["gcwrapper"]:
+        gcwrapper_calls()
+    else:
+        main()
+        gcwrapper_calls()

@@ -1,8 +1,10 @@
 """The reference's module names resolve to this library's pybind11 extensions (elf_amd/compat.py); SGF main-line reader; GTP
 coordinate letters.  The boundary itself is exercised in tests/test_pybind_boundary.py."""
-import glob
+import os
 
-import pytest
+import numpy as np
+
+from conftest import GOLDEN
 
 
 def test_reference_module_names_resolve(built):
@@ -23,18 +25,20 @@ def test_reference_module_names_resolve(built):
     assert GC.getParams()["num_action"] == 362 and GC.getParams()["ACTION_PASS"] == -99
 
 
-def test_sgf_main_line_matches_reference_loader(built):
-    """the preload_sgf reader of the boundary against the reference's own Sgf loader (via oracle/_ref) on ladder-suite files"""
+def test_sgf_main_line_matches_reference_loader(built, tmp_path):
+    """the preload_sgf reader of the boundary against the reference's own Sgf loader on ladder-suite files: the first 25 files
+    of tests/golden/sgf_ladder_texts.npz with the main lines the reference replayed from them (oracle/gen_golden.py)"""
     from elf_amd import compat
-    from pyoracle import Ref
     compat.install_reference_module_names()
     import _elf
-    files = sorted(glob.glob("/root/reference/ladder_suite/ladder/*.sgf"))[:25]
-    if not files or not Ref.available(19):
-        pytest.skip("reference tree / oracle/_ref not present")
-    R = Ref(19)
-    for f in files:
-        mv, _ = R.sgf_moves(f)
+    g = np.load(os.path.join(GOLDEN, "sgf_ladder_texts.npz"))
+    t, m = g["text_offsets"], g["main_line_offsets"]
+    assert len(m) == 26
+    for i in range(25):
+        f = str(tmp_path / str(g["names"][i]))
+        with open(f, "wb") as fh:
+            fh.write(g["text"][t[i]:t[i + 1]].tobytes())
+        mv = g["main_line"][m[i]:m[i + 1]]
         assert list(_elf._go.sgf_main_line(f, 19)) == [int(c) for c in mv], f
 
 

@@ -6,6 +6,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -156,6 +157,50 @@ def test_stub_line(tmp_path):
     assert rep["n_gpus"] == 1 and rep["steps"] == 3 and full["metric"] == rep["metric"]
 
 
+def test_dump_outputs_belongs_to_the_headline(tmp_path):
+    """--dump-outputs writes the headline's outputs: asking for it with another workload is a usage error, before any work"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "stub", "--dump-outputs", str(tmp_path / "out")],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr and not (tmp_path / "out").exists()
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run (no --full) times the headline only -- no sub-results, no CPU baseline, no in-run parity check -- and
+    --dump-outputs writes the last timed step's outputs as float32 / float64 .npy files under 64 MB; two runs with the same
+    arguments write the same arrays (seeded inputs; pseudo-random replies keep the net out of the comparison)."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--games", "64", "--rollouts", "64", "--net", "random",
+           "--steps", "4", "--warmup", "2"]
+    dumps = []
+    for k in range(2):
+        env = dict(os.environ, ELF_BENCH_FULL=str(tmp_path / ("full%d.json" % k)))
+        out = tmp_path / ("out%d" % k)
+        r = subprocess.run(cmd + ["--dump-outputs", str(out)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rep, full = one_line(r.stdout, env)
+        assert rep["steps"] == 4 and rep["warmup"] == 2 and rep["ms_per_step"] > 0 and rep["unit"] == "rollouts/s"
+        assert "sub" not in rep and rep["cpu_baseline"] is None and "parity" not in full
+        files = sorted(os.listdir(out))
+        assert files == sorted(n + ".npy" for n in full["dumped_outputs"]["files"]) and "leaf_features.npy" in files
+        assert sum(os.path.getsize(out / f) for f in files) < 64 << 20
+        arrs = {f: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert arrs["leaf_features.npy"].shape == (1024, 18, 19, 19) and arrs["last_moves.npy"].shape == (64,)
+        # the contents: 64 games x 16 rollouts fill at most 1024 rows, the sample is all of them
+        assert np.array_equal(arrs["sample_rows.npy"], np.arange(1024)) and 0 < arrs["leaf_rows.npy"][0] <= 1024
+        feat = arrs["leaf_features.npy"][:int(arrs["leaf_rows.npy"][0])]
+        assert feat.any() and np.isin(feat, (0.0, 1.0)).all()               # AGZ planes are 0/1
+        assert np.allclose(arrs["net_policy.npy"].sum(axis=1), 1.0, atol=1e-4) and (np.abs(arrs["net_value.npy"]) <= 1).all()
+        counters = arrs["selfplay_counters.npy"][0]                          # moves, games, rollouts, rows, steps, node_visits, boundaries
+        win = full["selfplay_stats_window"]
+        assert counters[2] >= win["rollouts"] > 0 and counters[5] >= win["node_visits"] > 0 and counters[4] >= 4 + 2
+        played = (arrs["last_moves.npy"] >= 0).sum()
+        assert 0 < played <= counters[0]
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
 @pytest.mark.gpu
 def test_two_ranks_share_the_gpu_on_the_real_workloads(tmp_path):
     """The world > 1 branches of run_mcts / run_games on real kernels: two ranks on the one GPU of this box (ELF_BENCH_SHARE_GPU=1,
@@ -164,7 +209,7 @@ def test_two_ranks_share_the_gpu_on_the_real_workloads(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["ELF_BENCH_SHARE_GPU"] = "1"
     env["ELF_BENCH_FULL"] = str(tmp_path / "full.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "both", "--games", "32", "--groups", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "both", "--full", "--games", "32", "--groups", "2",
                         "--rollouts", "64", "--steps", "6", "--warmup", "2", "--net-blocks", "2", "--net-dim", "32",
                         "--games-rollouts", "16", "--games-cutoff", "6", "--games-generations", "2"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)

@@ -220,47 +220,69 @@ class _Rec:
         return SM()
 
 
-def test_restated_wrapper_makes_the_reference_s_calls():
-    """tests/gcwrapper_restated.py against the reference's unmodified utils_elf.py on a recording mock: same calls, same order,
-    same arguments, same resulting batch layout (skipped where /root/reference is absent, i.e. on the GPU box)."""
-    ref = load_reference_utils()
-    if ref is None:
-        pytest.skip("/root/reference not present")
-    import gcwrapper_restated as mine
+def wrapper_calls(mod, is_ref):
+    """What GCWrapper.__init__ of `mod` does on the recording mock: (calls, batch layout, name2idx, idx2name), JSON-normalised"""
+    import json
     fields = {"s": ("float", [16, 18, 19, 19]), "pi": ("float", [16, 362]), "V": ("float", [16]), "a": ("int64_t", [16]), "rv": ("int64_t", [16]),
               "black_ver": ("int64_t", [16]), "white_ver": ("int64_t", [16])}
-    out = []
-    for mod in (ref, mine):
-        log = []
-        ctx = _Rec(log, fields)
+    log = []
+    ctx = _Rec(log, fields)
 
-        class GC:
-            def ctx(self_inner):
-                return ctx
-        if mod is ref:
-            import contextlib
-            import io
-            with contextlib.redirect_stdout(io.StringIO()):          # Allocator prints every field
-                w = mod.GCWrapper(GC(), 16, game_py_desc(16), num_recv=2, gpu=None, use_numpy=False, params={})
-        else:
-            w = mod.GCWrapper(GC(), 16, game_py_desc(16), num_recv=2, gpu=None, params={})
-        layout = [({k: (tuple(t.shape), str(t.dtype)) for k, t in b["input"].items()}, {k: (tuple(t.shape), str(t.dtype)) for k, t in b["reply"].items()})
-                  for b in w.batches]
-        out.append((log, layout, dict(w.name2idx), dict(w.idx2name)))
-        assert w.reg_callback("actor_black", lambda b: None) and not w.reg_callback_if_exists("nope", None)
-        with pytest.raises(ValueError):
-            w.reg_callback("nope", None)
-        with pytest.raises(ValueError):
-            w.start()                                                # callbacks missing (utils_elf.py:416-424)
-    assert out[0] == out[1]
+    class GC:
+        def ctx(self_inner):
+            return ctx
+    if is_ref:
+        import contextlib
+        import io
+        with contextlib.redirect_stdout(io.StringIO()):          # Allocator prints every field
+            w = mod.GCWrapper(GC(), 16, game_py_desc(16), num_recv=2, gpu=None, use_numpy=False, params={})
+    else:
+        w = mod.GCWrapper(GC(), 16, game_py_desc(16), num_recv=2, gpu=None, params={})
+    layout = [({k: (tuple(t.shape), str(t.dtype)) for k, t in b["input"].items()}, {k: (tuple(t.shape), str(t.dtype)) for k, t in b["reply"].items()})
+              for b in w.batches]
+    assert w.reg_callback("actor_black", lambda b: None) and not w.reg_callback_if_exists("nope", None)
+    with pytest.raises(ValueError):
+        w.reg_callback("nope", None)
+    with pytest.raises(ValueError):
+        w.start()                                                # callbacks missing (utils_elf.py:416-424)
+    return json.loads(json.dumps([log, layout, dict(w.name2idx), dict(w.idx2name)]))
+
+
+def canonical_calls(calls):
+    """wrapper_calls without the order that follows Python's set iteration (string hashing, PYTHONHASHSEED): the keys of each
+    allocateSharedMem and the run of `set` calls after it are sorted"""
+    out, run = [], []
+    for e in calls[0]:
+        if e[0] == "set":
+            run.append(e)
+            continue
+        out += sorted(run)
+        run = []
+        out.append([e[0], e[1], sorted(e[2])] if e[0] == "allocateSharedMem" else e)
+    return [out + sorted(run)] + calls[1:]
+
+
+REF_CALLS = os.path.join(GOLDEN, "gcwrapper_reference_calls.json")   # wrapper_calls of the reference's utils_elf.py (oracle/gen_golden_wire.py)
+
+
+def test_restated_wrapper_makes_the_reference_s_calls():
+    """tests/gcwrapper_restated.py against the reference's unmodified utils_elf.py on a recording mock: same calls, same order,
+    same arguments, same resulting batch layout -- against the file itself where the reference tree is present, and always against
+    the calls it was recorded to make (tests/golden/gcwrapper_reference_calls.json, in an order free of string hashing)."""
+    import json
+    import gcwrapper_restated as mine
+    got = wrapper_calls(mine, False)
+    assert canonical_calls(got) == json.load(open(REF_CALLS))
+    ref = load_reference_utils()
+    if ref is not None:
+        assert wrapper_calls(ref, True) == got
 
 
 def test_reference_gcwrapper_allocates_against_the_context(mods):
     """The reference's unmodified GCWrapper.__init__ (Allocator.spec2batches) against the real pybind Context: every tensor it
-    allocates gets registered (address + byte strides), indices and labels come back as the reference's would."""
-    ref = load_reference_utils()
-    if ref is None:
-        pytest.skip("/root/reference not present")
+    allocates gets registered (address + byte strides), indices and labels come back as the reference's would.  Where
+    the reference tree is absent, its restatement (checked call for call against the original above) stands in, as on the GPU."""
+    ref, is_ref = _wrapper_module()
     _elf, go, _ = mods
     import contextlib
     import io
@@ -269,7 +291,7 @@ def test_reference_gcwrapper_allocates_against_the_context(mods):
     co.mcts_options.num_threads, co.mcts_options.num_rollouts_per_batch = 1, 16
     GC = go.GameContext(co, opt)
     with contextlib.redirect_stdout(io.StringIO()):
-        w = ref.GCWrapper(GC, 128, game_py_desc(128), num_recv=2, gpu=None, use_numpy=False, params=GC.getParams())
+        w = ref.GCWrapper(GC, 128, game_py_desc(128), num_recv=2, gpu=None, params=GC.getParams(), **({"use_numpy": False} if is_ref else {}))
     assert len(w.batches) == 8 and w.name2idx["actor_black"] == [0, 1] and w.name2idx["game_start"] == [6, 7] and w.idx2name[4] == "game_end"
     assert tuple(w.batches[0]["input"]["s"].shape) == (128, 18, 19, 19) and tuple(w.batches[1]["reply"]["pi"].shape) == (128, 362)
     assert w.batches[6]["input"]["black_ver"].dtype.is_floating_point is False and w.batches[4]["input"] == {}

@@ -2,13 +2,28 @@
 The four cases of the reference's own sgf/sgf_test.cc (gtest is absent in the image, so they are restated here: the texts are
 the test's, the replay runs on the CPU oracle) and, where oracle/_ref is present, a differential against the real loader on
 hand-made texts (comments with brackets, escapes, variations, setup stones, blanks inside moves) and on the ladder suite."""
-import glob
 import os
 
 import numpy as np
 import pytest
 
+from conftest import GOLDEN
 from pyoracle import Port, Ref
+
+
+def ladder_texts():
+    """tests/golden/sgf_ladder_texts.npz (oracle/gen_golden.py): the first 60 ladder-suite SGF texts and what the reference's
+    Sgf::load made of each -> [(name, text, (moves, players, header))]"""
+    g = np.load(os.path.join(GOLDEN, "sgf_ladder_texts.npz"))
+    t, p = g["text_offsets"], g["parse_offsets"]
+    out = []
+    for i, name in enumerate(g["names"]):
+        text = g["text"][t[i]:t[i + 1]].tobytes().decode("latin-1")
+        h = g["parse_header"][i]
+        want = (g["parse_moves"][p[i]:p[i + 1]], g["parse_players"][p[i]:p[i + 1]],
+                dict(size=int(h[0]), komi=float(h[1]), handi=int(h[2]), winner=int(h[3]), win_margin=float(h[4])))
+        out.append((str(name), text, want))
+    return out
 
 MAKE_SGF = ("(;CA[UTF-8]SZ[9]PB[Murakawa Daisuke]PW[Iyama Yuta]KM[6.5]HA[0]RE[W+1.5]GM[1];"
             "B[fd];W[cf];B[eg];W[dd];B[dc];W[cc];B[de];W[cd];B[ed];W[he];B[ce];W[be];B[df];W[bf];"
@@ -88,13 +103,23 @@ def test_differential_against_the_reference_loader(built):
         assert len(got[0]) == len(wm), t
         assert np.array_equal(got[1][has_move], wm[has_move]) and np.array_equal(got[0][has_move], wp[has_move]), t
         assert got[2] == pytest.approx(wh), t
-    files = sorted(glob.glob("/root/reference/ladder_suite/*/*.sgf"))
     R19 = Ref(19)
-    for f in files[:60]:
-        text = open(f, encoding="latin-1").read()
+    for f, text, _ in ladder_texts():
         wm, wp, wh = R19.sgf_parse(text)
         pl, mv, h = parse_sgf(19, text)
         ok = pl != 0                    # (a trailing node without a move is uninitialised memory in the reference)
+        assert len(mv) == len(wm) and np.array_equal(mv[ok], wm[ok]) and np.array_equal(pl[ok], wp[ok]) and h == pytest.approx(wh), f
+        assert ok.sum() >= len(mv) - 1
+
+
+def test_ladder_suite_against_the_recorded_reference_loader(built):
+    """the same 60 ladder-suite files against the reference loader's recorded results (runs where oracle/_ref is absent)"""
+    from elf_amd.train import parse_sgf
+    cases = ladder_texts()
+    assert len(cases) == 60
+    for f, text, (wm, wp, wh) in cases:
+        pl, mv, h = parse_sgf(19, text)
+        ok = pl != 0
         assert len(mv) == len(wm) and np.array_equal(mv[ok], wm[ok]) and np.array_equal(pl[ok], wp[ok]) and h == pytest.approx(wh), f
         assert ok.sum() >= len(mv) - 1
 

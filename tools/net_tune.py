@@ -1,7 +1,7 @@
 """GPU-box helper: exhaustive MIOpen tuning of the benchmark net's convolution shapes (BASELINE configs[2]: 20 blocks x 256
 channels, fp16 channels_last, 2048 positions per call), writing MIOpen's user databases to the directory given as argv[1].
-The tuned databases are committed under elf_amd/data/miopen_db/ and bench.py points MIOPEN_USER_DB_PATH at them, so a fresh
-box runs the tuned kernels without searching.  Usage: python tools/net_tune.py <db_dir> [rows]"""
+The databases are committed under elf_amd/data/miopen_db/ and bench.py copies them into the user database directory where
+none of that name exists, so a fresh box runs the recorded kernels without searching.  Usage: python tools/net_tune.py <db_dir> [rows]"""
 import os
 import sys
 import time

@@ -6,7 +6,7 @@
 #     cp gpurun_out/<tag>/{pytest_gpu.txt,bench_line.json,bench_full.json,summary_*.txt} profiles/ with the <tag>_ prefix
 # Steps
 #   tests     python -m pytest tests -m gpu                                          -> pytest_gpu.txt
-#   bench     the default `python bench.py` (the driver's command)                   -> bench_line.json, bench_full.json
+#   bench     `python bench.py --full` (headline + every sub-result)                 -> bench_line.json, bench_full.json
 #   stats     rocprofv3 --kernel-trace --stats of board / board9 / search-only / train / features  -> summary_<w>.txt
 #   pmc       separate --pmc passes (FETCH_SIZE, WRITE_SIZE, LDS, SQ issue) of the same commands   -> pmc_*/ (never combined with a trace)
 #   chase     tools/chase.hip: ns per dependent load by footprint and number of chasing waves     -> chase.txt, chase.json
@@ -38,7 +38,7 @@ if has tests; then
   timeout 300 python -c 'import __graft_entry__ as g; g.smoke()' 2>&1 | tail -2 >> $OUT/pytest_gpu.txt
 fi
 if has bench; then
-  ( time ELF_BENCH_FULL=$OUT/bench_full.json timeout 1500 python bench.py > $OUT/bench_line.json 2> $OUT/bench.err ) 2> $OUT/bench.time
+  ( time ELF_BENCH_FULL=$OUT/bench_full.json timeout 1500 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err ) 2> $OUT/bench.time
   tail -3 $OUT/bench.time; wc -c $OUT/bench_line.json
 fi
 if has stats || has pmc; then
