@@ -97,17 +97,34 @@ struct SpGame {
   }
 };
 
+// A device buffer and its host mirror: size, allocation, free and the two copy directions of a scratch array come from its one
+// declaration.  The copies are queued on the stream and move the first n elements (up: from the mirror or from a list of the
+// caller's, down: into the mirror); nothing here waits.
+template <class T>
+struct SpBuf {
+  T* d = nullptr;
+  std::vector<T> h;
+  SpBuf() = default;
+  SpBuf(const SpBuf&) = delete;
+  SpBuf& operator=(const SpBuf&) = delete;
+  ~SpBuf() { release(); }
+  hipError_t alloc(size_t n, T fill = T()) { h.assign(n, fill); return hipMalloc((void**)&d, sizeof(T) * n); }
+  void release() { if (d) (void)hipFree(d); d = nullptr; }
+  hipError_t up(size_t n, hipStream_t s, const T* src) { return hipMemcpyAsync(d, src, sizeof(T) * n, hipMemcpyHostToDevice, s); }
+  hipError_t up(size_t n, hipStream_t s) { return up(n, s, h.data()); }
+  hipError_t down(size_t n, hipStream_t s) { return hipMemcpyAsync(h.data(), d, sizeof(T) * n, hipMemcpyDeviceToHost, s); }
+};
+
 struct SpPool {              // one MCTSGoAI role: its tree pool and options
   ElfMcts* mcts = nullptr;
   ElfMctsOptions mo{};
   int rollouts_per_thread = 0, K = 0, T = 1, KT = 0, steps_per_move = 0, W = 0;
-  int32_t* d_counts = nullptr;           // [4]: rows, error bits, running total of rows (u64)
-  int32_t h_counts[2] = {0, 0};
+  SpBuf<int32_t> counts;                 // [4]: rows, error bits, running total of rows (u64)
   int last_rows = 0;                     // rows of the last select, -1 = left on the device
-  uint8_t *d_start = nullptr, *d_active = nullptr;
-  int64_t* d_ver = nullptr;
-  std::vector<uint8_t> h_start, h_active, up_active;   // up_active: what d_active holds
-  std::vector<int64_t> h_ver, up_ver;
+  SpBuf<uint8_t> start, active;
+  SpBuf<int64_t> ver;
+  std::vector<uint8_t> up_active;        // what active.d holds
+  std::vector<int64_t> up_ver;
   std::vector<uint8_t> h_d4;
   std::vector<int32_t> h_tdraws;         // [G][T] D4 draws per search thread of the move that just ended (elfmcts_thread_draws)
   int n_active = 0;
@@ -122,15 +139,11 @@ struct ElfSelfPlay {
   int G = 0, NE = 0, NA = 0;
   hipStream_t stream = nullptr;
   std::vector<SpGame> games;
-  // device scratch
-  int32_t* d_info = nullptr;     // [G][8]
-  int32_t *d_coord = nullptr, *d_visits = nullptr, *d_moves = nullptr, *d_ids = nullptr, *d_binfo = nullptr;
-  float *d_prior = nullptr, *d_reward = nullptr, *d_etas = nullptr, *d_Z = nullptr, *d_val = nullptr;
-  uint8_t* d_ok = nullptr;
-  // host mirrors
-  std::vector<int32_t> h_info, h_coord, h_visits, h_moves, h_binfo;
-  std::vector<float> h_prior, h_reward, h_etas, h_Z, h_val;
-  std::vector<uint8_t> h_ok;
+  // device scratch with its host mirrors (ids is only ever uploaded from the callers' own lists)
+  SpBuf<int32_t> info;           // [G][8]
+  SpBuf<int32_t> coord, visits, moves, ids, binfo;
+  SpBuf<float> prior, reward, etas, Z, val;
+  SpBuf<uint8_t> ok;
   bool step_open = false;        // between begin_step and end_step
   // requests: `cur` is the one being delivered (every game must receive it before the next one goes out, dispatcher.h:104-152)
   std::deque<SpRequest> mailbox;
@@ -180,8 +193,45 @@ static void sp_for_games(const std::vector<int32_t>& ids, F fn) {
   HostWorkers::get().run(n, nt, [&](size_t i) { fn(ids[i]); });
 }
 
-static ElfTsOptions sp_ts_of(const ElfSpOptions& o);
-static bool sp_ts_pool_equal(const ElfTsOptions& a, const ElfTsOptions& b);
+// The twelve fields of a request's TSOptions that the tree pools are built from, each next to the field of ElfSpOptions it lives in
+// (`flag`: a bool of the reference, any non-zero value is true).  max_num_moves, seed, verbose*, log_prefix take part in
+// ModelPair::operator== (sp_ts_equal) but never in the shape of a pool.
+template <class T, class O, class F>   // ElfTsOptions, ElfSpOptions, either of them const or not
+static void sp_ts_fields(T& t, O& o, F f) {
+  f(t.num_threads, o.mcts.num_threads, false); f(t.num_rollouts_per_thread, o.num_rollouts_per_thread, false);
+  f(t.num_rollouts_per_batch, o.mcts.num_rollouts_per_batch, false); f(t.persistent_tree, o.persistent_tree, true);
+  f(t.pick_method, o.pick_method, false); f(t.root_epsilon, o.root_epsilon, false); f(t.root_alpha, o.root_alpha, false);
+  f(t.virtual_loss, o.mcts.virtual_loss, false); f(t.use_prior, o.mcts.use_prior, true); f(t.c_puct, o.mcts.c_puct, false);
+  f(t.unexplored_q_zero, o.mcts.unexplored_q_zero, true); f(t.root_unexplored_q_zero, o.mcts.root_unexplored_q_zero, true);
+}
+// TSOptions <-> the fields of ElfSpOptions they live in
+static void sp_ts_from(ElfTsOptions* t, const ElfSpOptions& o) {
+  sp_ts_fields(*t, o, [](auto& tf, const auto& of, bool flag) { tf = flag ? of != 0 : of; });
+}
+static ElfTsOptions sp_ts_of(const ElfSpOptions& o) {
+  ElfTsOptions t;
+  memset(&t, 0, sizeof(t));
+  sp_ts_from(&t, o);
+  return t;
+}
+static void sp_ts_into(const ElfTsOptions& t, ElfSpOptions* o) {
+  sp_ts_fields(t, *o, [](const auto& tf, auto& of, bool flag) { of = flag ? tf != 0 : tf; });
+}
+// do the pools built from `o` have the shape TSOptions `t` asks for?
+static bool sp_ts_pool_equal(const ElfTsOptions& t, const ElfSpOptions& o) {
+  bool eq = true;
+  sp_ts_fields(t, o, [&](const auto& tf, const auto& of, bool flag) { eq = eq && (flag ? (tf != 0) == (of != 0) : tf == of); });
+  return eq;
+}
+static bool sp_ts_equal(const ElfTsOptions& a, const ElfTsOptions& b) {      // TSOptions::operator== (tree_search_options.h:133-180)
+  return a.max_num_moves == b.max_num_moves && a.num_threads == b.num_threads && a.num_rollouts_per_thread == b.num_rollouts_per_thread &&
+         a.num_rollouts_per_batch == b.num_rollouts_per_batch && (a.verbose != 0) == (b.verbose != 0) && (a.verbose_time != 0) == (b.verbose_time != 0) &&
+         a.seed == b.seed && (a.persistent_tree != 0) == (b.persistent_tree != 0) && a.pick_method == b.pick_method &&
+         !strncmp(a.log_prefix, b.log_prefix, sizeof(a.log_prefix)) && a.root_epsilon == b.root_epsilon && a.root_alpha == b.root_alpha &&
+         a.virtual_loss == b.virtual_loss && (a.use_prior != 0) == (b.use_prior != 0) && a.c_puct == b.c_puct &&
+         (a.unexplored_q_zero != 0) == (b.unexplored_q_zero != 0) && (a.root_unexplored_q_zero != 0) == (b.root_unexplored_q_zero != 0);
+}
+
 static SpRecordMeta sp_meta(const ElfSelfPlay* sp, const SpGame& gm) {
   // Record.request = curr_request_ (go_state_ext.h:134): the game's own request incl. the mcts_opt it carried
   SpRecordMeta m = elfrec_meta_from_options(sp->opt);
@@ -194,13 +244,7 @@ static SpRecordMeta sp_meta(const ElfSelfPlay* sp, const SpGame& gm) {
   // some games while the rest played on could not rebuild the context's tree pools (sp_poll_requests, "deferred"); those games'
   // records carry the search options that were actually used, not the ones the request asked for
   ElfTsOptions used = gm.req.ts;
-  const ElfTsOptions ctx = sp_ts_of(sp->opt);
-  if (!sp_ts_pool_equal(used, ctx)) {
-    used.num_threads = ctx.num_threads; used.num_rollouts_per_thread = ctx.num_rollouts_per_thread; used.num_rollouts_per_batch = ctx.num_rollouts_per_batch;
-    used.persistent_tree = ctx.persistent_tree; used.pick_method = ctx.pick_method; used.root_epsilon = ctx.root_epsilon; used.root_alpha = ctx.root_alpha;
-    used.virtual_loss = ctx.virtual_loss; used.use_prior = ctx.use_prior; used.c_puct = ctx.c_puct; used.unexplored_q_zero = ctx.unexplored_q_zero;
-    used.root_unexplored_q_zero = ctx.root_unexplored_q_zero;
-  }
+  if (!sp_ts_pool_equal(used, sp->opt)) sp_ts_from(&used, sp->opt);
   elfrec_meta_set_ts(&m, used);
   return m;
 }
@@ -238,16 +282,16 @@ static void sp_state_restart(SpGame& gm) {
 static int sp_forward_preload(ElfSelfPlay* sp, const std::vector<int32_t>& ids) {
   const int k = (int)ids.size(), n = (int)sp->sgf.size();
   if (k == 0) return 0;
-  HIPCHK(hipMemcpyAsync(sp->d_ids, ids.data(), 4 * k, hipMemcpyHostToDevice, sp->stream));
+  HIPCHK(sp->ids.up(k, sp->stream, ids.data()));
   int fwd = 0;
   for (; fwd < n && fwd < sp->sgf_move_to; ++fwd) {            // while (!_sgf_iter.done() && i < preload_sgf_move_to)
     std::vector<int32_t> mv(k, (int32_t)sp->sgf[fwd]);
-    HIPCHK(hipMemcpyAsync(sp->d_moves, mv.data(), 4 * k, hipMemcpyHostToDevice, sp->stream));
-    SPCHK(elfgo_forward(sp->eng, sp->d_ids, sp->d_moves, k, sp->d_ok, sp->stream));
-    HIPCHK(hipMemcpyAsync(sp->h_ok.data(), sp->d_ok, k, hipMemcpyDeviceToHost, sp->stream));
+    HIPCHK(sp->moves.up(k, sp->stream, mv.data()));
+    SPCHK(elfgo_forward(sp->eng, sp->ids.d, sp->moves.d, k, sp->ok.d, sp->stream));
+    HIPCHK(sp->ok.down(k, sp->stream));
     HIPCHK(hipStreamSynchronize(sp->stream));
     for (int j = 0; j < k; ++j)
-      if (sp->h_ok[j] != 1) return ELFGO_E_MCTS_BASE - ELFMCTS_E_FORWARD;   // "Preload sgf: move not valid!" :211-215
+      if (sp->ok.h[j] != 1) return ELFGO_E_MCTS_BASE - ELFMCTS_E_FORWARD;   // "Preload sgf: move not valid!" :211-215
     for (int g : ids) {
       sp->games[g].ply++;
       if (sp->opt.keep_records > 0) sp->games[g].rec.moves.push_back((uint16_t)sp->sgf[fwd]);
@@ -259,39 +303,6 @@ static int sp_forward_preload(ElfSelfPlay* sp, const std::vector<int32_t>& ids) 
 
 // effective options of the "actor_white" AI: init_ai's overrides (game_selfplay.cc:51-70) of GameOptions.white_puct /
 // white_mcts_rollout_per_batch / white_mcts_rollout_per_thread
-// TSOptions <-> the fields of ElfSpOptions they live in
-static ElfTsOptions sp_ts_of(const ElfSpOptions& o) {
-  ElfTsOptions t;
-  memset(&t, 0, sizeof(t));
-  t.num_threads = o.mcts.num_threads; t.num_rollouts_per_thread = o.num_rollouts_per_thread; t.num_rollouts_per_batch = o.mcts.num_rollouts_per_batch;
-  t.persistent_tree = o.persistent_tree != 0; t.pick_method = o.pick_method; t.root_epsilon = o.root_epsilon; t.root_alpha = o.root_alpha;
-  t.virtual_loss = o.mcts.virtual_loss; t.use_prior = o.mcts.use_prior != 0; t.unexplored_q_zero = o.mcts.unexplored_q_zero != 0;
-  t.root_unexplored_q_zero = o.mcts.root_unexplored_q_zero != 0; t.c_puct = o.mcts.c_puct;
-  return t;
-}
-static void sp_ts_into(const ElfTsOptions& t, ElfSpOptions* o) {
-  o->mcts.num_threads = t.num_threads; o->num_rollouts_per_thread = t.num_rollouts_per_thread; o->mcts.num_rollouts_per_batch = t.num_rollouts_per_batch;
-  o->persistent_tree = t.persistent_tree != 0; o->pick_method = t.pick_method; o->root_epsilon = t.root_epsilon; o->root_alpha = t.root_alpha;
-  o->mcts.virtual_loss = t.virtual_loss; o->mcts.use_prior = t.use_prior != 0; o->mcts.unexplored_q_zero = t.unexplored_q_zero != 0;
-  o->mcts.root_unexplored_q_zero = t.root_unexplored_q_zero != 0; o->mcts.c_puct = t.c_puct;
-}
-// the fields of a request's TSOptions that the tree pools are built from (what sp_ts_into stores): max_num_moves, seed, verbose*,
-// log_prefix take part in ModelPair::operator== (sp_ts_equal) but never in the shape of a pool
-static bool sp_ts_pool_equal(const ElfTsOptions& a, const ElfTsOptions& b) {
-  return a.num_threads == b.num_threads && a.num_rollouts_per_thread == b.num_rollouts_per_thread && a.num_rollouts_per_batch == b.num_rollouts_per_batch &&
-         (a.persistent_tree != 0) == (b.persistent_tree != 0) && a.pick_method == b.pick_method && a.root_epsilon == b.root_epsilon &&
-         a.root_alpha == b.root_alpha && a.virtual_loss == b.virtual_loss && (a.use_prior != 0) == (b.use_prior != 0) && a.c_puct == b.c_puct &&
-         (a.unexplored_q_zero != 0) == (b.unexplored_q_zero != 0) && (a.root_unexplored_q_zero != 0) == (b.root_unexplored_q_zero != 0);
-}
-static bool sp_ts_equal(const ElfTsOptions& a, const ElfTsOptions& b) {      // TSOptions::operator== (tree_search_options.h:133-180)
-  return a.max_num_moves == b.max_num_moves && a.num_threads == b.num_threads && a.num_rollouts_per_thread == b.num_rollouts_per_thread &&
-         a.num_rollouts_per_batch == b.num_rollouts_per_batch && (a.verbose != 0) == (b.verbose != 0) && (a.verbose_time != 0) == (b.verbose_time != 0) &&
-         a.seed == b.seed && (a.persistent_tree != 0) == (b.persistent_tree != 0) && a.pick_method == b.pick_method &&
-         !strncmp(a.log_prefix, b.log_prefix, sizeof(a.log_prefix)) && a.root_epsilon == b.root_epsilon && a.root_alpha == b.root_alpha &&
-         a.virtual_loss == b.virtual_loss && (a.use_prior != 0) == (b.use_prior != 0) && a.c_puct == b.c_puct &&
-         (a.unexplored_q_zero != 0) == (b.unexplored_q_zero != 0) && (a.root_unexplored_q_zero != 0) == (b.root_unexplored_q_zero != 0);
-}
-
 static void sp_pool_options(const ElfSpOptions& o, int a, ElfMctsOptions* mo, int* rollouts_per_thread) {
   *mo = o.mcts;
   *rollouts_per_thread = o.num_rollouts_per_thread;
@@ -303,9 +314,7 @@ static void sp_pool_options(const ElfSpOptions& o, int a, ElfMctsOptions* mo, in
 }
 
 static void sp_pool_free(SpPool& p) {
-  void* ptrs[] = {p.d_counts, p.d_start, p.d_active, p.d_ver};
-  for (void* q : ptrs) if (q) (void)hipFree(q);
-  p.d_counts = nullptr; p.d_start = p.d_active = nullptr; p.d_ver = nullptr;
+  p.counts.release(); p.start.release(); p.active.release(); p.ver.release();
   if (p.mcts) elfmcts_destroy(p.mcts);
   p.mcts = nullptr;
 }
@@ -324,15 +333,25 @@ static int sp_pool_create(ElfSelfPlay* sp, int a) {
     int fmt = 0;
     if (elfmcts_get_feature_format(sp->pool[0].mcts, &fmt) == 0) (void)elfmcts_set_feature_format(p.mcts, fmt);
   }
-  HIPCHK(hipMalloc((void**)&p.d_counts, 16));
-  HIPCHK(hipMemset(p.d_counts, 0, 16));
-  HIPCHK(hipMalloc((void**)&p.d_start, G));
-  HIPCHK(hipMalloc((void**)&p.d_active, G));
-  HIPCHK(hipMalloc((void**)&p.d_ver, 8 * (size_t)G));
-  p.h_start.assign(G, 0); p.h_active.assign(G, 0); p.up_active.assign(G, 0xFF);
-  p.h_ver.assign(G, -1); p.up_ver.assign(G, -2);
+  HIPCHK(p.counts.alloc(4));
+  HIPCHK(hipMemset(p.counts.d, 0, sizeof(int32_t) * 4));
+  HIPCHK(p.start.alloc(G));
+  HIPCHK(p.active.alloc(G));
+  HIPCHK(p.ver.alloc(G, -1));
+  p.up_active.assign(G, 0xFF); p.up_ver.assign(G, -2);
   p.h_d4.assign((size_t)G * p.W, 0);
   p.h_tdraws.assign((size_t)G * p.T, 0);
+  return 0;
+}
+
+// the listed games go back to the empty board and lose the trees of both AIs (GoState::reset; _ai->endGame / _ai2->endGame = resetTree)
+static int sp_reset_boards_and_trees(ElfSelfPlay* sp, const std::vector<int32_t>& ids) {
+  const int k = (int)ids.size();
+  HIPCHK(sp->ids.up(k, sp->stream, ids.data()));
+  SPCHK(elfgo_reset(sp->eng, sp->ids.d, k, sp->stream));
+  for (int a = 0; a < 2; ++a)
+    if (sp->pool[a].mcts) SPCHK(elfmcts_clear(sp->pool[a].mcts, sp->ids.d, k, sp->stream));
+  HIPCHK(hipStreamSynchronize(sp->stream));   // ids may be a temporary
   return 0;
 }
 
@@ -364,11 +383,7 @@ static int sp_restart_games(ElfSelfPlay* sp, const std::vector<int32_t>& ids) {
     gm.sgf_iter = 0;
     gm.ai = -1;
   }
-  HIPCHK(hipMemcpyAsync(sp->d_ids, ids.data(), 4 * k, hipMemcpyHostToDevice, sp->stream));
-  SPCHK(elfgo_reset(sp->eng, sp->d_ids, k, sp->stream));
-  for (int a = 0; a < 2; ++a)
-    if (sp->pool[a].mcts) SPCHK(elfmcts_clear(sp->pool[a].mcts, sp->d_ids, k, sp->stream));
-  HIPCHK(hipStreamSynchronize(sp->stream));   // ids may be a temporary
+  SPCHK(sp_reset_boards_and_trees(sp, ids));
   if (!sp->sgf.empty()) SPCHK(sp_forward_preload(sp, ids));
   return 0;
 }
@@ -450,7 +465,7 @@ static int sp_poll_requests(ElfSelfPlay* sp) {
       // in the middle of play under the old options -- then every playing game is idle at the barrier and holds no tree.
       bool playing_on = false;
       for (const SpGame& gm : sp->games) playing_on = playing_on || gm.phase == PH_PLAY;
-      const bool ts_differ = !sp_ts_pool_equal(sp->cur.ts, sp_ts_of(sp->opt));
+      const bool ts_differ = !sp_ts_pool_equal(sp->cur.ts, sp->opt);
       if (sp->cur_n_restart > 0 && !playing_on && ts_differ) SPCHK(sp_apply_ts(sp, sp->cur.ts));
       else if (sp->cur_n_restart > 0 && playing_on && ts_differ) {
         // some games restarted under a request whose search options differ from the pools', while others play on under the old
@@ -467,13 +482,13 @@ static int sp_poll_requests(ElfSelfPlay* sp) {
 }
 
 static int sp_upload_masks(ElfSelfPlay* sp, SpPool& p) {
-  if (p.h_active != p.up_active) {
-    HIPCHK(hipMemcpyAsync(p.d_active, p.h_active.data(), sp->G, hipMemcpyHostToDevice, sp->stream));
-    p.up_active = p.h_active;
+  if (p.active.h != p.up_active) {
+    HIPCHK(p.active.up(sp->G, sp->stream));
+    p.up_active = p.active.h;
   }
-  if (p.h_ver != p.up_ver) {
-    HIPCHK(hipMemcpyAsync(p.d_ver, p.h_ver.data(), 8 * (size_t)sp->G, hipMemcpyHostToDevice, sp->stream));
-    p.up_ver = p.h_ver;
+  if (p.ver.h != p.up_ver) {
+    HIPCHK(p.ver.up(sp->G, sp->stream));
+    p.up_ver = p.ver.h;
   }
   return 0;
 }
@@ -504,54 +519,54 @@ static int sp_begin_searches(ElfSelfPlay* sp) {
     // MCTSAI_T::act -> align_state (mcts.h:141-167): advanceMoves happened when the moves were played (both trees follow every
     // move); a tree that is not persistent is reset now
     if (!sp->opt.persistent_tree) {
-      HIPCHK(hipMemcpyAsync(sp->d_ids, starting[a].data(), 4 * k, hipMemcpyHostToDevice, sp->stream));
-      SPCHK(elfmcts_clear(p.mcts, sp->d_ids, k, sp->stream));
+      HIPCHK(sp->ids.up(k, sp->stream, starting[a].data()));
+      SPCHK(elfmcts_clear(p.mcts, sp->ids.d, k, sp->stream));
       HIPCHK(hipStreamSynchronize(sp->stream));
     }
-    std::fill(p.h_start.begin(), p.h_start.end(), (uint8_t)GMASK_IDLE);
+    std::fill(p.start.h.begin(), p.start.h.end(), (uint8_t)GMASK_IDLE);
     bool any_search = false;
     for (int g : starting[a]) {
-      p.h_start[g] = sp->games[g].policy_only ? GMASK_POLICY_ONLY : GMASK_SEARCH;
-      p.h_active[g] = p.h_start[g];
-      p.h_ver[g] = sp->games[g].actor_ver[a];
+      p.start.h[g] = sp->games[g].policy_only ? GMASK_POLICY_ONLY : GMASK_SEARCH;
+      p.active.h[g] = p.start.h[g];
+      p.ver.h[g] = sp->games[g].actor_ver[a];
       any_search = any_search || !sp->games[g].policy_only;
     }
     const bool all = k == G;
-    if (!all) HIPCHK(hipMemcpyAsync(p.d_start, p.h_start.data(), G, hipMemcpyHostToDevice, sp->stream));
-    SPCHK(elfmcts_set_game_mask(p.mcts, all ? nullptr : p.d_start));
+    if (!all) HIPCHK(p.start.up(G, sp->stream));
+    SPCHK(elfmcts_set_game_mask(p.mcts, all ? nullptr : p.start.d));
     // TreeSearchT::run :410-417 / runPolicyOnly :385-392: setRootNodeState
     SPCHK(elfmcts_set_root(p.mcts, nullptr, sp->stream));
     if (sp->opt.root_epsilon > 0.0f && any_search) {
-      SPCHK(elfmcts_root(p.mcts, sp->d_info, nullptr, nullptr, nullptr, nullptr, nullptr, sp->stream));
-      HIPCHK(hipMemcpyAsync(sp->h_info.data(), sp->d_info, sizeof(int32_t) * G * ELFMCTS_ROOT_WORDS, hipMemcpyDeviceToHost, sp->stream));
+      SPCHK(elfmcts_root(p.mcts, sp->info.d, nullptr, nullptr, nullptr, nullptr, nullptr, sp->stream));
+      HIPCHK(sp->info.down((size_t)G * ELFMCTS_ROOT_WORDS, sp->stream));
       HIPCHK(hipStreamSynchronize(sp->stream));
       // NodeT::enhanceExploration (tree_search_node.h:132-155), draws from actors_[0]->rng(); not part of runPolicyOnly
       for (int g : starting[a])
-        if (sp->h_info[g * ELFMCTS_ROOT_WORDS + 6]) return ELFGO_E_MCTS_BASE - sp->h_info[g * ELFMCTS_ROOT_WORDS + 6];
+        if (sp->info.h[g * ELFMCTS_ROOT_WORDS + 6]) return ELFGO_E_MCTS_BASE - sp->info.h[g * ELFMCTS_ROOT_WORDS + 6];
       sp_for_games(starting[a], [&](int g) {
-        float* et = &sp->h_etas[(size_t)g * sp->NE];
-        if (sp->games[g].policy_only) { sp->h_Z[g] = 1.0f; return; }
-        const int n = sp->h_info[g * ELFMCTS_ROOT_WORDS + 0];
+        float* et = &sp->etas.h[(size_t)g * sp->NE];
+        if (sp->games[g].policy_only) { sp->Z.h[g] = 1.0f; return; }
+        const int n = sp->info.h[g * ELFMCTS_ROOT_WORDS + 0];
         std::gamma_distribution<> dis(sp->opt.root_alpha);
         float Z = 1e-10;
         for (int i = 0; i < n; ++i) {
           et[i] = dis(sp->games[g].actor_rng[a]);
           Z += et[i];
         }
-        sp->h_Z[g] = Z;
+        sp->Z.h[g] = Z;
       });
       // policy-only games of this batch must not receive noise: they are masked out for the noise launch
       bool mixed = false;
       for (int g : starting[a]) mixed = mixed || sp->games[g].policy_only;
       if (mixed) {
-        std::vector<uint8_t> m2(p.h_start);
+        std::vector<uint8_t> m2(p.start.h);
         for (int g : starting[a]) if (sp->games[g].policy_only) m2[g] = GMASK_IDLE;
-        HIPCHK(hipMemcpyAsync(p.d_start, m2.data(), G, hipMemcpyHostToDevice, sp->stream));
-        SPCHK(elfmcts_set_game_mask(p.mcts, p.d_start));
+        HIPCHK(p.start.up(G, sp->stream, m2.data()));
+        SPCHK(elfmcts_set_game_mask(p.mcts, p.start.d));
       }
-      HIPCHK(hipMemcpyAsync(sp->d_etas, sp->h_etas.data(), sizeof(float) * (size_t)G * sp->NE, hipMemcpyHostToDevice, sp->stream));
-      HIPCHK(hipMemcpyAsync(sp->d_Z, sp->h_Z.data(), sizeof(float) * G, hipMemcpyHostToDevice, sp->stream));
-      SPCHK(elfmcts_dirichlet(p.mcts, sp->d_etas, sp->d_Z, sp->opt.root_epsilon, sp->stream));
+      HIPCHK(sp->etas.up((size_t)G * sp->NE, sp->stream));
+      HIPCHK(sp->Z.up(G, sp->stream));
+      SPCHK(elfmcts_dirichlet(p.mcts, sp->etas.d, sp->Z.d, sp->opt.root_epsilon, sp->stream));
       if (mixed) HIPCHK(hipStreamSynchronize(sp->stream));   // m2 is a temporary
     }
     // BoardFeature::RandomShuffle draws of this move (go/mcts/mcts.h:175-183), from a copy of the actor stream
@@ -578,11 +593,7 @@ static int sp_restart_finished(ElfSelfPlay* sp, const std::vector<int32_t>& ids)
   const int k = (int)ids.size();
   if (k == 0) return 0;
   // _ai->endGame / _ai2->endGame (resetTree), _state_ext.restart() (state reset, resign check reset)
-  HIPCHK(hipMemcpyAsync(sp->d_ids, ids.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, sp->stream));
-  SPCHK(elfgo_reset(sp->eng, sp->d_ids, k, sp->stream));
-  for (int a = 0; a < 2; ++a)
-    if (sp->pool[a].mcts) SPCHK(elfmcts_clear(sp->pool[a].mcts, sp->d_ids, k, sp->stream));
-  HIPCHK(hipStreamSynchronize(sp->stream));   // ids may be a temporary
+  SPCHK(sp_reset_boards_and_trees(sp, ids));
   for (int g : ids) sp_state_restart(sp->games[g]);
   sp->n_games += k;
   return 0;
@@ -600,151 +611,195 @@ static float sp_final_value(ElfSelfPlay* sp, SpGame& gm, int reason, float evalu
   if (reason == ELFSP_FR_RESIGN) return ((gm.ply & 1) == 1) ? -1.0f : 1.0f;   // nextPlayer() == S_WHITE ? 1 : -1; ply 1 = Black to move
   return evaluated;
 }
-// the part of act() after the search (:373-429) for every game whose search has just had its last batch
+// one finished game: score it (sp_final_value), count it, write its record
+static void sp_finish_game(ElfSelfPlay* sp, int g, int reason, float evaluated) {
+  SpGame& gm = sp->games[g];
+  const float fv = sp_final_value(sp, gm, reason, evaluated);
+  sp->sum_final += fv;
+  sp_finish_record(sp, g, fv, gm.ply);
+}
+
+// GoState::evaluate(komi) of the listed games' boards, queued: val.d[i] <- the Tromp-Taylor score of game ids[i]
+static int sp_queue_evaluate(ElfSelfPlay* sp, const int32_t* ids, int k) {
+  HIPCHK(sp->ids.up(k, sp->stream, ids));
+  return elfgo_evaluate(sp->eng, sp->ids.d, k, sp->opt.mcts.komi, sp->val.d, sp->stream);
+}
+
+// finish_game(reason) -> setFinalValue: GoState::evaluate(komi) (go_state_ext.h:100-102) of the listed games as their boards stand,
+// then their records
+static int sp_score_and_finish(ElfSelfPlay* sp, const int32_t* ids, int k, int reason) {
+  SPCHK(sp_queue_evaluate(sp, ids, k));
+  HIPCHK(sp->val.down(k, sp->stream));
+  HIPCHK(hipStreamSynchronize(sp->stream));
+  for (int i = 0; i < k; ++i) sp_finish_game(sp, ids[i], reason, sp->val.h[i]);
+  return 0;
+}
+
+struct SpRoot {       // what elfmcts_root reports of one game's finished search
+  int n;              // edges
+  const int32_t *coord, *visits;
+  const float *prior, *reward;
+  float root_value;
+};
+struct SpDecision {
+  int move, best_action, total_visits;
+  float max_score, predicted;
+  bool resign;
+};
+
+// The decision of act() after one game's search (:373-391): which move, and whether to resign instead.  Host arithmetic only, kept
+// as the reference writes it (mixed float / double included).  Draws, in this order: `pick_rng` (uniform_random only), gm.rng for
+// the sampled move, gm.rng for the never-resign flag (once per game).  tt_score / last_board_move: the Tromp-Taylor score and the
+// last move of the game board, read only under following_pass.
+static SpDecision sp_decide_move(SpGame& gm, const ElfSpOptions& opt, const SpRoot& root, float tt_score, int last_board_move,
+                                 std::mt19937& pick_rng) {
+  const int n = root.n;
+  const int32_t *coord = root.coord, *visits = root.visits;
+  const float *prior = root.prior, *reward = root.reward;
+  // chooseAction :495-528 / runPolicyOnly :401-405 with MCTSResultT::addActions (tree_search_base.h:237-294)
+  const int method = gm.policy_only ? ELFSP_PICK_STRONGEST_PRIOR : opt.pick_method;
+  int best_action = M_INVALID, total_visits = 0, best_i = -1, random_idx = 0;
+  float max_score = -3.402823466e+38f;
+  if (method == ELFSP_PICK_UNIFORM_RANDOM && n > 0) random_idx = (int)(pick_rng() % (unsigned)n);
+  std::vector<float> scores(n);
+  for (int i = 0; i < n; ++i) {
+    const float score = method == ELFSP_PICK_MOST_VISITED ? (float)visits[i] : method == ELFSP_PICK_STRONGEST_PRIOR ? prior[i] : 1.0f;
+    scores[i] = score;
+    total_visits += visits[i];
+    if (method == ELFSP_PICK_UNIFORM_RANDOM) {
+      if (i == random_idx) { max_score = score; best_action = coord[i]; best_i = i; }
+    } else if (score > max_score) { max_score = score; best_action = coord[i]; best_i = i; }
+  }
+  int c = best_action;
+  if (!gm.policy_only) {
+    // mcts_make_diverse_move (game_selfplay.cc:80-95): MCTSPolicy::normalize (tree_search_base.h:190-203) + sampleAction
+    const bool diverse = gm.ply <= opt.policy_distri_cutoff;
+    const bool keep_policy = opt.keep_records > 0 && (diverse || opt.policy_distri_training_for_all);
+    std::vector<std::pair<int, float>> policy;
+    if ((diverse && n > 0) || keep_policy) {
+      policy.resize(n);
+      float exp_sum = 0;
+      for (int i = 0; i < n; ++i) {
+        float e = std::pow(scores[i], 1.0 / 1.0f);
+        policy[i] = std::make_pair(coord[i], e);
+        exp_sum += e;
+      }
+      for (auto& pe : policy) pe.second /= exp_sum;
+    }
+    if (diverse && n > 0) {
+      // elf_utils::sample_multinomial (elf/utils/utils.h:159-182)
+      float Z = 0.0;
+      for (const auto& pe : policy) Z += pe.second;
+      std::uniform_real_distribution<> dis(0, Z);
+      float rd = dis(gm.rng);
+      std::vector<float> accu(n + 1);
+      accu[0] = 0;
+      size_t pick = n - 1;
+      for (size_t i = 1; i < accu.size(); i++) {
+        accu[i] = policy[i - 1].second + accu[i - 1];
+        if (rd < accu[i]) { pick = i - 1; break; }
+      }
+      c = policy[pick].first;
+    }
+    if (keep_policy) {   // _state_ext.addMCTSPolicy(policy) :89-92
+      std::vector<int32_t> pc(n);
+      std::vector<float> pp(n);
+      for (int i = 0; i < n; ++i) { pc[i] = policy[i].first; pp[i] = policy[i].second; }
+      elfrec_append_policy(opt.board_size, pc.data(), pp.data(), n, &gm.rec.policies);
+    }
+  }
+  // mcts_update_info :97-119 with MCTSGoAI::getValue (go/mcts/mcts.h:358-365)
+  float predicted = root.root_value;
+  if (total_visits != 0 && best_i >= 0) predicted = reward[best_i] / visits[best_i];
+  gm.last_predicted = predicted;
+  if (opt.keep_records > 0) gm.rec.values.push_back(predicted);   // addPredictedValue, mcts_update_info :98-100
+  if (opt.following_pass) {   // "If the opponent wants pass, and we are in good, we follow." :104-111 (human games)
+    const bool black = (gm.ply & 1) == 1;
+    const float sc = tt_score;
+    const bool we_are_good = black ? (sc > 0 && predicted > 0.9) : (sc < 0 && predicted < -0.9);
+    if (we_are_good && last_board_move == M_PASS && gm.ply > 1) c = M_PASS;
+  }
+  // shouldResign (go_state_ext.h:207-214) -> ResignCheck::check (game_utils.h:24-40); side to move = parity of ply
+  bool resign = false;
+  {
+    const bool black = (gm.ply & 1) == 1;   // ply 1 = Black to move
+    const float value = black ? predicted : -predicted;
+    if (!gm.has_calculated_never_resign) {
+      std::uniform_real_distribution<> dis(0.0, 1.0);
+      gm.never_resign = (dis(gm.rng) < gm.req.never_resign_prob);
+      gm.has_calculated_never_resign = true;
+    }
+    const float thres = (gm.req.black_thres + gm.req.white_thres) / 2.0;   // setRequest, go_state_ext.h:62-66
+    if (!gm.never_resign && !(value >= -1.0 + thres)) resign = true;
+  }
+  return SpDecision{c, best_action, total_visits, max_score, predicted, resign};
+}
+
+// the part of act() after the search (:373-429) for every game whose search has just had its last batch: the staging of what
+// sp_decide_move reads, and what follows from its verdict (finish / preloaded SGF exhausted / forward the move)
 static int sp_finish_moves(ElfSelfPlay* sp, const std::vector<int32_t> (&done)[2]) {
   const int G = sp->G, NE = sp->NE;
+  const size_t GE = (size_t)G * NE;
   std::vector<int32_t> finished, sgf_done, movers;
-  std::fill(sp->h_moves.begin(), sp->h_moves.end(), -1);
+  std::fill(sp->moves.h.begin(), sp->moves.h.end(), -1);
   bool first_wait = true;
   for (int a = 0; a < 2; ++a) {
     if (done[a].empty()) continue;
     SpPool& p = sp->pool[a];
-    SPCHK(elfmcts_root(p.mcts, sp->d_info, sp->d_coord, sp->d_visits, sp->d_prior, sp->d_reward, nullptr, sp->stream));
-    HIPCHK(hipMemcpyAsync(sp->h_info.data(), sp->d_info, sizeof(int32_t) * G * ELFMCTS_ROOT_WORDS, hipMemcpyDeviceToHost, sp->stream));
-    HIPCHK(hipMemcpyAsync(sp->h_coord.data(), sp->d_coord, sizeof(int32_t) * (size_t)G * NE, hipMemcpyDeviceToHost, sp->stream));
-    HIPCHK(hipMemcpyAsync(sp->h_visits.data(), sp->d_visits, sizeof(int32_t) * (size_t)G * NE, hipMemcpyDeviceToHost, sp->stream));
-    HIPCHK(hipMemcpyAsync(sp->h_prior.data(), sp->d_prior, sizeof(float) * (size_t)G * NE, hipMemcpyDeviceToHost, sp->stream));
-    HIPCHK(hipMemcpyAsync(sp->h_reward.data(), sp->d_reward, sizeof(float) * (size_t)G * NE, hipMemcpyDeviceToHost, sp->stream));
+    SPCHK(elfmcts_root(p.mcts, sp->info.d, sp->coord.d, sp->visits.d, sp->prior.d, sp->reward.d, nullptr, sp->stream));
+    HIPCHK(sp->info.down((size_t)G * ELFMCTS_ROOT_WORDS, sp->stream));
+    HIPCHK(sp->coord.down(GE, sp->stream));
+    HIPCHK(sp->visits.down(GE, sp->stream));
+    HIPCHK(sp->prior.down(GE, sp->stream));
+    HIPCHK(sp->reward.down(GE, sp->stream));
     if (p.T > 1) SPCHK(elfmcts_thread_draws(p.mcts, p.h_tdraws.data(), sp->stream));
     HIPCHK(hipStreamSynchronize(sp->stream));
     if (first_wait) { sp->t_after_drain = std::chrono::steady_clock::now(); first_wait = false; }
     // online mode, following_pass (mcts_update_info :104-111): Tromp-Taylor score and last move of the game boards
-    std::vector<float> tt_score;
-    if (sp->opt.following_pass) {
+    const bool follow = sp->opt.following_pass != 0;
+    if (follow) {
       const int k = (int)done[a].size();
-      tt_score.resize(k);
-      HIPCHK(hipMemcpyAsync(sp->d_ids, done[a].data(), 4 * k, hipMemcpyHostToDevice, sp->stream));
-      SPCHK(elfgo_evaluate(sp->eng, sp->d_ids, k, sp->opt.mcts.komi, sp->d_val, sp->stream));
-      SPCHK(elfgo_info(sp->eng, sp->d_ids, k, sp->d_binfo, sp->stream));
-      HIPCHK(hipMemcpyAsync(tt_score.data(), sp->d_val, 4 * k, hipMemcpyDeviceToHost, sp->stream));
-      HIPCHK(hipMemcpyAsync(sp->h_binfo.data(), sp->d_binfo, sizeof(int32_t) * k * ELFGO_INFO_WORDS, hipMemcpyDeviceToHost, sp->stream));
+      SPCHK(sp_queue_evaluate(sp, done[a].data(), k));
+      SPCHK(elfgo_info(sp->eng, sp->ids.d, k, sp->binfo.d, sp->stream));
+      HIPCHK(sp->val.down(k, sp->stream));
+      HIPCHK(sp->binfo.down((size_t)k * ELFGO_INFO_WORDS, sp->stream));
       HIPCHK(hipStreamSynchronize(sp->stream));
     }
     for (size_t di = 0; di < done[a].size(); ++di) {
       const int g = done[a][di];
       SpGame& gm = sp->games[g];
-      const int32_t* info = &sp->h_info[g * ELFMCTS_ROOT_WORDS];
+      const int32_t* info = &sp->info.h[g * ELFMCTS_ROOT_WORDS];
       if (info[6]) return ELFGO_E_MCTS_BASE - info[6];
       gm.actor_rng[a].discard((unsigned long long)info[5]);   // D4 draws the search consumed (thread 0's actor)
       for (int t = 1; t < p.T && t - 1 < (int)gm.thread_rng[a].size(); ++t)
         gm.thread_rng[a][t - 1].discard((unsigned long long)p.h_tdraws[(size_t)g * p.T + t]);
-      p.h_active[g] = GMASK_IDLE;
-      const int n = info[0];
-      const int32_t* coord = &sp->h_coord[(size_t)g * NE];
-      const int32_t* visits = &sp->h_visits[(size_t)g * NE];
-      const float* prior = &sp->h_prior[(size_t)g * NE];
-      const float* reward = &sp->h_reward[(size_t)g * NE];
-      float root_value;
-      memcpy(&root_value, &info[4], 4);
-      // chooseAction :495-528 / runPolicyOnly :401-405 with MCTSResultT::addActions (tree_search_base.h:237-294)
-      const int method = gm.policy_only ? ELFSP_PICK_STRONGEST_PRIOR : sp->opt.pick_method;
-      int best_action = M_INVALID, total_visits = 0, best_i = -1, random_idx = 0;
-      float max_score = -3.402823466e+38f;
-      if (method == ELFSP_PICK_UNIFORM_RANDOM && n > 0) random_idx = (int)(sp->pick_rng() % (unsigned)n);
-      std::vector<float> scores(n);
-      for (int i = 0; i < n; ++i) {
-        const float score = method == ELFSP_PICK_MOST_VISITED ? (float)visits[i] : method == ELFSP_PICK_STRONGEST_PRIOR ? prior[i] : 1.0f;
-        scores[i] = score;
-        total_visits += visits[i];
-        if (method == ELFSP_PICK_UNIFORM_RANDOM) {
-          if (i == random_idx) { max_score = score; best_action = coord[i]; best_i = i; }
-        } else if (score > max_score) { max_score = score; best_action = coord[i]; best_i = i; }
-      }
-      int c = best_action;
-      if (!gm.policy_only) {
-        // mcts_make_diverse_move (game_selfplay.cc:80-95): MCTSPolicy::normalize (tree_search_base.h:190-203) + sampleAction
-        const bool diverse = gm.ply <= sp->opt.policy_distri_cutoff;
-        const bool keep_policy = sp->opt.keep_records > 0 && (diverse || sp->opt.policy_distri_training_for_all);
-        std::vector<std::pair<int, float>> policy;
-        if ((diverse && n > 0) || keep_policy) {
-          policy.resize(n);
-          float exp_sum = 0;
-          for (int i = 0; i < n; ++i) {
-            float e = std::pow(scores[i], 1.0 / 1.0f);
-            policy[i] = std::make_pair(coord[i], e);
-            exp_sum += e;
-          }
-          for (auto& pe : policy) pe.second /= exp_sum;
-        }
-        if (diverse && n > 0) {
-          // elf_utils::sample_multinomial (elf/utils/utils.h:159-182)
-          float Z = 0.0;
-          for (const auto& pe : policy) Z += pe.second;
-          std::uniform_real_distribution<> dis(0, Z);
-          float rd = dis(gm.rng);
-          std::vector<float> accu(n + 1);
-          accu[0] = 0;
-          size_t pick = n - 1;
-          for (size_t i = 1; i < accu.size(); i++) {
-            accu[i] = policy[i - 1].second + accu[i - 1];
-            if (rd < accu[i]) { pick = i - 1; break; }
-          }
-          c = policy[pick].first;
-        }
-        if (keep_policy) {   // _state_ext.addMCTSPolicy(policy) :89-92
-          std::vector<int32_t> pc(n);
-          std::vector<float> pp(n);
-          for (int i = 0; i < n; ++i) { pc[i] = policy[i].first; pp[i] = policy[i].second; }
-          elfrec_append_policy(sp->opt.board_size, pc.data(), pp.data(), n, &gm.rec.policies);
-        }
-      }
-      // mcts_update_info :97-119 with MCTSGoAI::getValue (go/mcts/mcts.h:358-365)
-      float predicted = root_value;
-      if (total_visits != 0 && best_i >= 0) predicted = reward[best_i] / visits[best_i];
-      gm.last_predicted = predicted;
-      if (sp->opt.keep_records > 0) gm.rec.values.push_back(predicted);   // addPredictedValue, mcts_update_info :98-100
-      if (sp->opt.following_pass) {   // "If the opponent wants pass, and we are in good, we follow." :104-111 (human games)
-        const bool black = (gm.ply & 1) == 1;
-        const float sc = tt_score[di];
-        const bool we_are_good = black ? (sc > 0 && predicted > 0.9) : (sc < 0 && predicted < -0.9);
-        if (we_are_good && sp->h_binfo[di * ELFGO_INFO_WORDS + 2] == M_PASS && gm.ply > 1) c = M_PASS;
-      }
+      p.active.h[g] = GMASK_IDLE;
+      SpRoot root{info[0], &sp->coord.h[(size_t)g * NE], &sp->visits.h[(size_t)g * NE], &sp->prior.h[(size_t)g * NE],
+                  &sp->reward.h[(size_t)g * NE], 0.0f};
+      memcpy(&root.root_value, &info[4], 4);
+      const SpDecision d = sp_decide_move(gm, sp->opt, root, follow ? sp->val.h[di] : 0.0f,
+                                          follow ? sp->binfo.h[di * ELFGO_INFO_WORDS + 2] : -1, sp->pick_rng);
       if (sp->log_cap > 0 && (int)sp->log_search.size() < sp->log_cap) {
         ElfSpSearchRec r;
-        r.game = g; r.move_played = c; r.best_action = best_action; r.total_visits = total_visits; r.n_edges = n;
-        r.root_value = root_value; r.max_score = max_score; r.predicted_value = predicted;
+        r.game = g; r.move_played = d.move; r.best_action = d.best_action; r.total_visits = d.total_visits; r.n_edges = root.n;
+        r.root_value = root.root_value; r.max_score = d.max_score; r.predicted_value = d.predicted;
         sp->log_search.push_back(r);
-        sp->log_coord.insert(sp->log_coord.end(), coord, coord + NE);
-        sp->log_visits.insert(sp->log_visits.end(), visits, visits + NE);
-        sp->log_prior.insert(sp->log_prior.end(), prior, prior + NE);
-        sp->log_reward.insert(sp->log_reward.end(), reward, reward + NE);
-      }
-      // shouldResign (go_state_ext.h:207-214) -> ResignCheck::check (game_utils.h:24-40); side to move = parity of ply
-      bool resign = false;
-      {
-        const bool black = (gm.ply & 1) == 1;   // ply 1 = Black to move
-        const float value = black ? predicted : -predicted;
-        if (!gm.has_calculated_never_resign) {
-          std::uniform_real_distribution<> dis(0.0, 1.0);
-          gm.never_resign = (dis(gm.rng) < gm.req.never_resign_prob);
-          gm.has_calculated_never_resign = true;
-        }
-        const float thres = (gm.req.black_thres + gm.req.white_thres) / 2.0;   // setRequest, go_state_ext.h:62-66
-        if (!gm.never_resign && !(value >= -1.0 + thres)) resign = true;
+        sp->log_coord.insert(sp->log_coord.end(), root.coord, root.coord + NE);
+        sp->log_visits.insert(sp->log_visits.end(), root.visits, root.visits + NE);
+        sp->log_prior.insert(sp->log_prior.end(), root.prior, root.prior + NE);
+        sp->log_reward.insert(sp->log_reward.end(), root.reward, root.reward + NE);
       }
       gm.ai = -1;
       sp->n_moves++;
-      if (resign && gm.ply >= 50) {
+      if (d.resign && gm.ply >= 50) {
         gm.last_move = M_RESIGN;
-        const float fv = sp_final_value(sp, gm, ELFSP_FR_RESIGN, 0.0f);   // finish_game(FR_RESIGN) :387-391
-        sp->sum_final += fv;
-        sp_finish_record(sp, g, fv, gm.ply);
+        sp_finish_game(sp, g, ELFSP_FR_RESIGN, 0.0f);   // finish_game(FR_RESIGN) :387-391
         finished.push_back(g);
       } else if (!sp->sgf.empty() && gm.sgf_iter >= (int)sp->sgf.size()) {
         sgf_done.push_back(g);         // preloaded SGF exhausted: finish_game(FR_MAX_STEP), game_selfplay.cc:392-396
       } else {
-        if (!sp->sgf.empty()) c = sp->sgf[gm.sgf_iter++];       // "Move changes from {} to {}" :397-405
-        sp->h_moves[g] = c;
+        const int c = sp->sgf.empty() ? d.move : sp->sgf[gm.sgf_iter++];       // "Move changes from {} to {}" :397-405
+        sp->moves.h[g] = c;
         gm.last_move = c;
         movers.push_back(g);
       }
@@ -752,18 +807,8 @@ static int sp_finish_moves(ElfSelfPlay* sp, const std::vector<int32_t> (&done)[2
   }
   if (!sgf_done.empty()) {
     // setFinalValue(FR_MAX_STEP) = GoState::evaluate(komi) of the position the search started from; no move is forwarded
-    const int k = (int)sgf_done.size();
-    HIPCHK(hipMemcpyAsync(sp->d_ids, sgf_done.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, sp->stream));
-    SPCHK(elfgo_evaluate(sp->eng, sp->d_ids, k, sp->opt.mcts.komi, sp->d_val, sp->stream));
-    HIPCHK(hipMemcpyAsync(sp->h_val.data(), sp->d_val, sizeof(float) * k, hipMemcpyDeviceToHost, sp->stream));
-    HIPCHK(hipStreamSynchronize(sp->stream));
-    for (int i = 0; i < k; ++i) {
-      SpGame& gm = sp->games[sgf_done[i]];
-      const float fv = sp_final_value(sp, gm, ELFSP_FR_MAX_STEP, sp->h_val[i]);
-      sp->sum_final += fv;
-      sp_finish_record(sp, sgf_done[i], fv, gm.ply);
-      finished.push_back(sgf_done[i]);
-    }
+    SPCHK(sp_score_and_finish(sp, sgf_done.data(), (int)sgf_done.size(), ELFSP_FR_MAX_STEP));
+    finished.insert(finished.end(), sgf_done.begin(), sgf_done.end());
   }
   std::vector<int32_t> by_end;
   std::sort(movers.begin(), movers.end());   // with every game moving, list position == game index (the ids == NULL launches below)
@@ -771,52 +816,60 @@ static int sp_finish_moves(ElfSelfPlay* sp, const std::vector<int32_t> (&done)[2
     // GoStateExt::forward(c) (game_selfplay.cc:408) on the real game boards; the trees of both AIs follow (advanceMoves -> treeAdvance)
     const int k = (int)movers.size();
     std::vector<int32_t> mv(k);
-    for (int i = 0; i < k; ++i) mv[i] = sp->h_moves[movers[i]];
+    for (int i = 0; i < k; ++i) mv[i] = sp->moves.h[movers[i]];
     const bool all = k == G;
     if (all) {
-      HIPCHK(hipMemcpyAsync(sp->d_moves, sp->h_moves.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, sp->stream));
-      SPCHK(elfgo_forward(sp->eng, nullptr, sp->d_moves, G, sp->d_ok, sp->stream));
+      HIPCHK(sp->moves.up(G, sp->stream));
+      SPCHK(elfgo_forward(sp->eng, nullptr, sp->moves.d, G, sp->ok.d, sp->stream));
     } else {
-      HIPCHK(hipMemcpyAsync(sp->d_ids, movers.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, sp->stream));
-      HIPCHK(hipMemcpyAsync(sp->d_moves, mv.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, sp->stream));
-      SPCHK(elfgo_forward(sp->eng, sp->d_ids, sp->d_moves, k, sp->d_ok, sp->stream));
-      HIPCHK(hipStreamSynchronize(sp->stream));   // d_moves is reused for the per-game list below
-      HIPCHK(hipMemcpyAsync(sp->d_moves, sp->h_moves.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, sp->stream));
+      HIPCHK(sp->ids.up(k, sp->stream, movers.data()));
+      HIPCHK(sp->moves.up(k, sp->stream, mv.data()));
+      SPCHK(elfgo_forward(sp->eng, sp->ids.d, sp->moves.d, k, sp->ok.d, sp->stream));
+      HIPCHK(hipStreamSynchronize(sp->stream));   // moves.d is reused for the per-game list below
+      HIPCHK(sp->moves.up(G, sp->stream));
     }
     if (sp->opt.persistent_tree)
       for (int a = 0; a < 2; ++a)
-        if (sp->pool[a].mcts) SPCHK(elfmcts_advance(sp->pool[a].mcts, sp->d_moves, sp->stream));   // games without a move: -1
-    SPCHK(elfgo_info(sp->eng, all ? nullptr : sp->d_ids, k, sp->d_binfo, sp->stream));
-    HIPCHK(hipMemcpyAsync(sp->h_binfo.data(), sp->d_binfo, sizeof(int32_t) * k * ELFGO_INFO_WORDS, hipMemcpyDeviceToHost, sp->stream));
-    HIPCHK(hipMemcpyAsync(sp->h_ok.data(), sp->d_ok, k, hipMemcpyDeviceToHost, sp->stream));
+        if (sp->pool[a].mcts) SPCHK(elfmcts_advance(sp->pool[a].mcts, sp->moves.d, sp->stream));   // games without a move: -1
+    SPCHK(elfgo_info(sp->eng, all ? nullptr : sp->ids.d, k, sp->binfo.d, sp->stream));
+    HIPCHK(sp->binfo.down((size_t)k * ELFGO_INFO_WORDS, sp->stream));
+    HIPCHK(sp->ok.down(k, sp->stream));
     HIPCHK(hipStreamSynchronize(sp->stream));
     for (int i = 0; i < k; ++i) {
       const int g = movers[i];
       SpGame& gm = sp->games[g];
-      if (sp->h_ok[i] != 1) return ELFGO_E_MCTS_BASE - ELFMCTS_E_FORWARD;   // "Something is wrong! Move cannot be applied" :409-418
-      const int32_t* bi = &sp->h_binfo[i * ELFGO_INFO_WORDS];
+      if (sp->ok.h[i] != 1) return ELFGO_E_MCTS_BASE - ELFMCTS_E_FORWARD;   // "Something is wrong! Move cannot be applied" :409-418
+      const int32_t* bi = &sp->binfo.h[i * ELFGO_INFO_WORDS];
       gm.ply = bi[0];
-      if (sp->opt.keep_records > 0) gm.rec.moves.push_back((uint16_t)sp->h_moves[g]);   // GoState::_moves
+      if (sp->opt.keep_records > 0) gm.rec.moves.push_back((uint16_t)sp->moves.h[g]);   // GoState::_moves
       const bool terminated = bi[9] != 0;
       if (terminated || (sp->opt.move_cutoff > 0 && gm.ply >= sp->opt.move_cutoff)) by_end.push_back(g);   // :420-429
     }
   }
   if (!by_end.empty()) {
     // finish_game -> setFinalValue: GoState::evaluate(komi) (go_state_ext.h:100-102)
-    const int k = (int)by_end.size();
-    HIPCHK(hipMemcpyAsync(sp->d_ids, by_end.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, sp->stream));
-    SPCHK(elfgo_evaluate(sp->eng, sp->d_ids, k, sp->opt.mcts.komi, sp->d_val, sp->stream));
-    HIPCHK(hipMemcpyAsync(sp->h_val.data(), sp->d_val, sizeof(float) * k, hipMemcpyDeviceToHost, sp->stream));
-    HIPCHK(hipStreamSynchronize(sp->stream));
-    for (int i = 0; i < k; ++i) {
-      SpGame& gm = sp->games[by_end[i]];
-      const float fv = sp_final_value(sp, gm, ELFSP_FR_MAX_STEP, sp->h_val[i]);
-      sp->sum_final += fv;
-      sp_finish_record(sp, by_end[i], fv, gm.ply);
-    }
+    SPCHK(sp_score_and_finish(sp, by_end.data(), (int)by_end.size(), ELFSP_FR_MAX_STEP));
     finished.insert(finished.end(), by_end.begin(), by_end.end());
   }
   SPCHK(sp_restart_finished(sp, finished));
+  return 0;
+}
+
+// row counts of the pools that selected in this step -> n_rows[2] (0 for a pool that did not); waits for the stream; a pool's error
+// word ends the call
+static int sp_fetch_rows(ElfSelfPlay* sp, int* n_rows) {
+  for (int a = 0; a < 2; ++a) {
+    SpPool& p = sp->pool[a];
+    n_rows[a] = 0;
+    if (p.selected) HIPCHK(p.counts.down(2, sp->stream));
+  }
+  HIPCHK(hipStreamSynchronize(sp->stream));
+  for (int a = 0; a < 2; ++a) {
+    SpPool& p = sp->pool[a];
+    if (!p.selected) continue;
+    if (p.counts.h[1]) return ELFGO_E_MCTS_BASE - p.counts.h[1];
+    n_rows[a] = p.counts.h[0];
+  }
   return 0;
 }
 
@@ -861,16 +914,12 @@ int elfsp_create(const ElfSpOptions* o, int device, const uint64_t* zobrist_host
     sp->games[g].rng.seed((std::mt19937::result_type)seed);
   }
   sp->pick_rng.seed(o->seed != 0 ? (std::mt19937::result_type)(o->seed ^ 0x5EEDu) : (std::mt19937::result_type)time(NULL));
-#define A(ptr, bytes) do { hipError_t _e = hipMalloc((void**)&(ptr), (bytes)); if (_e != hipSuccess) { elfsp_destroy(sp); return (int)_e; } } while (0)
   const size_t GE = (size_t)G * sp->NE;
-  A(sp->d_info, sizeof(int32_t) * G * ELFMCTS_ROOT_WORDS);
-  A(sp->d_coord, 4 * GE); A(sp->d_visits, 4 * GE); A(sp->d_prior, 4 * GE); A(sp->d_reward, 4 * GE); A(sp->d_etas, 4 * GE);
-  A(sp->d_Z, 4 * G); A(sp->d_moves, 4 * G); A(sp->d_ids, 4 * G); A(sp->d_val, 4 * G); A(sp->d_ok, G);
-  A(sp->d_binfo, sizeof(int32_t) * G * ELFGO_INFO_WORDS);
-#undef A
-  sp->h_info.resize(G * ELFMCTS_ROOT_WORDS); sp->h_coord.resize(GE); sp->h_visits.resize(GE); sp->h_prior.resize(GE);
-  sp->h_reward.resize(GE); sp->h_etas.assign(GE, 0.f); sp->h_Z.resize(G); sp->h_moves.resize(G); sp->h_val.resize(G);
-  sp->h_ok.resize(G); sp->h_binfo.resize(G * ELFGO_INFO_WORDS);
+  hipError_t e = sp->info.alloc((size_t)G * ELFMCTS_ROOT_WORDS);   // the first failure ends the chain
+  (e || (e = sp->coord.alloc(GE)) || (e = sp->visits.alloc(GE)) || (e = sp->prior.alloc(GE)) || (e = sp->reward.alloc(GE)) ||
+   (e = sp->etas.alloc(GE)) || (e = sp->Z.alloc(G)) || (e = sp->moves.alloc(G)) || (e = sp->ids.alloc(G)) || (e = sp->val.alloc(G)) ||
+   (e = sp->ok.alloc(G)) || (e = sp->binfo.alloc((size_t)G * ELFGO_INFO_WORDS)));
+  if (e != hipSuccess) { elfsp_destroy(sp); return (int)e; }
   sp->log_cap = o->log_searches;
   // the request the games start under unless the caller sends one before the first step: self-play with ElfSpOptions.model_ver
   SpRequest r;
@@ -889,13 +938,10 @@ int elfsp_create(const ElfSpOptions* o, int device, const uint64_t* zobrist_host
 int elfsp_destroy(ElfSelfPlay* sp) {
   if (!sp) return ELFGO_E_BADARG;
   DevGuard _dg(sp->eng ? sp->eng->device : 0);
-  void* ptrs[] = {sp->d_info, sp->d_coord, sp->d_visits, sp->d_prior, sp->d_reward, sp->d_etas, sp->d_Z,
-                  sp->d_moves, sp->d_ids, sp->d_val, sp->d_ok, sp->d_binfo};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
   sp_pool_free(sp->pool[0]);
   sp_pool_free(sp->pool[1]);
   if (sp->eng) elfgo_destroy(sp->eng);
-  delete sp;
+  delete sp;   // the scratch buffers free themselves (SpBuf), still on the engine's device
   return 0;
 }
 
@@ -903,9 +949,8 @@ ElfGoEngine* elfsp_engine(ElfSelfPlay* sp) { return sp ? sp->eng : nullptr; }
 int64_t elfsp_ts_requests_deferred(const ElfSelfPlay* sp) { return sp ? sp->ts_deferred : ELFGO_E_BADARG; }
 int elfsp_ts_games_deferred(const ElfSelfPlay* sp) {
   if (!sp) return ELFGO_E_BADARG;
-  const ElfTsOptions ctx = sp_ts_of(sp->opt);
   int k = 0;
-  for (const SpGame& gm : sp->games) k += gm.phase == PH_PLAY && !gm.req.wait() && !sp_ts_pool_equal(gm.req.ts, ctx);
+  for (const SpGame& gm : sp->games) k += gm.phase == PH_PLAY && !gm.req.wait() && !sp_ts_pool_equal(gm.req.ts, sp->opt);
   return k;
 }
 ElfMcts* elfsp_mcts(ElfSelfPlay* sp) { return sp ? sp->pool[0].mcts : nullptr; }
@@ -934,37 +979,26 @@ int elfsp_begin_step2(ElfSelfPlay* sp, void* const* s_dst, int64_t stride_elems,
     p.last_rows = 0;
     p.n_active = 0;
     if (!p.mcts) continue;
-    for (int g = 0; g < sp->G; ++g) p.n_active += p.h_active[g] != GMASK_IDLE;
+    for (int g = 0; g < sp->G; ++g) p.n_active += p.active.h[g] != GMASK_IDLE;
     if (p.n_active > 0 && !s_dst[a]) return ELFGO_E_BADARG;   // this AI has rows to write and nowhere to write them
   }
   for (int a = 0; a < 2; ++a) {
     SpPool& p = sp->pool[a];
     if (p.n_active == 0) continue;
     bool plain = p.n_active == sp->G;
-    for (int g = 0; plain && g < sp->G; ++g) plain = p.h_active[g] == GMASK_SEARCH;
+    for (int g = 0; plain && g < sp->G; ++g) plain = p.active.h[g] == GMASK_SEARCH;
     SPCHK(sp_upload_masks(sp, p));
-    SPCHK(elfmcts_set_game_mask(p.mcts, plain ? nullptr : p.d_active));
-    SPCHK(elfmcts_set_required_versions(p.mcts, p.d_ver));
-    SPCHK(elfmcts_select(p.mcts, nullptr, s_dst[a], stride_elems, p.d_counts, sp->stream));
+    SPCHK(elfmcts_set_game_mask(p.mcts, plain ? nullptr : p.active.d));
+    SPCHK(elfmcts_set_required_versions(p.mcts, p.ver.d));
+    SPCHK(elfmcts_select(p.mcts, nullptr, s_dst[a], stride_elems, p.counts.d, sp->stream));
     p.selected = true;
     p.last_rows = -1;
   }
   sp->step_open = true;
   if (!n_rows) return 0;          // row counts and error words stay on the device until the move boundary
-  for (int a = 0; a < 2; ++a) {
-    SpPool& p = sp->pool[a];
-    n_rows[a] = 0;
-    if (!p.selected) continue;
-    HIPCHK(hipMemcpyAsync(p.h_counts, p.d_counts, 8, hipMemcpyDeviceToHost, sp->stream));
-  }
-  HIPCHK(hipStreamSynchronize(sp->stream));
-  for (int a = 0; a < 2; ++a) {
-    SpPool& p = sp->pool[a];
-    if (!p.selected) continue;
-    if (p.h_counts[1]) return ELFGO_E_MCTS_BASE - p.h_counts[1];
-    p.last_rows = p.h_counts[0];
-    n_rows[a] = p.last_rows;
-  }
+  SPCHK(sp_fetch_rows(sp, n_rows));
+  for (int a = 0; a < 2; ++a)
+    if (sp->pool[a].selected) sp->pool[a].last_rows = n_rows[a];
   return 0;
 }
 
@@ -980,20 +1014,7 @@ int elfsp_begin_step(ElfSelfPlay* sp, void* s_dst, int64_t stride_elems, int* n_
 int elfsp_last_rows2(ElfSelfPlay* sp, int* n_rows) {
   if (!sp || !n_rows) return ELFGO_E_BADARG;
   DevGuard _dg(sp->eng->device);
-  for (int a = 0; a < 2; ++a) {
-    SpPool& p = sp->pool[a];
-    n_rows[a] = 0;
-    if (!p.selected) continue;
-    HIPCHK(hipMemcpyAsync(p.h_counts, p.d_counts, 8, hipMemcpyDeviceToHost, sp->stream));
-  }
-  HIPCHK(hipStreamSynchronize(sp->stream));
-  for (int a = 0; a < 2; ++a) {
-    SpPool& p = sp->pool[a];
-    if (!p.selected) continue;
-    if (p.h_counts[1]) return ELFGO_E_MCTS_BASE - p.h_counts[1];
-    n_rows[a] = p.h_counts[0];
-  }
-  return 0;
+  return sp_fetch_rows(sp, n_rows);
 }
 
 int elfsp_last_rows(ElfSelfPlay* sp, int* n_rows) {
@@ -1018,7 +1039,7 @@ int elfsp_end_step2(ElfSelfPlay* sp, const float* const* pi, int64_t pi_stride_f
     SPCHK(elfmcts_expand(p.mcts, pia, pi_stride_floats, va, rv ? rv[a] : nullptr, p.last_rows, sp->stream));
     p.selected = false;
     for (int g = 0; g < sp->G; ++g) {
-      if (p.h_active[g] == GMASK_IDLE) continue;
+      if (p.active.h[g] == GMASK_IDLE) continue;
       SpGame& gm = sp->games[g];
       sp->n_rollouts += gm.policy_only ? 1 : p.KT;
       if (++gm.step >= gm.steps) done[a].push_back(g);
@@ -1171,32 +1192,32 @@ int elfsp_play(ElfSelfPlay* sp, const int32_t* moves_host, void* stream) {
   if (sp_any_search_open(sp, ids.data(), (int)ids.size())) return ELFGO_E_BADARG;
   SPCHK(sp_poll_requests(sp));   // the games of a fresh context start with their first request
   const int k = (int)ids.size();
-  HIPCHK(hipMemcpyAsync(sp->d_ids, ids.data(), 4 * k, hipMemcpyHostToDevice, sp->stream));
-  HIPCHK(hipMemcpyAsync(sp->d_moves, mv.data(), 4 * k, hipMemcpyHostToDevice, sp->stream));
-  SPCHK(elfgo_forward(sp->eng, sp->d_ids, sp->d_moves, k, sp->d_ok, sp->stream));
-  HIPCHK(hipMemcpyAsync(sp->h_ok.data(), sp->d_ok, k, hipMemcpyDeviceToHost, sp->stream));
+  HIPCHK(sp->ids.up(k, sp->stream, ids.data()));
+  HIPCHK(sp->moves.up(k, sp->stream, mv.data()));
+  SPCHK(elfgo_forward(sp->eng, sp->ids.d, sp->moves.d, k, sp->ok.d, sp->stream));
+  HIPCHK(sp->ok.down(k, sp->stream));
   HIPCHK(hipStreamSynchronize(sp->stream));
   // "Invalid move ... please try again" (:323-327): refused moves leave their game untouched
   std::vector<int32_t> adv(G, -1);
   int bad = 0;
   for (int j = 0; j < k; ++j) {
-    if (sp->h_ok[j] != 1) { bad++; continue; }
+    if (sp->ok.h[j] != 1) { bad++; continue; }
     adv[ids[j]] = mv[j];
     sp->games[ids[j]].online_counter++;
   }
   if (sp->opt.persistent_tree) {
-    HIPCHK(hipMemcpyAsync(sp->d_moves, adv.data(), 4 * G, hipMemcpyHostToDevice, sp->stream));
+    HIPCHK(sp->moves.up(G, sp->stream, adv.data()));
     for (int a = 0; a < 2; ++a)
-      if (sp->pool[a].mcts) SPCHK(elfmcts_advance(sp->pool[a].mcts, sp->d_moves, sp->stream));
+      if (sp->pool[a].mcts) SPCHK(elfmcts_advance(sp->pool[a].mcts, sp->moves.d, sp->stream));
   }
-  SPCHK(elfgo_info(sp->eng, nullptr, G, sp->d_binfo, sp->stream));
-  HIPCHK(hipMemcpyAsync(sp->h_binfo.data(), sp->d_binfo, sizeof(int32_t) * G * ELFGO_INFO_WORDS, hipMemcpyDeviceToHost, sp->stream));
+  SPCHK(elfgo_info(sp->eng, nullptr, G, sp->binfo.d, sp->stream));
+  HIPCHK(sp->binfo.down((size_t)G * ELFGO_INFO_WORDS, sp->stream));
   HIPCHK(hipStreamSynchronize(sp->stream));
   std::vector<int32_t> two_pass;
   for (int g = 0; g < G; ++g) {
     if (adv[g] < 0) continue;
     SpGame& gm = sp->games[g];
-    const int32_t* bi = &sp->h_binfo[g * ELFGO_INFO_WORDS];
+    const int32_t* bi = &sp->binfo.h[g * ELFGO_INFO_WORDS];
     gm.ply = bi[0];
     if (sp->opt.keep_records > 0) gm.rec.moves.push_back((uint16_t)adv[g]);
     if (bi[2] == M_PASS && bi[3] == M_PASS) two_pass.push_back(g);   // "If the human opponent pass, we pass as well" :319-322
@@ -1233,19 +1254,9 @@ int elfsp_finish(ElfSelfPlay* sp, const int32_t* games_host, int n, int reason, 
   DevGuard _dg(sp->eng->device);
   sp->stream = (hipStream_t)stream;
   SPCHK(sp_poll_requests(sp));
-  HIPCHK(hipMemcpyAsync(sp->d_ids, games_host, 4 * n, hipMemcpyHostToDevice, sp->stream));
-  SPCHK(elfgo_evaluate(sp->eng, sp->d_ids, n, sp->opt.mcts.komi, sp->d_val, sp->stream));   // setFinalValue: evaluate(komi)
-  HIPCHK(hipMemcpyAsync(sp->h_val.data(), sp->d_val, sizeof(float) * n, hipMemcpyDeviceToHost, sp->stream));
-  HIPCHK(hipStreamSynchronize(sp->stream));
-  std::vector<int32_t> ids(games_host, games_host + n);
-  for (int j = 0; j < n; ++j) {
-    SpGame& gm = sp->games[games_host[j]];
-    const float fv = sp_final_value(sp, gm, reason, sp->h_val[j]);
-    sp->sum_final += fv;
-    sp_finish_record(sp, games_host[j], fv, gm.ply);
-    gm.online_counter++;
-  }
-  return sp_restart_finished(sp, ids);
+  SPCHK(sp_score_and_finish(sp, games_host, n, reason));
+  for (int j = 0; j < n; ++j) sp->games[games_host[j]].online_counter++;
+  return sp_restart_finished(sp, std::vector<int32_t>(games_host, games_host + n));
 }
 
 int elfsp_restart(ElfSelfPlay* sp, const int32_t* games_host, int n, void* stream) {
@@ -1303,7 +1314,7 @@ int elfsp_stats(ElfSelfPlay* sp, int64_t* out) {
     SPCHK(elfmcts_node_visits(p.mcts, &nv));      // synchronises the device
     out[8] += nv;
     uint64_t total_rows = 0;
-    HIPCHK(hipMemcpy(&total_rows, p.d_counts + 2, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&total_rows, p.counts.d + 2, 8, hipMemcpyDeviceToHost));
     rows += total_rows;
   }
   sp->n_rows = (int64_t)rows;
