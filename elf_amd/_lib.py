@@ -42,6 +42,11 @@ SIGNATURES = {
     "elfgo_info": (_i, [_vp, _vp, _i, _vp, _vp]),
     "elfgo_export_board": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "elfgo_playout": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "elfgo_area_map": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "elfgo_own_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "elfgo_own_destroy": (_i, [_vp]),
+    "elfgo_own_scratch_bytes": (_sz, [_vp]),
+    "elfgo_own_run": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "elfmcts_create": (_i, [_vp, _i, _i, _i, _vp, C.POINTER(_vp)]),
     "elfmcts_destroy": (_i, [_vp]),
     "elfmcts_set_options": (_i, [_vp, _vp]),

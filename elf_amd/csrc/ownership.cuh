@@ -1,0 +1,204 @@
+// Per-point answers from the board engine: the Tromp-Taylor area map of a position (k_area_map) and Monte-Carlo ownership
+// from device playouts (k_playout_own).  One wave64 = one board, as everywhere else; Board<N> is used through its public
+// members only.
+//   area:    simple_flood_fill per colour + the black && !white / white && !black rule of simple_tt_scoring
+//            (base/go_state.h:32-93) -- Board::tt_area()'s fill, restated here because it must keep the rows it popcounts
+//   policy:  k_playout's (elf_amd.hip), restated move for move: uniform over the legal, non-true-eye points in x-major
+//            order, rng % count with playout_rng_k(key, ply), pass when there is none
+#pragma once
+#include "go_board.cuh"
+#include "engine_host.h"
+
+#define OWN_WAVE 64
+#define OWN_WAVES 4   // boards per workgroup of k_playout_own: k_playout's PLAYOUT_WAVES
+
+// seed(i, k) = seeds[i] + k * 0x9E3779B97F4A7C15 (mod 2^64): playout 0 of a row is what k_playout plays with seeds[i]
+__device__ __forceinline__ u64 own_seed(u64 row_seed, int k) { return row_seed + (u64)k * 0x9E3779B97F4A7C15ull; }
+
+// Area rows of the board's current stones: lane x < N ends with bit y of `ab` / `aw` set iff point a = x*N + y is black / white
+// area; lanes >= N hold 0.  Row-bitboard flood fill in registers, both colours at once, to a fixed point.
+template <int N>
+__device__ __forceinline__ void area_rows(const Board<N>& bd, u32& ab, u32& aw) {
+  constexpr int R = Geo<N>::R;
+  const int lane = bd.lane;
+  // re-slice the action-order bitboards into rows: row x = bits [x*N, x*N+N)
+  const int bit0 = (lane < N ? lane : 0) * N, w = bit0 >> 6, s = bit0 & 63;
+  u64 bl = 0, bh = 0, wl = 0, wh = 0;
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    const u64 bk = rl64(bd.Bw, k), wk = rl64(bd.Ww, k);
+    if (w == k) { bl = bk; wl = wk; }
+    if (w + 1 == k) { bh = bk; wh = wk; }
+  }
+  const u32 rowmask = (1u << N) - 1;
+  u32 B = 0, Wt = 0;
+  if (lane < N) {
+    B = (u32)(s ? ((bl >> s) | (bh << (64 - s))) : bl) & rowmask;
+    Wt = (u32)(s ? ((wl >> s) | (wh << (64 - s))) : wl) & rowmask;
+  }
+  const u32 E = (lane < N) ? (~(B | Wt) & rowmask) : 0u;
+  u32 rb = B, rw = Wt;
+  for (;;) {
+    u32 ub = __shfl_up(rb, 1, 64), db = __shfl_down(rb, 1, 64);
+    u32 uw = __shfl_up(rw, 1, 64), dw = __shfl_down(rw, 1, 64);
+    if (lane == 0) { ub = 0; uw = 0; }
+    if (lane >= N - 1) { db = 0; dw = 0; }
+    u32 nb = rb | (E & ((rb << 1) | (rb >> 1) | ub | db));
+    u32 nw = rw | (E & ((rw << 1) | (rw >> 1) | uw | dw));
+    // finish the in-row run before the next vertical exchange
+    for (int q = 0; q < 5; ++q) {
+      nb |= E & ((nb << 1) | (nb >> 1));
+      nw |= E & ((nw << 1) | (nw >> 1));
+    }
+    const bool ch = (nb != rb) || (nw != rw);
+    rb = nb; rw = nw;
+    if (!__any(ch)) break;
+  }
+  ab = rb & ~rw;
+  aw = rw & ~rb;
+}
+
+// area(black) - area(white) of the rows above, wave-uniform
+__device__ __forceinline__ int area_diff(u32 ab, u32 aw) {
+  int d = __popc(ab) - __popc(aw);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+  return rfl(d);
+}
+
+// out[i][a] = 0 neutral, 1 black area, 2 white area; a = x*N + y.  The super-ko rule of GoState::evaluate plays no part.
+template <int N>
+__global__ __launch_bounds__(OWN_WAVE) void k_area_map(Pool<N> pool, const int32_t* ids, int n, uint8_t* out) {
+  using G = Geo<N>;
+  __shared__ Slot<N> lds;
+  const int b = ids ? ids[blockIdx.x] : (int)blockIdx.x;
+  Board<N> bd;
+  bd.init(&lds, pool.zob, pool.skr(b));
+  bd.load(&pool.slots[b]);
+  u32 ab, aw;
+  area_rows<N>(bd, ab, aw);
+  if (bd.lane < N) {
+    uint8_t* o = out + (size_t)blockIdx.x * G::NP + bd.lane * N;
+    for (int y = 0; y < N; ++y) o[y] = (uint8_t)(((ab >> y) & 1u) | (((aw >> y) & 1u) << 1));
+  }
+}
+
+// +1 into dst[0][a] for every black-area point of this lane's row and into dst[1][a] for every white-area one.  dst is the
+// workgroup's LDS counters or a row of the global ones; integer adds, so the sums do not depend on who adds first.
+template <int N>
+__device__ __forceinline__ void own_add_rows(int* dst, u32 ab, u32 aw, int lane) {
+  constexpr int NP = Geo<N>::NP;
+  // one pass over the set bits (lanes >= N hold none); a loop, not N unrolled tests: the unrolled form's 2N addresses are
+  // invariant in the caller's playout loop and would be kept in registers across it
+  u32 m = ab | aw;
+  while (m) {
+    const int y = __builtin_ctz(m);
+    m &= m - 1;
+    atomicAdd(&dst[((ab >> y) & 1u ? 0 : NP) + lane * N + y], 1);
+  }
+}
+
+// Ownership: for source row i and playout k < K, a private copy of slot ids[i] is played to the end with seed(i, k) and its
+// area rows are added into counts[i][2][N*N]; stats[i] = {sum of (black area - white area), playouts with
+// (float)diff - komi > 0, playouts that ended on a super-ko repeat, steps played}.
+//  * The source slot is only read.  The copy lives in LDS; its super-ko records go to this wave's own record area in
+//    `scratch` ([lanes][MAXMOVE+2][SKW] u64), which receives the source's first sk_len records whenever the wave turns to
+//    another slot (a playout only appends behind them, so they survive from one playout of a slot to the next).
+//  * Waves are persistent: the (i, k) pairs, row-major, are cut into groups of OWN_WAVES consecutive pairs and workgroup g
+//    plays a contiguous run of groups, one pair per wave.  Scratch is therefore bounded by the waves in flight.
+//  * Counters are accumulated in LDS for the row the workgroup is on (the row of a group's first pair) and flushed with
+//    atomicAdd when that row changes and at the end; a wave whose pair already belongs to the next row (a group may straddle
+//    two rows) adds to the global counters directly.
+template <int N>
+__global__ __launch_bounds__(OWN_WAVE * OWN_WAVES) void k_playout_own(Pool<N> pool, u64* scratch, const int32_t* ids, const u64* seeds,
+                                                                       int n, int K, int max_steps, float komi, int32_t* counts,
+                                                                       unsigned long long* stats) {
+  using G = Geo<N>;
+  __shared__ Slot<N> lds_all[OWN_WAVES];
+  __shared__ u64 zlds[G::P];
+  __shared__ u32 mlds[G::NP + 2];   // floor(2^32 / d) for the pick's rng % candidates
+  __shared__ int acc[2 * G::NP];
+  for (int j = threadIdx.x; j < G::P; j += OWN_WAVE * OWN_WAVES) zlds[j] = pool.zob[j];
+  for (int j = threadIdx.x; j < G::NP + 2; j += OWN_WAVE * OWN_WAVES) mlds[j] = (u32)pool.zob[G::ZOBW + 4 * G::R + j];
+  for (int j = threadIdx.x; j < 2 * G::NP; j += OWN_WAVE * OWN_WAVES) acc[j] = 0;
+  __syncthreads();
+  const int wv = rfl((int)(threadIdx.x >> 6));   // wave-uniform by construction
+  u64* const rec = scratch + (size_t)(blockIdx.x * OWN_WAVES + wv) * (G::MAXMOVE + 2) * G::SKW;
+  Slot<N>& lds = lds_all[wv];
+  Board<N> bd;
+  bd.init(&lds, pool.zob, rec);
+  const GameSK<N> sk{rec};
+  const int pairs = n * K, groups = (pairs + OWN_WAVES - 1) / OWN_WAVES;   // n * K < 2^31 - OWN_WAVES: checked by the host
+  const int q0 = (int)((long long)groups * blockIdx.x / gridDim.x), q1 = (int)((long long)groups * (blockIdx.x + 1) / gridDim.x);
+  int have = -1;     // the slot whose record prefix `rec` holds
+  int wg_row = -1;   // the row `acc` counts for
+  auto flush = [&]() {
+    int* g = counts + (size_t)wg_row * 2 * G::NP;
+    for (int j = threadIdx.x; j < 2 * G::NP; j += OWN_WAVE * OWN_WAVES) {
+      const int v = acc[j];
+      if (v) { atomicAdd(&g[j], v); acc[j] = 0; }
+    }
+  };
+  for (int q = q0; q < q1; ++q) {
+    const int row0 = q * OWN_WAVES / K;
+    if (row0 != wg_row) {   // the same decision in every wave of the workgroup
+      if (wg_row >= 0) { flush(); __syncthreads(); }
+      wg_row = row0;
+    }
+    const int p = q * OWN_WAVES + wv;
+    if (p < pairs) {
+      const int row = p / K, k = p - row * K;
+      const int b = ids ? ids[row] : row;
+      bd.load(&pool.slots[b]);
+      if (b != have) {
+        const u64* src = pool.skr(b);
+        for (int j = bd.lane; j < bd.sk_len * G::SKW; j += OWN_WAVE) rec[j] = src[j];
+        have = b;
+      }
+      const u32 key = playout_key(own_seed(seeds[row], k));
+      bd.playout_begin(zlds);
+      int steps = 0;
+      while (steps < max_steps && !bd.terminated()) {
+        const u32 x = playout_rng_k(key, (u32)bd.ply);
+        u64 legal, cand;
+        bd.template legal_moves<true, true>(legal, cand);
+        // the (x % total)-th set bit of the lane-distributed candidate bitboard: inclusive prefix sum of the word counts over
+        // the lanes of row 0 on the DPP network, the word, the rank inside it
+        const int cnt = __popcll(cand);
+        int inc = cnt;
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, true);
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, true);
+        if (G::R > 4) inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, true);
+        const int total = rl(inc, G::R - 1);
+        int pick_a = -1;   // action id of the chosen candidate, -1 = pass
+        if (total > 0) {
+          const u32 qd = __umulhi(x, (u32)rfl((int)mlds[total]));   // floor(2^32 / total) estimate of x / total, at most one too small
+          u32 rr = x - qd * (u32)total;
+          if (rr >= (u32)total) rr -= (u32)total;
+          const int kw = __popc((u32)bal_le((u32)inc, rr) & ((1u << G::R) - 1u));
+          const int base = rl(inc - cnt, kw);
+          const u64 wk = rl64(cand, kw);
+          const u32 rank = __builtin_amdgcn_mbcnt_hi((u32)(wk >> 32), __builtin_amdgcn_mbcnt_lo((u32)wk, 0));
+          const u64 sel = bal_eq(rank, rr - (u32)base) & wk;
+          pick_a = kw * 64 + (int)__builtin_ctzll(sel);
+        }
+        if (!(pick_a >= 0 ? bd.forward_legal_action(pick_a, sk) : bd.forward(M_PASS, sk))) break;
+        ++steps;
+      }
+      u32 ab, aw;
+      area_rows<N>(bd, ab, aw);
+      const int diff = area_diff(ab, aw);
+      if (row == wg_row) own_add_rows<N>(acc, ab, aw, bd.lane);
+      else own_add_rows<N>(counts + (size_t)row * 2 * G::NP, ab, aw, bd.lane);
+      if (bd.lane == 0) {
+        unsigned long long* st = stats + (size_t)row * 4;
+        atomicAdd(&st[0], (unsigned long long)(long long)diff);
+        if ((float)diff - komi > 0.0f) atomicAdd(&st[1], 1ull);
+        if (bd.superko) atomicAdd(&st[2], 1ull);
+        atomicAdd(&st[3], (unsigned long long)steps);
+      }
+    }
+    __syncthreads();   // this group's LDS adds are in before a flush reads them
+  }
+  if (wg_row >= 0) flush();
+}

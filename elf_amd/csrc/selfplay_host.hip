@@ -1337,3 +1337,9 @@ int elfsp_search_log(const ElfSelfPlay* sp, int first, int n, ElfSpSearch* rec, 
 }
 
 }  // extern "C"
+
+// Area map and Monte-Carlo ownership (elfgo_area_map, elfgo_own_*): device code in ownership.cuh, entry points and launches in
+// ownership_host.h.  They are compiled here only because this is the library's one HIP translation unit that the hash of the
+// profiled kernel sources (elf_amd._lib.KERNEL_SOURCES, stamped into profiles/pmc_*.json) does not cover; the next change that
+// re-profiles moves them into a translation unit of their own.
+#include "ownership_host.h"

@@ -109,6 +109,9 @@ class GoEngine:
 
     def close(self):
         if getattr(self, "_h", None):
+            if getattr(self, "_own", None):
+                self.L.elfgo_own_destroy(self._own[1])
+                self._own = None
             if not getattr(self, "_borrowed", False):
                 self.L.elfgo_destroy(self._h)
             self._h = None
@@ -230,3 +233,44 @@ class GoEngine:
             out = torch.empty((k, 4), dtype=torch.int32, device=self.device)
         check(self.L.elfgo_playout(self._h, p, C.c_void_p(sd.data_ptr()), k, int(max_steps), C.c_void_p(out.data_ptr()), self._stream()))
         return out
+
+    # ---- per-point answers
+    def area_map(self, ids=None, n=None):
+        """Tromp-Taylor area per point -> uint8 tensor [k, N*N]: 0 neutral, 1 black, 2 white, index a = x*N + y."""
+        t, p, k = self._ids(ids, n)
+        out = torch.empty((k, self.n * self.n), dtype=torch.uint8, device=self.device)
+        check(self.L.elfgo_area_map(self._h, p, k, C.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
+    def ownership(self, seeds, ids=None, playouts=256, komi=7.5, max_steps=1 << 20, max_lanes=0):
+        """Monte-Carlo ownership: `playouts` config-2 playouts from a private copy of each listed slot (the slots themselves are
+        only read), playout k of row i with seed seeds[i] + k * 0x9E3779B97F4A7C15 (mod 2^64).  Returns a dict:
+        counts int32 [k, 2, N*N] (playouts in which the point ended as black / white area) and stats int64 [k, 4] (sum of
+        black - white area, black wins after komi, super-ko endings, steps played) straight from the device, and derived from
+        them own = (black - white) / playouts float32 [k, N*N], score_mean = mean area difference - komi, black_win_rate.
+        The scratch handle is made on first use and lives until close(); max_lanes bounds the playouts in flight (0 = a default
+        from the CU count)."""
+        if isinstance(seeds, torch.Tensor):
+            sd = seeds.to(self.device).contiguous()
+        else:
+            sd = torch.from_numpy(np.ascontiguousarray(seeds, dtype=np.uint64).view(np.int64)).to(self.device)
+        k = sd.numel()
+        t, p, k2 = self._ids(ids, k)
+        assert k2 == k
+        own = getattr(self, "_own", None)
+        if own is None or own[0] != int(max_lanes):
+            if own is not None:
+                self.sync()
+                self.L.elfgo_own_destroy(own[1])
+                self._own = None
+            h = C.c_void_p()
+            check(self.L.elfgo_own_create(self._h, int(max_lanes), C.byref(h)))
+            self._own = own = (int(max_lanes), h)
+        counts = torch.empty((k, 2, self.n * self.n), dtype=torch.int32, device=self.device)
+        stats = torch.empty((k, 4), dtype=torch.int64, device=self.device)
+        check(self.L.elfgo_own_run(own[1], p, C.c_void_p(sd.data_ptr()), k, int(playouts), int(max_steps), float(komi),
+                                   C.c_void_p(counts.data_ptr()), C.c_void_p(stats.data_ptr()), self._stream()))
+        return dict(counts=counts, stats=stats,
+                    own=(counts[:, 0] - counts[:, 1]).to(torch.float32) / playouts,
+                    score_mean=stats[:, 0].to(torch.float64) / playouts - komi,
+                    black_win_rate=stats[:, 1].to(torch.float64) / playouts)

@@ -39,7 +39,7 @@ def xy2move(x, y):
 
 
 class GtpEngine:
-    def __init__(self, actor, board_size=19, komi=7.5, device=0, **selfplay_options):
+    def __init__(self, actor, board_size=19, komi=7.5, device=0, status_playouts=256, status_seed=1, **selfplay_options):
         opts = dict(mcts_rollout_per_thread=1600, mcts_rollout_per_batch=8, mcts_puct=1.5, mcts_virtual_loss=1,
                     mcts_persistent_tree=True, policy_distri_cutoff=0, resign_thres=0.0, seed=1)
         opts.update(selfplay_options)
@@ -49,9 +49,15 @@ class GtpEngine:
         self.sp.reg_callback("actor_black", actor)
         self.boards = self.sp.board_engine()
         self.exit = False
+        self.status_playouts = int(status_playouts)
+        self.status_seed = int(status_seed)
         self.commands = {k[3:]: f for k, f in inspect.getmembers(self, predicate=inspect.ismethod) if k.startswith("on_")}
+        # private extensions carry the "elf-" prefix (GTP 2, section 2.13); a method name cannot hold the hyphen
+        self.commands["elf-ownership"] = self.commands.pop("elf_ownership")
+        self.commands["elf-score_estimate"] = self.commands.pop("elf_score_estimate")
 
     def close(self):
+        self.boards.close()      # the ownership scratch goes before the engine it was made over
         self.sp.close()
 
     # ---- board queries (GoGameSelfPlay.showBoard/getNextPlayer/getLastMove/getScore, inference/Pybind.cc:31-45)
@@ -153,6 +159,35 @@ class GtpEngine:
             score = float(self.boards.evaluate(komi=self.komi, n=1).cpu()[0])     # GoGameSelfPlay::getScore
         else:
             score = float(self.sp.last_score()[0])                                # getLastScore
+        return True, ("B+%.1f" % score) if score > 0 else ("W+%.1f" % -score)
+
+    # ---- dead stones and territory by random playouts (GoEngine.ownership on game 0's current position)
+    def _status_counts(self):
+        """-> (stone colour per point, playouts that ended with the point black, ... white), numpy [N*N] in action order"""
+        import numpy as np
+        own = self.boards.ownership(np.array([self.status_seed], np.uint64), ids=[0], playouts=self.status_playouts, komi=self.komi)
+        counts = own["counts"].cpu().numpy()[0]
+        col = self.boards.export_board(n=1)[0].cpu().numpy()[0]
+        return col, counts[0], counts[1]
+
+    def on_final_status_list(self, items):
+        """A stone is dead iff its point ends as the opponent's area in more of the playouts than as its own colour's, else
+        alive.  Seki is not detected: `seki` is always the empty list (stones in seki are reported alive)."""
+        if len(items) < 2 or items[1] not in ("dead", "alive", "seki"):
+            return False, "invalid status"
+        col, cb, cw = self._status_counts()
+        dead = ((col == 1) & (cw > cb)) | ((col == 2) & (cb > cw))
+        pick = dead if items[1] == "dead" else ((col != 0) & ~dead) if items[1] == "alive" else (col < 0)
+        return True, " ".join(xy2move(a // self.n, a % self.n) for a in range(self.n * self.n) if pick[a])
+
+    def on_elf_ownership(self, items):
+        col, cb, cw = self._status_counts()
+        own = (cb - cw).reshape(self.n, self.n) / float(self.status_playouts)     # [x][y]
+        return True, "\n" + "\n".join(" ".join("%5.2f" % own[x, y] for x in range(self.n)) for y in range(self.n - 1, -1, -1))
+
+    def on_elf_score_estimate(self, items):
+        col, cb, cw = self._status_counts()
+        score = float(int((cb > cw).sum()) - int((cw > cb).sum())) - self.komi
         return True, ("B+%.1f" % score) if score > 0 else ("W+%.1f" % -score)
 
     def on_list_commands(self, items):

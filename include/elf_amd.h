@@ -91,6 +91,33 @@ int elfgo_export_board(ElfGoEngine* e, const int32_t* ids, int n, uint8_t* colou
 int elfgo_playout(ElfGoEngine* e, const int32_t* ids, const uint64_t* seeds, int n, int max_steps,
                   uint32_t* out, void* stream);
 
+/* Tromp-Taylor area of each point of a position (simple_flood_fill per colour + the black && !white / white && !black rule of
+ * simple_tt_scoring, go_state.h:32-93): out[i][a] = 0 neutral, 1 black, 2 white, a = x*N + y (the action order of
+ * elfgo_legal_mask under D4 code 0); row stride N*N bytes.  Always the flood fill of the stones: the super-ko +-1 rule of
+ * GoState::evaluate plays no part. */
+int elfgo_area_map(ElfGoEngine* e, const int32_t* ids, int n, uint8_t* out, void* stream);
+
+/* Monte-Carlo ownership from device playouts.  The handle owns the scratch of the playout copies (one super-ko record area
+ * per wave in flight) and the launch geometry; several handles may share an engine.  max_lanes = waves in flight
+ * (<= 0: a default from the device's CU count); destroy the handle before its engine. */
+typedef struct ElfGoOwnership ElfGoOwnership;
+int elfgo_own_create(ElfGoEngine* e, int max_lanes, ElfGoOwnership** out);
+int elfgo_own_destroy(ElfGoOwnership* o);
+size_t elfgo_own_scratch_bytes(const ElfGoOwnership* o);
+/* For source row i < n and playout k < playouts: a private copy of slot ids[i] is played with elfgo_playout's policy and RNG
+ * to GoState::terminated() or max_steps, with
+ *     seed(i, k) = seeds[i] + k * 0x9E3779B97F4A7C15   (mod 2^64)
+ * (playout 0 of a row is what elfgo_playout would play from that slot with seeds[i]), and the area map of its end position
+ * (elfgo_area_map's; a playout cut by max_steps is scored where it stands) is added into
+ *     counts[i][0][a] black, counts[i][1][a] white                       int32 [n][2][N*N]
+ *     stats[i] = { sum of (black area - white area), playouts with (float)diff - komi > 0,
+ *                  playouts that ended with the super-ko flag set, sum of steps played }   int64 [n][4]
+ * The call zeroes counts and stats on `stream` itself.  Integer sums only: the result does not depend on scheduling or on
+ * max_lanes.  The source slots are only read (header, stones, Bloom words and super-ko records alike); a slot may be named
+ * several times.  ELFGO_E_BADARG for a null pointer (ids may be NULL), n <= 0 or playouts <= 0. */
+int elfgo_own_run(ElfGoOwnership* o, const int32_t* ids, const uint64_t* seeds, int n, int playouts, int max_steps,
+                  float komi, int32_t* counts, int64_t* stats, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Device-resident MCTS (one tree per game) -- replaces, behind the same seams, the reference's
  *   elf/ai/tree_search/tree_search.h        TreeSearchT / TreeSearchSingleThreadT::batch_rollouts (:200-262)
