@@ -378,6 +378,12 @@ int orc_is_true_eye(const OrcState* st, int c, int player) {
   return !fake;
 }
 
+/* orc_is_true_eye of every point for `player`, action order a = x*N + y (one call per position for the per-ply tests) */
+void orc_true_eye_mask(const OrcState* st, int player, uint8_t* mask) {
+  for (int x = 0; x < N; ++x)
+    for (int y = 0; y < N; ++y) mask[x * N + y] = (uint8_t)orc_is_true_eye(st, OFFSETXY(x, y), player);
+}
+
 /* ---- config-2 protocol, RNG shared verbatim with ref_capi.cc and the HIP kernel */
 static inline uint32_t fmix32(uint32_t h) {
   h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;

@@ -1,8 +1,10 @@
 """TEST INFRASTRUCTURE ONLY: ctypes bindings for the two CPU checkers.
 
 * ``Port(n)``  -> oracle/libgo_oracle{n}.so  (C restatement, oracle/go_oracle.c; travels as source)
-* ``Ref(n)``   -> oracle/_ref/libelfref{n}.so (the real reference compiled in place; prebuilt .so
-                  travels to the GPU box, sources never enter this repo)
+* ``Ref(n)``   -> oracle/_ref/libelfref{n}.so (the real reference compiled in place against the stand-in headers of
+                  oracle/shim; prebuilt .so travels to the GPU box, sources never enter this repo)
+* ``RefBoard(n)`` -> oracle/_ref/libelfboard{n}.so (the reference's board engine alone, base/board.cc + base/common.cc, built
+                  with NO stand-in on the include path: evidence that shares no header with ``Ref``)
 
 Both expose the same small interface so tests can run one move list through either.
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
@@ -113,6 +115,21 @@ class _Engine:
     def is_true_eye(self, s, c, player):
         return bool(self._eye(s, int(c), int(player)))
 
+    def true_eye_mask(self, s, player):
+        """is_true_eye of every point for `player`, action order (x*n + y)"""
+        n = self.n
+        a = np.zeros(n * n, np.uint8)
+        f = getattr(self.L, self.prefix + "true_eye_mask", None)
+        if f is not None:
+            f.restype = None
+            f.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+            f(s, int(player), a.ctypes.data)
+        else:
+            for x in range(n):
+                for y in range(n):
+                    a[x * n + y] = self._eye(s, (y + 1) * (n + 2) + x + 1, int(player))
+        return a
+
     def playout_moves(self, s, seed, max_steps=100000):
         mv = np.zeros(2 * self.n * self.n + 8, np.int32)
         k = self._pm(s, C.c_uint64(int(seed)), int(max_steps), mv.ctypes.data)
@@ -205,6 +222,106 @@ class Ref(_Engine):
         self.L.ref_zobrist.argtypes = [C.c_void_p]
         self.L.ref_zobrist(z.ctypes.data)
         return z
+
+
+class RefBoard:
+    """The reference's board engine with no stand-in header anywhere in its build (oracle/ref_board_capi.cc over base/board.cc +
+    base/common.cc).  A handle is a plain Board: play() is TryPlay2 + Play, which is all GoState::forward does to its board;
+    super-ko, the move limit and `terminated` are GoState-level and do not exist here."""
+
+    @staticmethod
+    def path(n):
+        return os.path.join(HERE, "_ref", "libelfboard%d.so" % n)
+
+    @staticmethod
+    def available(n=19):
+        return os.path.exists(RefBoard.path(n))
+
+    def __init__(self, n=19):
+        self.n = n
+        L = self.L = C.CDLL(RefBoard.path(n))
+        vp = C.c_void_p
+        for name, res, args in (("new", vp, []), ("free", None, [vp]), ("reset", None, [vp]), ("clone", vp, [vp]),
+                                ("play", C.c_int, [vp, C.c_int]), ("try_play", C.c_int, [vp, C.c_int]), ("hash", C.c_uint64, [vp]),
+                                ("info", None, [vp, vp]), ("board", None, [vp, vp, vp]), ("legal_mask", None, [vp, vp]),
+                                ("true_eye_mask", None, [vp, C.c_int, vp]), ("is_true_eye", C.c_int, [vp, C.c_int, C.c_int]),
+                                ("is_game_end", C.c_int, [vp]), ("valid_moves", C.c_int, [vp, C.c_int, vp]),
+                                ("replay", C.c_int, [vp, vp, C.c_int] + [vp] * 8), ("board_size", C.c_int, [])):
+            f = getattr(L, "rb_" + name)
+            f.restype, f.argtypes = res, args
+        assert L.rb_board_size() == n
+
+    def new(self):
+        return self.L.rb_new()
+
+    def free(self, b):
+        self.L.rb_free(b)
+
+    def reset(self, b):
+        self.L.rb_reset(b)
+
+    def clone(self, b):
+        return self.L.rb_clone(b)
+
+    def play(self, b, c):
+        """TryPlay2 then Play; the TryPlay2 result"""
+        return self.L.rb_play(b, int(c))
+
+    def try_play(self, b, c):
+        return self.L.rb_try_play(b, int(c))
+
+    def hash(self, b):
+        return int(self.L.rb_hash(b))
+
+    def info(self, b):
+        a = np.zeros(10, np.int32)
+        self.L.rb_info(b, a.ctypes.data)
+        return a
+
+    def board(self, b):
+        col = np.zeros(self.n * self.n, np.uint8)
+        lib = np.zeros(self.n * self.n, np.int16)
+        self.L.rb_board(b, col.ctypes.data, lib.ctypes.data)
+        return col, lib
+
+    def legal_mask(self, b):
+        a = np.zeros(self.n * self.n + 1, np.uint8)
+        self.L.rb_legal_mask(b, a.ctypes.data)
+        return a
+
+    def true_eye_mask(self, b, player):
+        a = np.zeros(self.n * self.n, np.uint8)
+        self.L.rb_true_eye_mask(b, int(player), a.ctypes.data)
+        return a
+
+    def is_true_eye(self, b, c, player):
+        return bool(self.L.rb_is_true_eye(b, int(c), int(player)))
+
+    def is_game_end(self, b):
+        return bool(self.L.rb_is_game_end(b))
+
+    def valid_moves(self, b, player):
+        """FindAllValidMoves for `player`, in that function's own order (Coords)"""
+        a = np.zeros(self.n * self.n, np.int32)
+        k = self.L.rb_valid_moves(b, int(player), a.ctypes.data)
+        return a[:k].copy()
+
+    def replay(self, moves, b=None):
+        """One call per game: plays `moves` from `b` (a fresh board when None, freed afterwards) and returns the arrays of all
+        len(moves) + 1 positions (row 0 = before the first move): dict(ok [k], hash [k+1] u64, info [k+1,10], colour, libs
+        [k+1,n*n], legal [k+1,n*n+1], eyes [k+1,2,n*n] (Black's, White's), game_end [k+1])"""
+        mv = np.ascontiguousarray(moves, dtype=np.int32)
+        k, p = mv.size, self.n * self.n
+        out = dict(ok=np.zeros(k, np.uint8), hash=np.zeros(k + 1, np.uint64), info=np.zeros((k + 1, 10), np.int32),
+                   colour=np.zeros((k + 1, p), np.uint8), libs=np.zeros((k + 1, p), np.int16), legal=np.zeros((k + 1, p + 1), np.uint8),
+                   eyes=np.zeros((k + 1, 2, p), np.uint8), game_end=np.zeros(k + 1, np.uint8))
+        own = b is None
+        if own:
+            b = self.new()
+        self.L.rb_replay(b, mv.ctypes.data, k, *[out[f].ctypes.data for f in ("ok", "hash", "info", "colour", "libs", "legal", "eyes", "game_end")])
+        if own:
+            self.free(b)
+        return out
 
 
 # ---- MCTS / self-play: the real reference stack (oracle/ref_selfplay.cc) and the stub net ----------------
