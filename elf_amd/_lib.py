@@ -42,6 +42,7 @@ SIGNATURES = {
     "elfgo_info": (_i, [_vp, _vp, _i, _vp, _vp]),
     "elfgo_export_board": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "elfgo_playout": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "elfgo_setup": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "elfgo_area_map": (_i, [_vp, _vp, _i, _vp, _vp]),
     "elfgo_own_create": (_i, [_vp, _i, C.POINTER(_vp)]),
     "elfgo_own_destroy": (_i, [_vp]),
@@ -89,6 +90,7 @@ SIGNATURES = {
     "elfsp_set_request2": (_i, [_vp, _vp]),
     "elfsp_set_request3": (_i, [_vp, _vp, _vp]),
     "elfrec_sgf_parse": (_i, [_i, C.c_char_p, _vp, _vp, _i, _vp]),
+    "elfrec_sgf_setup": (_i, [_i, C.c_char_p, _vp, _vp]),
     "elfrec_game_sgf": (_i64, [_vp, _vp, _i, _vp, _i, _f, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
     "elfrec_record_to_sgf": (_i64, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, _sz, C.c_char_p, _sz]),
     "elfrec_client_create": (_i, [C.c_char_p, C.POINTER(_vp)]),
@@ -120,6 +122,8 @@ SIGNATURES = {
     "elfsp_play": (_i, [_vp, _vp, _vp]),
     "elfsp_preload": (_i, [_vp, _vp, _i, _i, _vp]),
     "elfsp_restart": (_i, [_vp, _vp, _i, _vp]),
+    "elfsp_setup": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "elfsp_undo": (_i, [_vp, _vp, _i, _i, _vp]),
     "elfsp_finish": (_i, [_vp, _vp, _i, _i, _vp]),
     "elfsp_take_finished": (_i, [_vp, _vp, _i]),
     "elfsp_last_score": (_i, [_vp, _vp]),

@@ -448,6 +448,57 @@ int elfrec_sgf_parse(int board_size, const char* text, int32_t* players, uint16_
   return count;
 }
 
+// The AB / AW points of the header node, which the reader above (like the reference's) drops.  The scan is get_key_values' again:
+// a backslash hides the next character, a value runs to the next visible ']', the node ends at a visible ';' or ')' outside a
+// value; the second, third ... value of a property has an empty key and belongs to the property before it.
+int elfrec_sgf_setup(int board_size, const char* text, uint8_t* stones, ElfSgfHeader* header) {
+  if (board_size < 1 || !text || !stones) return ELFGO_E_BADARG;
+  const int N = board_size;
+  memset(stones, 0, (size_t)N * N);
+  if (header) {
+    header->size = N; header->komi = 7.5f; header->handi = 0; header->winner = 3; header->win_margin = 0.0f;
+    (void)elfrec_sgf_parse(board_size, text, nullptr, nullptr, 0, header);   // fills it when the text has entries
+  }
+  const int len = (int)strlen(text);
+  int i = 0;
+  while (i < len && text[i] != ';') i++;
+  if (i >= len) return 0;
+  std::string key, last_key;
+  int start = i + 1;
+  bool in_value = false, backslash = false;
+  auto blank = [](char c) { return c == ' ' || c == '\n' || c == '\r' || c == '\t'; };
+  for (++i; i < len; ++i) {
+    if (text[i] == '\\') { backslash = !backslash; continue; }
+    if (backslash) { backslash = false; continue; }
+    const char c = text[i];
+    if (!in_value) {
+      if (c == '[') {
+        int k0 = start, k1 = i;
+        while (k0 < k1 && blank(text[k0])) k0++;
+        while (k1 > k0 && blank(text[k1 - 1])) k1--;
+        key.assign(text + k0, (size_t)(k1 - k0));
+        if (key.empty()) key = last_key;
+        last_key = key;
+        start = i + 1;
+        in_value = true;
+      } else if (c == ';' || c == ')') break;
+    } else if (c == ']') {
+      const int colour = key == "AB" ? 1 : key == "AW" ? 2 : 0;
+      if (colour) {
+        int xy[2] = {0, 0}, m = 0;   // exactly two visible characters: a compressed list ("aa:cc") is not a point and is ignored
+        for (int j = start; j < i; ++j)
+          if (!blank(text[j])) { if (m < 2) xy[m] = text[j] - 'a'; ++m; }
+        if (m == 2 && xy[0] >= 0 && xy[0] < N && xy[1] >= 0 && xy[1] < N) stones[xy[0] * N + xy[1]] = (uint8_t)colour;
+      }
+      start = i + 1;
+      in_value = false;
+    }
+  }
+  int count = 0;
+  for (int a = 0; a < N * N; ++a) count += stones[a] != 0;
+  return count;
+}
+
 // GoStateExt::dumpSgf (go_state_ext.cc:26-82): the SGF text finish_game writes to <dump_record_prefix>_<game>_<seq>_<B|W>.sgf
 // (game_selfplay.cc:133-135, go_state_ext.h:48-56): result, player names, komi, every move with its predicted value.  The same
 // iostream / std::to_string calls as the reference, so that the numbers print alike.  git_hash / git_staged: the two lines of the

@@ -64,6 +64,11 @@ struct SpRequest {          // MsgRequest (common/record.h:119-149): ModelPair +
   void set_wait() { black_ver = white_ver = -1; }
 };
 
+struct SpPly {                // one move since the game (re)started, with what it appended to the pending Record
+  uint16_t move;
+  uint8_t has_value, has_policy;
+};
+
 struct SpGame {
   std::mt19937 rng;            // GoGameBase::_rng (game_base.h:32-38)
   std::mt19937 actor_rng[2];   // MCTSActor::rng_ (go/mcts/mcts.h:52) of "actor_black" / "actor_white", seeded with _rng() (game_selfplay.cc:47)
@@ -91,6 +96,15 @@ struct SpGame {
   bool policy_only = false;    // MCTSAI_T::actPolicyOnly instead of act
   SpRecord rec;                // GoStateExt::_mcts_policies / _predicted_values / the game's moves (go_state_ext.h:131-148)
   std::set<int64_t> using_models;   // GoStateExt::using_models_: every model version this game has been played with
+  // what elfsp_undo rebuilds the game from (setup_host.h): the set-up stones, if any, and every move since the (re)start
+  bool set_up = false;
+  uint8_t setup_player = 1;
+  std::vector<uint8_t> setup_stones;   // [N*N] when set_up
+  std::vector<SpPly> played;
+  bool pend_value = false, pend_policy = false;   // what the search that has just ended appended to `rec`
+  // the side to move: every move (a pass too) advances the ply by one, so it is the parity of the ply -- ply 1 = Black to move --
+  // unless the game was set up with White to move (elfsp_setup leaves the ply at 1)
+  bool black_to_move() const { return ((ply & 1) == 1) != (set_up && setup_player == S_WHITE); }
   void add_current_model() {   // GoStateExt::addCurrentModel (go_state_ext.h:68-73)
     if (req.black_ver >= 0) using_models.insert(req.black_ver);
     if (req.white_ver >= 0) using_models.insert(req.white_ver);
@@ -144,6 +158,7 @@ struct ElfSelfPlay {
   SpBuf<int32_t> coord, visits, moves, ids, binfo;
   SpBuf<float> prior, reward, etas, Z, val;
   SpBuf<uint8_t> ok;
+  SpBuf<uint8_t> su_stones, su_player;   // [G][N*N], [G]: the rows of an elfgo_setup launch (elfsp_setup, elfsp_undo)
   bool step_open = false;        // between begin_step and end_step
   // requests: `cur` is the one being delivered (every game must receive it before the next one goes out, dispatcher.h:104-152)
   std::deque<SpRequest> mailbox;
@@ -254,7 +269,7 @@ static void sp_finish_record(ElfSelfPlay* sp, int g, float final_value, int fina
   gm.last_final = final_value;
   sp->finished_values.push_back(final_value);
   if (sp->finished_values.size() > 65536) sp->finished_values.pop_front();
-  if (sp->opt.keep_records > 0) {
+  if (sp->opt.keep_records > 0 && !gm.set_up) {   // a Record cannot carry set-up stones: the trainer would replay it from the empty board
     SpRecord& r = gm.rec;
     r.reward = final_value;                      // _state.getFinalValue()
     r.never_resign = gm.never_resign;
@@ -274,6 +289,7 @@ static void sp_state_restart(SpGame& gm) {
   gm.ply = 1; gm.never_resign = false; gm.has_calculated_never_resign = false; gm.last_predicted = 0.0f;
   gm.seq++;
   gm.rec = SpRecord();
+  gm.set_up = false; gm.setup_stones.clear(); gm.played.clear();
   gm.using_models.clear();
   gm.add_current_model();
 }
@@ -294,6 +310,7 @@ static int sp_forward_preload(ElfSelfPlay* sp, const std::vector<int32_t>& ids) 
       if (sp->ok.h[j] != 1) return ELFGO_E_MCTS_BASE - ELFMCTS_E_FORWARD;   // "Preload sgf: move not valid!" :211-215
     for (int g : ids) {
       sp->games[g].ply++;
+      sp->games[g].played.push_back(SpPly{(uint16_t)sp->sgf[fwd], 0, 0});
       if (sp->opt.keep_records > 0) sp->games[g].rec.moves.push_back((uint16_t)sp->sgf[fwd]);
     }
   }
@@ -504,7 +521,7 @@ static int sp_begin_searches(ElfSelfPlay* sp) {
     SpGame& gm = sp->games[g];
     if (gm.phase != PH_PLAY || gm.ai >= 0) continue;
     gm.online_counter++;
-    const int colour = (gm.ply & 1) ? 0 : 1;      // ply 1 = Black to move
+    const int colour = gm.black_to_move() ? 0 : 1;
     const int a = gm.pool_of_colour[colour];
     gm.ai = a;
     gm.policy_only = colour == 0 ? sp->opt.black_use_policy_network_only != 0 : sp->opt.white_use_policy_network_only != 0;
@@ -608,7 +625,7 @@ static float sp_final_value(ElfSelfPlay* sp, SpGame& gm, int reason, float evalu
     return fv;
   }
   if (gm.req.is_selfplay() && sp->opt.cheat_selfplay_random_result) return gm.rng() % 2 == 0 ? 1.0f : -1.0f;
-  if (reason == ELFSP_FR_RESIGN) return ((gm.ply & 1) == 1) ? -1.0f : 1.0f;   // nextPlayer() == S_WHITE ? 1 : -1; ply 1 = Black to move
+  if (reason == ELFSP_FR_RESIGN) return gm.black_to_move() ? -1.0f : 1.0f;   // nextPlayer() == S_WHITE ? 1 : -1
   return evaluated;
 }
 // one finished game: score it (sp_final_value), count it, write its record
@@ -714,7 +731,7 @@ static SpDecision sp_decide_move(SpGame& gm, const ElfSpOptions& opt, const SpRo
   gm.last_predicted = predicted;
   if (opt.keep_records > 0) gm.rec.values.push_back(predicted);   // addPredictedValue, mcts_update_info :98-100
   if (opt.following_pass) {   // "If the opponent wants pass, and we are in good, we follow." :104-111 (human games)
-    const bool black = (gm.ply & 1) == 1;
+    const bool black = gm.black_to_move();
     const float sc = tt_score;
     const bool we_are_good = black ? (sc > 0 && predicted > 0.9) : (sc < 0 && predicted < -0.9);
     if (we_are_good && last_board_move == M_PASS && gm.ply > 1) c = M_PASS;
@@ -722,7 +739,7 @@ static SpDecision sp_decide_move(SpGame& gm, const ElfSpOptions& opt, const SpRo
   // shouldResign (go_state_ext.h:207-214) -> ResignCheck::check (game_utils.h:24-40); side to move = parity of ply
   bool resign = false;
   {
-    const bool black = (gm.ply & 1) == 1;   // ply 1 = Black to move
+    const bool black = gm.black_to_move();
     const float value = black ? predicted : -predicted;
     if (!gm.has_calculated_never_resign) {
       std::uniform_real_distribution<> dis(0.0, 1.0);
@@ -777,6 +794,7 @@ static int sp_finish_moves(ElfSelfPlay* sp, const std::vector<int32_t> (&done)[2
       SpRoot root{info[0], &sp->coord.h[(size_t)g * NE], &sp->visits.h[(size_t)g * NE], &sp->prior.h[(size_t)g * NE],
                   &sp->reward.h[(size_t)g * NE], 0.0f};
       memcpy(&root.root_value, &info[4], 4);
+      const size_t n_val = gm.rec.values.size(), n_pol = gm.rec.policies.size();
       const SpDecision d = sp_decide_move(gm, sp->opt, root, follow ? sp->val.h[di] : 0.0f,
                                           follow ? sp->binfo.h[di * ELFGO_INFO_WORDS + 2] : -1, sp->pick_rng);
       if (sp->log_cap > 0 && (int)sp->log_search.size() < sp->log_cap) {
@@ -789,6 +807,7 @@ static int sp_finish_moves(ElfSelfPlay* sp, const std::vector<int32_t> (&done)[2
         sp->log_prior.insert(sp->log_prior.end(), root.prior, root.prior + NE);
         sp->log_reward.insert(sp->log_reward.end(), root.reward, root.reward + NE);
       }
+      gm.pend_value = gm.rec.values.size() != n_val; gm.pend_policy = gm.rec.policies.size() != n_pol;
       gm.ai = -1;
       sp->n_moves++;
       if (d.resign && gm.ply >= 50) {
@@ -841,6 +860,7 @@ static int sp_finish_moves(ElfSelfPlay* sp, const std::vector<int32_t> (&done)[2
       if (sp->ok.h[i] != 1) return ELFGO_E_MCTS_BASE - ELFMCTS_E_FORWARD;   // "Something is wrong! Move cannot be applied" :409-418
       const int32_t* bi = &sp->binfo.h[i * ELFGO_INFO_WORDS];
       gm.ply = bi[0];
+      gm.played.push_back(SpPly{(uint16_t)sp->moves.h[g], (uint8_t)gm.pend_value, (uint8_t)gm.pend_policy});
       if (sp->opt.keep_records > 0) gm.rec.moves.push_back((uint16_t)sp->moves.h[g]);   // GoState::_moves
       const bool terminated = bi[9] != 0;
       if (terminated || (sp->opt.move_cutoff > 0 && gm.ply >= sp->opt.move_cutoff)) by_end.push_back(g);   // :420-429
@@ -918,7 +938,8 @@ int elfsp_create(const ElfSpOptions* o, int device, const uint64_t* zobrist_host
   hipError_t e = sp->info.alloc((size_t)G * ELFMCTS_ROOT_WORDS);   // the first failure ends the chain
   (e || (e = sp->coord.alloc(GE)) || (e = sp->visits.alloc(GE)) || (e = sp->prior.alloc(GE)) || (e = sp->reward.alloc(GE)) ||
    (e = sp->etas.alloc(GE)) || (e = sp->Z.alloc(G)) || (e = sp->moves.alloc(G)) || (e = sp->ids.alloc(G)) || (e = sp->val.alloc(G)) ||
-   (e = sp->ok.alloc(G)) || (e = sp->binfo.alloc((size_t)G * ELFGO_INFO_WORDS)));
+   (e = sp->ok.alloc(G)) || (e = sp->binfo.alloc((size_t)G * ELFGO_INFO_WORDS)) ||
+   (e = sp->su_stones.alloc((size_t)G * o->board_size * o->board_size)) || (e = sp->su_player.alloc(G)));
   if (e != hipSuccess) { elfsp_destroy(sp); return (int)e; }
   sp->log_cap = o->log_searches;
   // the request the games start under unless the caller sends one before the first step: self-play with ElfSpOptions.model_ver
@@ -1219,6 +1240,7 @@ int elfsp_play(ElfSelfPlay* sp, const int32_t* moves_host, void* stream) {
     SpGame& gm = sp->games[g];
     const int32_t* bi = &sp->binfo.h[g * ELFGO_INFO_WORDS];
     gm.ply = bi[0];
+    gm.played.push_back(SpPly{(uint16_t)adv[g], 0, 0});
     if (sp->opt.keep_records > 0) gm.rec.moves.push_back((uint16_t)adv[g]);
     if (bi[2] == M_PASS && bi[3] == M_PASS) two_pass.push_back(g);   // "If the human opponent pass, we pass as well" :319-322
   }
@@ -1343,3 +1365,6 @@ int elfsp_search_log(const ElfSelfPlay* sp, int first, int n, ElfSpSearch* rec, 
 // profiled kernel sources (elf_amd._lib.KERNEL_SOURCES, stamped into profiles/pmc_*.json) does not cover; the next change that
 // re-profiles moves them into a translation unit of their own.
 #include "ownership_host.h"
+// Position setup and undo (elfgo_setup, elfsp_setup, elfsp_undo): device code in setup.cuh, entry points in setup_host.h, here
+// for the same reason.
+#include "setup_host.h"

@@ -155,6 +155,26 @@ class GoEngine:
         assert k == k2
         check(self.L.elfgo_copy(self._h, dp, sp, k, self._stream()))
 
+    def setup(self, stones, ids=None, next_player=None):
+        """Put stones on boards (elfgo_setup): stones [k, N*N] or [N*N] uint8 (0 empty, 1 black, 2 white, index a = x*N + y --
+        what export_board()[0] returns, so `eng.setup(eng.export_board(src)[0], dst)` copies positions without their
+        history), next_player per row (1 / 2; None = Black).  Returns uint8 tensor: 1 set up, 0 refused (a byte above 2, a
+        player other than 1 / 2, a group without a liberty); a refused slot is left as it was."""
+        st = torch.as_tensor(stones, dtype=torch.uint8, device=self.device).reshape(-1, self.n * self.n).contiguous()
+        k = st.shape[0]
+        t, p, k2 = self._ids(ids, k)
+        assert k2 == k
+        npl = None
+        if next_player is not None:
+            npl = torch.as_tensor(next_player, dtype=torch.uint8, device=self.device).reshape(-1).contiguous()
+            if npl.numel() == 1 and k > 1:
+                npl = npl.repeat(k)
+            assert npl.numel() == k
+        ok = torch.empty(k, dtype=torch.uint8, device=self.device)
+        check(self.L.elfgo_setup(self._h, p, C.c_void_p(st.data_ptr()), C.c_void_p(npl.data_ptr()) if npl is not None else None, k,
+                                 C.c_void_p(ok.data_ptr()), self._stream()))
+        return ok
+
     def forward(self, ids, moves):
         """GoState::forward for each (slot, Coord). Returns uint8 tensor: 1 played, 0 refused, 255 M_INVALID."""
         mv = torch.as_tensor(moves, dtype=torch.int32, device=self.device).contiguous()

@@ -4,7 +4,9 @@ Mirrors the reference's console: `GoConsoleGTP` (scripts/elfgames/go/console_lib
 `human_actor` batch group of GoGameSelfPlay::act (src_cpp/elfgames/go/common/game_selfplay.cc:290-330): a human move is forwarded
 on the game board, `genmove` lets the MCTS AI search and play, `clear_board` finishes the game (FR_CLEAR).  Same command set,
 same replies ("= ..." / "? ..."), same coordinate letters (no 'I'): protocol_version, name, version, komi, boardsize,
-clear_board, play, genmove, showboard, final_score, list_commands, quit/exit.
+clear_board, play, genmove, showboard, final_score, list_commands, quit/exit.  On top of the reference's set (whose `u` / `h`
+commands are commented out, console_lib.py:196-204): undo, fixed_handicap, place_free_handicap, set_free_handicap, loadsgf,
+known_command -- what every GTP front-end sends -- over SelfPlay.setup / SelfPlay.undo.
 
     eng = GtpEngine(actor, board_size=19, mcts_rollout_per_thread=1600)     # actor(batch) -> dict(pi=..., V=...)
     eng.loop()                                                               # stdin/stdout, or eng.command("genmove b")
@@ -12,6 +14,7 @@ clear_board, play, genmove, showboard, final_score, list_commands, quit/exit.
 import inspect
 import sys
 
+from ._lib import ElfGoError
 from .engine import M_PASS
 
 M_RESIGN = 1   # base/common.h:44
@@ -36,6 +39,14 @@ def xy2move(x, y):
     if x >= 8:
         x += 1
     return chr(x + 65) + str(y + 1)
+
+
+# the reference's HandicapTable (base/go_state.cc:36-45) as GTP vertices, 19x19 only (it has none for 9x9)
+_H4 = ("D4", "Q16", "D16", "Q4")
+_H6 = _H4 + ("D10", "Q10")
+_H8 = _H6 + ("K16", "K4")
+HANDICAP_VERTICES = {2: ("D4", "Q16"), 3: ("D4", "Q16", "Q4"), 4: _H4, 5: _H4 + ("K10",), 6: _H6, 7: _H6 + ("K10",), 8: _H8,
+                     9: _H8 + ("K10",)}
 
 
 class GtpEngine:
@@ -120,11 +131,110 @@ class GtpEngine:
             return False, "We only support %dx%d board for now" % (self.n, self.n)
         return True, None
 
+    def _untouched(self):
+        """the game has neither moved nor been set up"""
+        info = self._info()
+        return int(info["ply"][0]) == 1 and int(info["hist_len"][0]) == 0
+
     def on_clear_board(self, items):
-        # M_CLEAR of the human actor (game_selfplay.cc:306-311): a game that has not started yet is left alone
-        if int(self._info()["ply"][0]) > 1:
+        # M_CLEAR of the human actor (game_selfplay.cc:306-311): a game that has not started yet is left alone; one that was only
+        # set up (ply still 1, its stones in the history ring) is cleared like one that has moved
+        if not self._untouched():
             self.sp.restart([0])
         return True, None
+
+    # ---- position setup and undo
+    def _place(self, vertices, next_player):
+        """black stones on `vertices`, `next_player` (1 / 2) to move, on a game that has not moved"""
+        import numpy as np
+        st = np.zeros(self.n * self.n, np.uint8)
+        for v in vertices:
+            x, y = move2xy(v)
+            st[x * self.n + y] = 1
+        self.sp.setup(st, [0], next_player)
+
+    def _handicap(self, items):
+        try:
+            k = int(items[1])
+        except (IndexError, ValueError):
+            return False, "invalid handicap"
+        if self.n != 19 or k not in HANDICAP_VERTICES:
+            return False, "invalid handicap"
+        if not self._untouched():
+            return False, "board not empty"
+        self._place(HANDICAP_VERTICES[k], 2)
+        return True, " ".join(HANDICAP_VERTICES[k])
+
+    def on_fixed_handicap(self, items):
+        return self._handicap(items)
+
+    def on_place_free_handicap(self, items):
+        return self._handicap(items)
+
+    def on_set_free_handicap(self, items):
+        try:
+            xy = {move2xy(v) for v in items[1:]}
+        except (IndexError, ValueError):
+            return False, "invalid vertex"
+        if len(xy) < 2 or any(not (0 <= x < self.n and 0 <= y < self.n) for x, y in xy):
+            return False, "invalid handicap"
+        if not self._untouched():
+            return False, "board not empty"
+        self._place([xy2move(x, y) for x, y in sorted(xy)], 2)
+        return True, None
+
+    def on_undo(self, items):
+        try:
+            self.sp.undo(1, [0])
+        except ElfGoError:
+            return False, "cannot undo"
+        return True, None
+
+    def on_loadsgf(self, items):
+        """loadsgf file [move_number]: the file's setup stones, then its moves up to (not including) move_number"""
+        from .train import parse_sgf, sgf_setup
+        if not self._untouched():
+            self.sp.restart([0])
+        try:
+            with open(items[1], "rb") as f:
+                text = f.read()
+            upto = int(items[2]) - 1 if len(items) > 2 else None
+            stones, k = sgf_setup(self.n, text)
+            parsed = parse_sgf(self.n, text)
+            if parsed is None and k == 0:
+                raise ValueError("no game in the file")
+            players, coords = (parsed[0], parsed[1]) if parsed is not None else ([], [])
+            # to move: the colour of the first move; without moves White if there are AB stones, else Black
+            first = int(players[0]) if len(players) else (2 if (stones == 1).any() else 1)
+            if first not in (1, 2):
+                raise ValueError("an entry without a move")
+            if k or first == 2:
+                self.sp.setup(stones, [0], first)
+            nxt, ply = first, 1
+
+            def play(c):
+                # two passes in a row (a bridging pass next to a pass of the file) end the game and restart the board: not loadable
+                nonlocal nxt, ply
+                self.sp.play([c])
+                nxt, ply = 3 - nxt, ply + 1
+                if int(self._info()["ply"][0]) != ply:
+                    raise ValueError("the game ended inside the file")
+            for t, (pl, c) in enumerate(zip(players, coords)):
+                if upto is not None and t >= upto:
+                    break
+                if int(pl) not in (1, 2):
+                    raise ValueError("an entry without a move")
+                if int(pl) != nxt:          # colours that do not alternate are bridged by a pass (sgf_test.cc:78-81)
+                    play(M_PASS)
+                play(int(c))
+        except (ElfGoError, OSError, ValueError):
+            if not self._untouched():
+                self.sp.restart([0])
+            return False, "cannot load file"
+        return True, None
+
+    def on_known_command(self, items):
+        return True, "true" if len(items) > 1 and items[1] in self.commands else "false"
 
     def on_play(self, items):
         ret, msg = self.check_player(items[1][0])
@@ -155,7 +265,7 @@ class GtpEngine:
         return True, "\n" + self.showboard()
 
     def on_final_score(self, items):
-        if int(self._info()["ply"][0]) > 1:
+        if not self._untouched():             # a game that has moved or was set up: this position's score
             score = float(self.boards.evaluate(komi=self.komi, n=1).cpu()[0])     # GoGameSelfPlay::getScore
         else:
             score = float(self.sp.last_score()[0])                                # getLastScore

@@ -318,6 +318,29 @@ class SelfPlay:
         g = np.ascontiguousarray(games, dtype=np.int32)
         check(self.L.elfsp_restart(self._h, g.ctypes.data, g.size, self._stream()))
 
+    def setup(self, stones, games=None, next_player=None):
+        """Set games up between two searches (elfsp_setup): stones [k, N*N] or [N*N] uint8 host rows (0 empty, 1 black, 2 white,
+        index a = x*N + y), games = the k game indices (None = games 0..k-1), next_player per row (1 / 2; None = Black).  Only
+        a game that has not moved yet can be set up.  Raises ElfGoError if a row is refused (that game is left untouched).
+        A game that was set up leaves no Record when it finishes."""
+        if hasattr(stones, "cpu"):
+            stones = stones.cpu().numpy()
+        st = np.ascontiguousarray(stones, dtype=np.uint8).reshape(-1, self.n * self.n)
+        k = st.shape[0]
+        g = np.ascontiguousarray(np.arange(k) if games is None else games, dtype=np.int32).reshape(-1)
+        if g.size != k:
+            raise ValueError("one game per stones row")
+        npl = None
+        if next_player is not None:
+            npl = np.ascontiguousarray(np.broadcast_to(np.asarray(next_player, dtype=np.uint8).reshape(-1), (k,)))
+        check(self.L.elfsp_setup(self._h, g.ctypes.data, k, st.ctypes.data, npl.ctypes.data if npl is not None else None, self._stream()))
+
+    def undo(self, count=1, games=None):
+        """Take back the last `count` moves of the listed games (None = every game) between two searches (elfsp_undo); raises
+        ElfGoError -- and changes nothing -- if a game has played fewer moves since it (re)started."""
+        g = np.ascontiguousarray(np.arange(self.num_games) if games is None else games, dtype=np.int32).reshape(-1)
+        check(self.L.elfsp_undo(self._h, g.ctypes.data, g.size, int(count), self._stream()))
+
     def last_score(self):
         out = np.zeros(self.num_games, np.float32)
         check(self.L.elfsp_last_score(self._h, out.ctypes.data))

@@ -195,6 +195,18 @@ def parse_sgf(board_size, text):
     return pl, mv, dict(size=h.size, komi=h.komi, handi=h.handi, winner=h.winner, win_margin=h.win_margin)
 
 
+def sgf_setup(board_size, text):
+    """The setup stones of an SGF text (elfrec_sgf_setup): the AB / AW points of its header node, which parse_sgf leaves out
+    -> (stones uint8 [N*N], 0 empty / 1 black / 2 white at index a = x*N + y: a row for GoEngine.setup, number of stones)"""
+    L = _lib.lib()
+    raw = text.encode("latin-1") if isinstance(text, str) else text
+    st = np.zeros(int(board_size) ** 2, np.uint8)
+    k = L.elfrec_sgf_setup(int(board_size), raw, st.ctypes.data, None)
+    if k < 0:
+        check(k)
+    return st, int(k)
+
+
 def record_to_sgf(board_size, rec, opt, filename, git_hash=None, git_staged=None):
     """GoStateExt::dumpSgf (go_state_ext.cc:26-82) for a finished game: rec = Record JSON text / dict, opt = the SpOptions the game
     was played under (komi, policy-only flags) -> SGF text (result, player names, komi, every move with its predicted value)"""

@@ -91,6 +91,20 @@ int elfgo_export_board(ElfGoEngine* e, const int32_t* ids, int n, uint8_t* colou
 int elfgo_playout(ElfGoEngine* e, const int32_t* ids, const uint64_t* seeds, int n, int max_steps,
                   uint32_t* out, void* stream);
 
+/* Put stones on boards: slot ids[i] <- the position whose stones are stones[i][a] (0 empty, 1 black, 2 white; a = x*N + y,
+ * the order of elfgo_export_board's colour rows, row stride N*N bytes) with next_player[i] (1 / 2; NULL = Black) to move.
+ * ok[i] = 1 done, 0 refused (a byte > 2, a player other than 1 / 2, or a group without a liberty): a refused slot is left
+ * exactly as it was.  ids NULL = slots [0, n); a slot named twice is the caller's error.  All pointers are device pointers.
+ * The slot afterwards is what elfgo_reset leaves (clearBoard, board.cc:79-107: ply 1, last moves M_INVALID, no ko, no captures,
+ * no super-ko records) plus the group tables and the Zobrist hash of the stones and the side to move -- for a legal arrangement
+ * of black stones PlaceHandicap's board (board.cc:109-126), generalised to both colours -- and the position is the ONE entry of
+ * the history ring (hist_len 1), so that elfgo_extract_agz shows the stones in planes 0 / 1 as it does for any position reached
+ * by play.  (The reference's GoState::applyHandicap leaves _history empty, its net would see an empty board under the handicap
+ * stones: a defect nobody exercises there -- nothing calls applyHandicap -- and not behaviour that is reproduced here.)
+ * SGF carries no ko point, so none can be set up. */
+int elfgo_setup(ElfGoEngine* e, const int32_t* ids, const uint8_t* stones, const uint8_t* next_player, int n, uint8_t* ok,
+                void* stream);
+
 /* Tromp-Taylor area of each point of a position (simple_flood_fill per colour + the black && !white / white && !black rule of
  * simple_tt_scoring, go_state.h:32-93): out[i][a] = 0 neutral, 1 black, 2 white, a = x*N + y (the action order of
  * elfgo_legal_mask under D4 code 0); row stride N*N bytes.  Always the flood fill of the stones: the super-ko +-1 rule of
@@ -422,6 +436,25 @@ int elfsp_play(ElfSelfPlay* sp, const int32_t* moves_host, void* stream);
  * each search's move is replaced by the next listed move (:392-405); the search that finds the list exhausted finishes the game
  * (FR_MAX_STEP).  An illegal listed move returns ELFGO_E_MCTS_BASE - ELFMCTS_E_FORWARD ("Preload sgf: move not valid!"). */
 int elfsp_preload(ElfSelfPlay* sp, const uint16_t* moves_host, int n, int move_to, void* stream);
+/* Between two searches: set the listed games up (stones_host [n][N*N], next_player_host [n] or NULL, as elfgo_setup; a game may
+ * be listed once).  A game can be set up only before its first move (PlaceHandicap's rule, board.cc:110-112): ELFGO_E_BADARG
+ * otherwise, or while a search is open; ELFGO_E_MCTS_BASE - ELFMCTS_E_FORWARD if a row is refused (that game is untouched, the
+ * others are set up).  The trees of those games are cleared in both AIs.
+ * A game that was set up finishes like any other (it is scored, elfsp_last_score / elfsp_take_finished report it, its seq
+ * advances) but leaves NO Record for elfsp_pop_record: a Record has no field for set-up stones and the trainer replays it from
+ * the empty board (GoStateExtOffline::fromRecord), so such a record could not be replayed. */
+int elfsp_setup(ElfSelfPlay* sp, const int32_t* games_host, int n, const uint8_t* stones_host,
+                const uint8_t* next_player_host, void* stream);
+/* Between two searches: take back the last `count` moves of each listed game (moves of searches and of elfsp_play alike).
+ * ELFGO_E_BADARG -- and nothing changes -- if count <= 0, if a game has played fewer than `count` moves since it
+ * (re)started (a finished game is gone: it restarted), while a search is open, or in a context that follows a preloaded move
+ * list (elfsp_preload).  The game is rebuilt on its slot from its set-up stones (or the empty board) and its first L - count
+ * moves: board, history ring, super-ko records and Bloom words, ply and the pending Record arrays (moves, values, policies)
+ * are those of the game after these moves; the trees of those games are cleared.  The game's random generators are NOT
+ * rewound, and neither are what was drawn or derived from them and from the searches taken back: the never-resign draw of the
+ * game and the last predicted value stay as they are.  Any other error (a device error while the boards are rebuilt) leaves
+ * the listed games restarted from the empty board. */
+int elfsp_undo(ElfSelfPlay* sp, const int32_t* games_host, int n, int count, void* stream);
 /* finish_game(reason) + restart (game_selfplay.cc:121-149) for the listed games between two searches: the game is scored
  * (FR_RESIGN: the side to move loses; every other reason: GoState::evaluate(komi), go_state_ext.h:76-103), leaves its record and
  * starts over from the empty board.  reason = FinishReason of common/go_state_ext.h:24-32. */
@@ -517,6 +550,13 @@ typedef struct ElfSgfHeader {
   float komi, win_margin;
 } ElfSgfHeader;
 int elfrec_sgf_parse(int board_size, const char* text, int32_t* players, uint16_t* coords, int cap, ElfSgfHeader* header);
+/* The setup stones of an SGF text, which elfrec_sgf_parse leaves out: the AB[..][..] / AW[..][..] points of the header node as
+ * a stones row for elfgo_setup (stones[a] = 0 / 1 / 2, a = x*N + y; a later property overwrites an earlier one on the same
+ * point).  Same reading rules as elfrec_sgf_parse: a backslash hides the next character, points off the board are ignored.
+ * A value that is not exactly one point -- a compressed list such as AB[aa:cc] (FF[4] rectangles) included -- is ignored:
+ * rectangles are not expanded.
+ * Returns the number of stones on the row (0: the text sets nothing up, or has no header node); `header` as elfrec_sgf_parse. */
+int elfrec_sgf_setup(int board_size, const char* text, uint8_t* stones, ElfSgfHeader* header);
 /* GoStateExt::dumpSgf (go_state_ext.cc:26-82): the SGF text the reference's finish_game writes for a finished game when
  * GameOptions.dump_record_prefix is set (file <prefix>_<game>_<seq>_<B|W>.sgf, go_state_ext.h:48-56): RE[] from the final value
  * ("B+R" / "W+R" for +-1, else the margin), PB / PW ("MCTS", "(policy only)" appended), KM, every move with "C[<n>: PredV: <v>]".
