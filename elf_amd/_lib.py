@@ -44,6 +44,7 @@ SIGNATURES = {
     "elfgo_playout": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "elfgo_setup": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "elfgo_area_map": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "elfgo_ladder_map": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "elfgo_own_create": (_i, [_vp, _i, C.POINTER(_vp)]),
     "elfgo_own_destroy": (_i, [_vp]),
     "elfgo_own_scratch_bytes": (_sz, [_vp]),

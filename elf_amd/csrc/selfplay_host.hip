@@ -1368,3 +1368,5 @@ int elfsp_search_log(const ElfSelfPlay* sp, int first, int n, ElfSpSearch* rec, 
 // Position setup and undo (elfgo_setup, elfsp_setup, elfsp_undo): device code in setup.cuh, entry points in setup_host.h, here
 // for the same reason.
 #include "setup_host.h"
+// Ladder reading (elfgo_ladder_map): device code in ladder.cuh, entry point in ladder_host.h, here for the same reason.
+#include "ladder_host.h"

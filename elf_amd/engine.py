@@ -262,6 +262,18 @@ class GoEngine:
         check(self.L.elfgo_area_map(self._h, p, k, C.c_void_p(out.data_ptr()), self._stream()))
         return out
 
+    def ladder_map(self, ids=None, n=None, with_calls=False):
+        """Ladder reading for the side to move (checkLadder, base/board.cc:476-524) -> int16 tensor [k, N*N], index a = x*N + y:
+        d > 0 where the mover would extend a group out of atari and still be captured in a ladder after d plies, else 0.
+        with_calls=True returns (depth, calls): calls is the reference's num_call of each point's search, 0 where none ran,
+        -1 where a bound of the device search cut it (that point's depth is 0)."""
+        t, p, k = self._ids(ids, n)
+        depth = torch.empty((k, self.n * self.n), dtype=torch.int16, device=self.device)
+        calls = torch.empty((k, self.n * self.n), dtype=torch.int16, device=self.device) if with_calls else None
+        check(self.L.elfgo_ladder_map(self._h, p, k, C.c_void_p(depth.data_ptr()), C.c_void_p(calls.data_ptr()) if with_calls else None,
+                                      self._stream()))
+        return (depth, calls) if with_calls else depth
+
     def ownership(self, seeds, ids=None, playouts=256, komi=7.5, max_steps=1 << 20, max_lanes=0):
         """Monte-Carlo ownership: `playouts` config-2 playouts from a private copy of each listed slot (the slots themselves are
         only read), playout k of row i with seed seeds[i] + k * 0x9E3779B97F4A7C15 (mod 2^64).  Returns a dict:

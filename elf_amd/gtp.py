@@ -6,7 +6,8 @@ on the game board, `genmove` lets the MCTS AI search and play, `clear_board` fin
 same replies ("= ..." / "? ..."), same coordinate letters (no 'I'): protocol_version, name, version, komi, boardsize,
 clear_board, play, genmove, showboard, final_score, list_commands, quit/exit.  On top of the reference's set (whose `u` / `h`
 commands are commented out, console_lib.py:196-204): undo, fixed_handicap, place_free_handicap, set_free_handicap, loadsgf,
-known_command -- what every GTP front-end sends -- over SelfPlay.setup / SelfPlay.undo.
+known_command -- what every GTP front-end sends -- over SelfPlay.setup / SelfPlay.undo; final_status_list and the private
+elf-ownership, elf-score_estimate and elf-ladders over the per-point answers of the board engine.
 
     eng = GtpEngine(actor, board_size=19, mcts_rollout_per_thread=1600)     # actor(batch) -> dict(pi=..., V=...)
     eng.loop()                                                               # stdin/stdout, or eng.command("genmove b")
@@ -66,6 +67,7 @@ class GtpEngine:
         # private extensions carry the "elf-" prefix (GTP 2, section 2.13); a method name cannot hold the hyphen
         self.commands["elf-ownership"] = self.commands.pop("elf_ownership")
         self.commands["elf-score_estimate"] = self.commands.pop("elf_score_estimate")
+        self.commands["elf-ladders"] = self.commands.pop("elf_ladders")
 
     def close(self):
         self.boards.close()      # the ownership scratch goes before the engine it was made over
@@ -299,6 +301,12 @@ class GtpEngine:
         col, cb, cw = self._status_counts()
         score = float(int((cb > cw).sum()) - int((cw > cb).sum())) - self.komi
         return True, ("B+%.1f" % score) if score > 0 else ("W+%.1f" % -score)
+
+    def on_elf_ladders(self, items):
+        """The points where the side to move would extend a group out of atari and still be captured in a ladder
+        (GoEngine.ladder_map on game 0's current position), as VERTEX:depth pairs in board order (a = x*N + y); empty if none."""
+        depth = self.boards.ladder_map(ids=[0]).cpu().numpy()[0]
+        return True, " ".join("%s:%d" % (xy2move(a // self.n, a % self.n), int(depth[a])) for a in range(self.n * self.n) if depth[a])
 
     def on_list_commands(self, items):
         return True, "\n".join(self.commands.keys())

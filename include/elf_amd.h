@@ -111,6 +111,17 @@ int elfgo_setup(ElfGoEngine* e, const int32_t* ids, const uint8_t* stones, const
  * GoState::evaluate plays no part. */
 int elfgo_area_map(ElfGoEngine* e, const int32_t* ids, int n, uint8_t* out, void* stream);
 
+/* Ladder reading for the side to move (checkLadder / checkLadderUseSearch, base/board.cc:299-439, :476-524):
+ *     depth[i][a] = checkLadder(board, GroupId4 of a, next_player) where point a = x*N + y is legal by TryPlay2, else 0
+ * A depth d > 0 means: the mover extends a group out of atari at a and is still captured in a ladder after d plies (the move at
+ * a included).  calls (may be NULL) receives the reference's num_call after the search of each point: 0 where the point is
+ * illegal or checkLadder's own test (two empty neighbours, one enemy group with >= 3 liberties, one own group in atari) rejects
+ * it without a search, -1 where a bound of the device search cut it (a line of more than 1024 moves, or more than 32000 plays
+ * for one point, backtracking replays included); such a point's depth is 0.  A row whose slot id lies outside the pool gets
+ * depth 0 and calls -1.  int16 [n][N*N] each, device pointers; ids NULL = slots [0, n).  The slots are only read: the search
+ * plays on a private copy with the reference's Board-level rules (no super-ko, termination or move-limit test). */
+int elfgo_ladder_map(ElfGoEngine* e, const int32_t* ids, int n, int16_t* depth, int16_t* calls, void* stream);
+
 /* Monte-Carlo ownership from device playouts.  The handle owns the scratch of the playout copies (one super-ko record area
  * per wave in flight) and the launch geometry; several handles may share an engine.  max_lanes = waves in flight
  * (<= 0: a default from the device's CU count); destroy the handle before its engine. */
