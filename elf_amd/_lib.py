@@ -148,6 +148,7 @@ SIGNATURES = {
     "elfrec_quantise_policy": (_i, [_i, _vp, _vp, _i, _vp]),
     "elfnet_bias_act_f16": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
     "elfnet_bias_act_bf16": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
+    "elfnet_conv3x3_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp]),
     "elfgo_set_device": (_i, [_i]),
     "elfgo_get_device": (_i, [C.POINTER(_i)]),
     "elfgo_mem_info": (_i, [_i, C.POINTER(_sz), C.POINTER(_sz)]),

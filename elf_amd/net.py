@@ -156,16 +156,21 @@ def make_net(board_size=19, num_block=20, dim=256, device="cuda", dtype=torch.fl
 
 
 class FusedInferenceNet:
-    """Inference-only execution of a BN-folded fp16 channels_last PolicyValueNet with ONE epilogue pass per convolution.
+    """Inference-only execution of a BN-folded fp16 channels_last PolicyValueNet with bias, skip and ReLU inside the convolutions.
 
-    The convolutions stay PyTorch-ROCm ops (MIOpen / CK implicit GEMM); what changes is what runs between them.  Eager PyTorch
-    issues conv -> bias add -> ReLU (-> residual add -> ReLU) as separate elementwise kernels, i.e. five HBM round trips of the
-    [B,256,N,N] activation per residual block; here each conv is bias-free and is followed by one in-place pass
-    (`elfnet_bias_act_f16`, elf_amd/csrc/net_epilogue.hip): relu(x + b) after the lower conv, relu(x + b + skip) after the upper.
+    Eager PyTorch issues conv -> bias add -> ReLU (-> residual add -> ReLU) as separate elementwise kernels, i.e. five HBM round
+    trips of the [B,256,N,N] activation per residual block.  Here a 3x3 trunk convolution of an fp16 net is ONE kernel,
+    `elfnet_conv3x3_f16` (elf_amd/csrc/net_conv.hip): Composable Kernel's implicit-GEMM main loop with the tile configuration MIOpen's
+    tuned database picks for this shape, and our functor in its epilogue: relu(conv + b) for the lower conv of a block,
+    relu(conv + b + skip) for the upper.  Nothing passes over the activation a second time.
+    Every other convolution (the 18-plane input conv, bf16 nets, a weight that is not channels_last) stays a bias-free PyTorch-ROCm
+    op (MIOpen) followed by one in-place pass, `elfnet_bias_act_f16` / `_bf16` (elf_amd/csrc/net_epilogue.hip).
     (PyTorch's own fused MIOpen ops, miopen_convolution_relu / miopen_convolution_add_relu, were measured and rejected: for
     fp16 channels_last MIOpen's fusion plan falls back to naive kernels, > 10x slower.)
-    Same function as PolicyValueNet.forward (src_py/elfgames/go/df_model3.py:62-110,224-313) up to fp16 rounding: the fused
-    epilogue rounds once where the eager sequence rounds after every kernel."""
+    Same function as PolicyValueNet.forward (src_py/elfgames/go/df_model3.py:62-110,224-313) up to fp16 rounding: the conv result
+    is rounded to fp16 once and the epilogue once, where the eager sequence rounds after every kernel."""
+
+    conv_algo = 0   # elfnet_conv3x3_f16's algo: 0 = MIOpen's tile configuration (DESIGN.md section 3 has the probe that chose it)
 
     def __init__(self, net):
         import ctypes as C
@@ -192,10 +197,33 @@ class FusedInferenceNet:
                                              C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
         return x
 
+    def _fusable(self, x, c):
+        """The convolutions elfnet_conv3x3_f16 takes: fp16, 3x3, stride 1, pad 1, one group, C and K multiples of 8, and a weight that
+        lies in memory as [K,3,3,C] (its strides are checked: a 4-d tensor can claim channels_last without them)."""
+        w = c.weight
+        k, cin = w.shape[0], w.shape[1]
+        return (self.dtype == torch.float16 and tuple(w.shape[2:]) == (3, 3) and tuple(c.stride) == (1, 1)
+                and tuple(c.padding) == (1, 1) and tuple(c.dilation) == (1, 1) and c.groups == 1 and c.bias is not None
+                and cin % 8 == 0 and k % 8 == 0 and x.shape[1] == cin
+                and tuple(w.stride()) == (9 * cin, 1, 3 * cin, cin))
+
     def _conv(self, x, c, res=None):
-        y = torch.nn.functional.conv2d(x, c.weight, None, c.stride, c.padding)
-        assert y.is_contiguous(memory_format=torch.channels_last)
-        return self._ep(y, c.bias, res)
+        if not self._fusable(x, c):
+            y = torch.nn.functional.conv2d(x, c.weight, None, c.stride, c.padding)
+            assert y.is_contiguous(memory_format=torch.channels_last)
+            return self._ep(y, c.bias, res)
+        assert x.is_contiguous(memory_format=torch.channels_last)
+        C = self.C
+        n, cin, h, w = x.shape
+        k = c.weight.shape[0]
+        # a fresh buffer per conv (inside a captured graph it comes from the graph's own pool); x, and res until the upper conv
+        # has run, stay alive in the caller
+        y = torch.empty((n, k, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        self.check(self.L.elfnet_conv3x3_f16(C.c_void_p(x.data_ptr()), C.c_void_p(c.weight.data_ptr()), C.c_void_p(c.bias.data_ptr()),
+                                             C.c_void_p(res.data_ptr()) if res is not None else None, C.c_void_p(y.data_ptr()),
+                                             n, h, w, cin, k, 1, self.conv_algo,
+                                             C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+        return y
 
     @torch.no_grad()
     def __call__(self, batch):

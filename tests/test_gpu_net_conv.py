@@ -1,0 +1,220 @@
+"""GPU: the trunk convolution with bias, skip and ReLU in its epilogue (elfnet_conv3x3_f16, elf_amd/csrc/net_conv.hip) against an
+fp32 evaluation of the same fp16 inputs, its argument checks, and FusedInferenceNet on top of it (eager and captured)."""
+import ctypes as C
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+CH = 256
+ROWS = 2048
+
+
+@pytest.fixture(scope="module")
+def elf(built):
+    import elf_amd
+    return elf_amd
+
+
+_cases = {}
+
+
+def _conv_fp32(x, w):
+    """conv2d(x, w, padding=1) in fp32 for NHWC x [rows,n,n,C] and w [K,3,3,C], written out as its nine taps: one fp32 GEMM per tap
+    over the zero-padded input, summed in fp32.  (F.conv2d itself would either search MIOpen's solvers for an fp32 shape nothing
+    else uses or, with MIOpen off, unfold row by row: 45 s for 2048 rows.  _case checks this against it on two rows.)"""
+    import torch
+    rows, n = x.shape[0], x.shape[1]
+    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))
+    out = torch.zeros((rows, n, n, w.shape[0]), device=x.device, dtype=torch.float32)
+    for ky in range(3):
+        for kx in range(3):
+            out += xp[:, ky:ky + n, kx:kx + n, :] @ w[:, ky, kx, :].t()
+    return out
+
+
+def _case(n):
+    """One seeded problem per board size, computed once and only read afterwards: fp16 inputs that are dense up to and including
+    the border cells (a wrong halo is an O(1) error), and on the same inputs, in fp32 by torch:
+        pre = conv2d(x, w, padding=1) + bias          (the skip is added per test: + res)
+        S0  = conv2d(|x|, |w|) + |bias|               (+ |res|)
+    The smaller row counts are the first rows of the 2048: a convolution does not mix rows."""
+    import torch
+    if n not in _cases:
+        g = torch.Generator(device="cuda").manual_seed(1000 + n)
+        x = torch.randn((ROWS, n, n, CH), device="cuda", generator=g).half()                    # NHWC
+        w = (torch.randn((CH, 3, 3, CH), device="cuda", generator=g) * (9 * CH) ** -0.5).half()  # [K,3,3,C]: conv output is O(1)
+        b = torch.randn((CH,), device="cuda", generator=g).half()
+        r = torch.randn((ROWS, n, n, CH), device="cuda", generator=g).half()
+        with torch.no_grad():
+            pre = _conv_fp32(x.float(), w.float())
+            s0 = _conv_fp32(x.float().abs(), w.float().abs())
+            with torch.backends.cudnn.flags(enabled=False):
+                lit = torch.nn.functional.conv2d(x[:2].float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), padding=1)
+        # the nine-tap form IS conv2d: against torch's own on two rows, to fp32 accumulation error (2^-24 per product, S0 their sum)
+        assert bool(((lit.permute(0, 2, 3, 1) - pre[:2]).abs() <= 2304 * 2.0 ** -24 * s0[:2]).all())
+        pre += b.float()
+        s0 += b.float().abs()
+        _cases[n] = dict(x=x, w=w, b=b, r=r, pre=pre, s0=s0)
+    return _cases[n]
+
+
+def _run(L, x, w, b, r, y, rows, n, relu, algo, c=CH, k=CH):
+    import torch
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    return L.elfnet_conv3x3_f16(p(x), p(w), p(b), p(r), p(y), rows, n, n, c, k, int(relu), algo,
+                                C.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+
+@pytest.mark.parametrize("algo", [0, 1])
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("use_res", [False, True])
+@pytest.mark.parametrize("n", [19, 9])
+@pytest.mark.parametrize("rows", [1, 48, ROWS])
+def test_conv3x3_against_fp32(elf, rows, n, use_res, relu, algo):
+    """|y - ref| <= 2^-10 |ref| + 2304 * 2^-24 * S per element, S = conv2d(|x|, |w|) + |bias| + |res|.  Derived, not measured: the
+    first term is the two fp16 roundings of the kernel (the first lands on the value before bias and skip, so where those cancel
+    it the bound rests on the slack of the second term); the second term is the worst-case fp32 accumulation error over the
+    9 * 256 products of one output."""
+    import torch
+    d = _case(n)
+    ref, s = d["pre"][:rows], d["s0"][:rows]
+    if use_res:
+        ref, s = ref + d["r"][:rows].float(), s + d["r"][:rows].float().abs()
+    if relu:
+        ref = torch.relu(ref)
+    y = torch.full((rows, n, n, CH), float("nan"), device="cuda", dtype=torch.float16)
+    rc = _run(elf.lib(), d["x"], d["w"], d["b"], d["r"] if use_res else None, y, rows, n, relu, algo)
+    assert rc == 0
+    torch.cuda.synchronize()
+    err = (y.float() - ref).abs()
+    bound = 2.0 ** -10 * ref.abs() + 2304 * 2.0 ** -24 * s
+    worst = (err / bound).max().item()   # nan (an element the kernel did not write) fails the comparison below
+    print("rows %d n %d res %d relu %d algo %d: max err %.3e, max err/bound %.3f" % (rows, n, use_res, relu, algo, err.max().item(), worst))
+    assert bool((err <= bound).all()), worst
+
+
+def test_conv3x3_argument_errors(elf):
+    """misaligned pointers, c % 8 != 0, a null y and y == x are refused with a status, and nothing is launched: y keeps its bytes"""
+    import torch
+    L = elf.lib()
+    d = _case(9)
+    x, w, b, r = d["x"], d["w"], d["b"], d["r"]
+    y = torch.full((4, 9, 9, CH), 7.0, device="cuda", dtype=torch.float16)
+    off = lambda t: C.c_void_p(t.data_ptr() + 2)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert L.elfnet_conv3x3_f16(off(x), p(w), p(b), None, p(y), 4, 9, 9, CH, CH, 1, 0, st) < 0
+    assert L.elfnet_conv3x3_f16(p(x), p(w), off(b), None, p(y), 4, 9, 9, CH, CH, 1, 0, st) < 0
+    assert L.elfnet_conv3x3_f16(p(x), p(w), p(b), off(r), p(y), 4, 9, 9, CH, CH, 1, 0, st) < 0
+    assert L.elfnet_conv3x3_f16(p(x), p(w), p(b), None, off(y), 4, 9, 9, CH, CH, 1, 0, st) < 0
+    assert L.elfnet_conv3x3_f16(p(x), p(w), p(b), None, p(y), 4, 9, 9, 12, CH, 1, 0, st) < 0      # c % 8
+    assert L.elfnet_conv3x3_f16(p(x), p(w), p(b), None, p(y), 4, 9, 9, CH, 12, 1, 0, st) < 0      # k % 8
+    assert L.elfnet_conv3x3_f16(p(x), p(w), p(b), None, None, 4, 9, 9, CH, CH, 1, 0, st) < 0      # null y
+    assert L.elfnet_conv3x3_f16(p(x), p(w), p(b), None, p(x), 4, 9, 9, CH, CH, 1, 0, st) < 0      # y == x
+    assert L.elfnet_conv3x3_f16(p(x), p(w), p(b), p(y), p(y), 4, 9, 9, CH, CH, 1, 0, st) < 0      # y == res
+    assert L.elfnet_conv3x3_f16(p(x), p(w), p(b), None, p(y), 4, 9, 9, CH, CH, 1, 2, st) < 0      # unknown algo
+    assert L.elfnet_conv3x3_f16(p(x), p(w), p(b), None, p(y), 0, 9, 9, CH, CH, 1, 0, st) == 0     # no rows: nothing to do
+    torch.cuda.synchronize()
+    assert bool((y == 7.0).all())
+
+
+def test_conv3x3_against_the_two_kernel_path(elf):
+    """At the benchmark's shape (2048 x 19 x 19 x 256, with skip): the count of elements that differ from F.conv2d followed by
+    elfnet_bias_act_f16 is printed, not asserted -- with algo 0 it is 0 where MIOpen picks the tile configuration its tuned
+    database names for this shape, and MIOpen may pick another solver under another database.  What holds anywhere: both paths
+    lie within the bound of test_conv3x3_against_fp32 around the same fp32 reference, so they differ by at most twice that."""
+    import torch
+    L = elf.lib()
+    d = _case(19)
+    x, w, b, r = d["x"], d["w"], d["b"], d["r"]
+    with torch.no_grad():
+        old = torch.nn.functional.conv2d(x.permute(0, 3, 1, 2), w.permute(0, 3, 1, 2), None, 1, 1)
+    assert old.is_contiguous(memory_format=torch.channels_last)
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert L.elfnet_bias_act_f16(C.c_void_p(old.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(r.data_ptr()), ROWS * 361, CH, 1, st) == 0
+    old = old.permute(0, 2, 3, 1)
+    ref = torch.relu(d["pre"] + r.float())
+    bound = 2.0 ** -10 * ref.abs() + 2304 * 2.0 ** -24 * (d["s0"] + r.float().abs())
+    for algo in (0, 1):
+        y = torch.empty((ROWS, 19, 19, CH), device="cuda", dtype=torch.float16)
+        assert _run(L, x, w, b, r, y, ROWS, 19, 1, algo) == 0
+        torch.cuda.synchronize()
+        diff = (y.float() - old.float()).abs()
+        print("algo %d: %d of %d elements differ from conv2d + elfnet_bias_act_f16, max |diff| %.3e"
+              % (algo, int((y != old).sum().item()), y.numel(), diff.max().item()))
+        assert bool((diff <= 2 * bound).all())
+
+
+def _nets():
+    import torch
+    from elf_amd.net import make_net
+    n, blocks, bs = 19, 2, 48
+    net16 = make_net(n, blocks, CH, "cuda", torch.float16, channels_last=True, seed=3, fold_bn=True)
+    net32 = make_net(n, blocks, CH, "cuda", torch.float32, channels_last=False, seed=3, fold_bn=True)
+    s = (torch.rand((bs, 18, n, n), device="cuda", generator=torch.Generator(device="cuda").manual_seed(5)) < 0.3).float()
+    return net16, net32, s
+
+
+def test_fused_net_on_the_conv_kernel_matches_eager_net(elf):
+    """A 2-block, 256-channel fp16 net -- every trunk conv goes through elfnet_conv3x3_f16 -- under the criterion of
+    test_fused_inference_matches_eager_net: at least as close to the fp32 net as eager fp16 + 1e-3, and within 2e-3 on pi and V."""
+    import torch
+    from elf_amd.net import FusedInferenceNet
+    net16, net32, s = _nets()
+    with torch.no_grad():
+        ref = net32({"s": s})
+        eager = net16({"s": s})
+    f = FusedInferenceNet(net16)
+    assert all(f._fusable(torch.empty((1, CH, 19, 19)), c) for blk in f.blocks for c in blk) and not f._fusable(s, f.first)
+    fused = f({"s": s})
+    for k in ("pi", "V"):
+        err_f = (fused[k] - ref[k]).abs().max().item()
+        err_e = (eager[k] - ref[k]).abs().max().item()
+        print(k, "fused err %.3e eager err %.3e" % (err_f, err_e))
+        assert err_f <= err_e + 1e-3 and err_f < 2e-3, (k, err_f, err_e)
+    assert torch.allclose(fused["pi"].sum(1), torch.ones(s.shape[0], device="cuda"), atol=1e-4)
+
+
+def test_fused_net_captured_equals_uncaptured(elf):
+    """The same net inside GraphedNet returns the pi / V bits of the uncaptured call, at 32 rows; and the trunk alone (the
+    input conv and the four elfnet_conv3x3_f16 calls), captured at 16 rows into a graph of its own, returns the bits of its uncaptured
+    call.  Why two sizes: the net's 1x1 head convolutions are MIOpen's, and at 16 rows MIOpen settles on another solver for
+    pi_final_conv inside a capture than outside one (measured: trunk output identical, 1534 of its 11 552 outputs differ, with and
+    without the fused convolutions) -- at 32 rows it does not, so that is where the whole net is compared."""
+    import torch
+    from elf_amd.net import FusedInferenceNet, GraphedNet
+    net16, _, s = _nets()
+    f = FusedInferenceNet(net16)
+    s16 = s.half().contiguous(memory_format=torch.channels_last)
+    x = s16[:32]
+    g = GraphedNet(f, x)
+    out = {k: v.clone() for k, v in g().items()}
+    plain = f({"s": x})
+    again = g()
+    torch.cuda.synchronize()
+    for k in ("pi", "V"):
+        print(k, "max |captured - uncaptured| %.3e" % (out[k] - plain[k]).abs().max().item())
+        assert torch.equal(out[k], plain[k]), k
+        assert torch.equal(again[k], plain[k]), k
+
+    def trunk(t):
+        h = f._conv(t, f.first)
+        for lo, up in f.blocks:
+            h = f._conv(f._conv(h, lo), up, res=h)
+        return h
+    x = s16[32:]
+    with torch.no_grad():
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            trunk(x)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            hg = trunk(x)
+        gr.replay()
+        hp = trunk(x)
+    torch.cuda.synchronize()
+    assert torch.equal(hg, hp)

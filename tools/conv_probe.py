@@ -1,21 +1,98 @@
-"""GPU-box helper: which layout / dtype / batch gives PyTorch-ROCm's 3x3 256->256 convolution (the net's hot op) its best rate."""
-import sys, time, torch
-torch.backends.cudnn.benchmark = True
-def timeit(f, it=10):
-    for _ in range(3): f()
-    torch.cuda.synchronize(); t = time.time()
-    for _ in range(it): f()
-    torch.cuda.synchronize(); return (time.time() - t) / it
-w0 = torch.randn(256, 256, 3, 3, device="cuda")
-for bs in (2048, 4096):
-    for dtype in (torch.float16, torch.bfloat16):
-        for cl in (True, False):
-            x = torch.randn(bs, 256, 19, 19, device="cuda").to(dtype)
-            w = w0.to(dtype)
-            if cl:
-                x = x.contiguous(memory_format=torch.channels_last); w = w.contiguous(memory_format=torch.channels_last)
-            t0 = time.time()
-            with torch.no_grad():
-                dt = timeit(lambda: torch.nn.functional.conv2d(x, w, None, 1, 1))
-            print("bs=%d %s %s: %.3f ms  %.0f TFLOP/s  (find+time %.1f s)" % (bs, str(dtype).split(".")[-1], "NHWC" if cl else "NCHW", dt * 1e3,
-                  2 * 256 * 256 * 9 * 361 * bs / dt / 1e12, time.time() - t0), flush=True)
+"""Times ONE trunk convolution of the benchmark net (rows = 2048, 19 x 19, 256 -> 256, fp16 NHWC), with and without the skip:
+    fused0 / fused1   elfnet_conv3x3_f16 with algo 0 / 1 (bias, skip and ReLU in the convolution's epilogue)
+    pair              what ran before: F.conv2d (MIOpen) followed by elfnet_bias_act_f16
+HIP events around `--launches` back-to-back launches after a warm-up, `--repeats` times; mean / min / max of the repeats in µs per
+convolution.  One process; run it under a time limit:
+    timeout -k 10 300 python tools/conv_probe.py [--algos 0,1] [--out profiles/conv_fused_probe.json]
+A variant the library refuses (a non-zero status, e.g. CK's IsSupportedArgument saying no on this device) is recorded with its
+status and not timed.  FusedInferenceNet.conv_algo changes to 1 only if algo 1's mean is below algo 0's by more than the spread
+(max - min over the repeats) of either."""
+import argparse
+import ctypes as C
+import json
+import os
+import shutil
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=2048)
+    ap.add_argument("--board-size", type=int, default=19)
+    ap.add_argument("--dim", type=int, default=256)
+    ap.add_argument("--launches", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--algos", default="0,1")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "conv_fused_probe.json"))
+    a = ap.parse_args()
+    # the pair runs the convolution MIOpen's tuned database names for this shape, as the benchmark does: the committed entries go
+    # into the user database directory where no file of that name is there yet (bench.py's seed_miopen_db)
+    src = os.path.join(ROOT, "elf_amd", "data", "miopen_db")
+    dst = os.environ.get("MIOPEN_USER_DB_PATH") or os.path.join(os.path.expanduser("~"), ".config", "miopen")
+    os.makedirs(dst, exist_ok=True)
+    for name in sorted(os.listdir(src)):
+        if not os.path.exists(os.path.join(dst, name)):
+            shutil.copyfile(os.path.join(src, name), os.path.join(dst, name))
+    import torch
+    import elf_amd
+    L = elf_amd.lib()
+    rows, n, ch = a.rows, a.board_size, a.dim
+    g = torch.Generator(device="cuda").manual_seed(7)
+    x = torch.randn((rows, n, n, ch), device="cuda", generator=g).half()
+    w = (torch.randn((ch, 3, 3, ch), device="cuda", generator=g) * (9 * ch) ** -0.5).half()
+    b = torch.randn((ch,), device="cuda", generator=g).half()
+    r = torch.randn((rows, n, n, ch), device="cuda", generator=g).half()
+    y = torch.empty_like(x)
+    xv, wv = x.permute(0, 3, 1, 2), w.permute(0, 3, 1, 2)
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+
+    def fused(algo, res):
+        return lambda: L.elfnet_conv3x3_f16(p(x), p(w), p(b), p(res), p(y), rows, n, n, ch, ch, 1, algo, st)
+
+    def pair(res):
+        def f():
+            o = torch.nn.functional.conv2d(xv, wv, None, 1, 1)
+            return L.elfnet_bias_act_f16(p(o), p(b), p(res), rows * n * n, ch, 1, st)
+        return f
+
+    def timed(fn):
+        rc = fn()
+        torch.cuda.synchronize()
+        if rc != 0:
+            return dict(status=int(rc))
+        for _ in range(a.warmup):
+            fn()
+        us = []
+        for _ in range(a.repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.launches):
+                fn()
+            e1.record()
+            e1.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3 / a.launches)
+        return dict(status=0, us=[round(u, 2) for u in us], mean_us=round(sum(us) / len(us), 2), min_us=round(min(us), 2),
+                    max_us=round(max(us), 2))
+
+    res = dict(shape=dict(rows=rows, board_size=n, channels=ch), launches=a.launches, warmup=a.warmup, repeats=a.repeats,
+               device=torch.cuda.get_device_name(0), method="HIP events around back-to-back launches, µs per convolution")
+    with torch.no_grad():
+        for skip, rr in (("noskip", None), ("skip", r)):
+            res["pair_" + skip] = timed(pair(rr))
+            for algo in [int(v) for v in a.algos.split(",") if v != ""]:
+                res["fused%d_%s" % (algo, skip)] = timed(fused(algo, rr))
+                print(skip, "algo", algo, res["fused%d_%s" % (algo, skip)], flush=True)
+            print(skip, "pair", res["pair_" + skip], flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
