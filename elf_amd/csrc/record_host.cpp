@@ -211,69 +211,100 @@ inline int Y(int c, int S) { return c / S - 1; }
 
 }  // namespace
 
-SpRecordMeta elfrec_meta_from_options(const ElfSpOptions& o) {
-  SpRecordMeta m{};
-  m.board_size = o.board_size; m.black_ver = o.model_ver; m.white_ver = -1;   // self-play: one AI plays both colours
-  m.num_threads = o.mcts.num_threads > 0 ? o.mcts.num_threads : 1; m.num_rollouts_per_thread = o.num_rollouts_per_thread; m.num_rollouts_per_batch = o.mcts.num_rollouts_per_batch;
-  m.virtual_loss = o.mcts.virtual_loss; m.persistent_tree = o.persistent_tree != 0; m.use_prior = o.mcts.use_prior != 0;
-  m.unexplored_q_zero = o.mcts.unexplored_q_zero != 0; m.root_unexplored_q_zero = o.mcts.root_unexplored_q_zero != 0;
-  m.c_puct = o.mcts.c_puct; m.root_epsilon = o.root_epsilon; m.root_alpha = o.root_alpha;
-  m.black_resign_thres = o.resign_thres; m.white_resign_thres = o.resign_thres; m.never_resign_prob = o.never_resign_prob;
-  m.num_game_thread_used = o.num_games;
-  m.pick_method = o.pick_method;
-  return m;
+SpRequest elfrec_request(const ElfSpRequest& q, const ElfTsOptions& ts, int rules) {
+  SpRequest r;
+  r.q = q; r.ts = ts;
+  if (rules & SPREQ_WAIT_VERSIONS) {
+    if (q.black_ver < 0) r.set_wait();
+    else if (q.white_ver < 0) r.q.white_ver = -1;
+  }
+  if ((rules & SPREQ_DEFAULT_CLIENT_TYPE) && q.client_type == 0) r.q.client_type = 1;
+  for (int32_t* flag : {&r.q.player_swap, &r.q.async, &r.ts.verbose, &r.ts.verbose_time, &r.ts.persistent_tree, &r.ts.use_prior,
+                        &r.ts.unexplored_q_zero, &r.ts.root_unexplored_q_zero})
+    *flag = *flag != 0;
+  const size_t len = strnlen(ts.log_prefix, sizeof(ts.log_prefix));
+  memset(r.ts.log_prefix + len, 0, sizeof(ts.log_prefix) - len);
+  return r;
 }
 
-namespace { void put_json_string(std::string& o, const std::string& t); }
-
-void elfrec_meta_set_ts(SpRecordMeta* m, const ElfTsOptions& t) {
-  m->num_threads = t.num_threads; m->num_rollouts_per_thread = t.num_rollouts_per_thread; m->num_rollouts_per_batch = t.num_rollouts_per_batch;
-  m->virtual_loss = t.virtual_loss; m->persistent_tree = t.persistent_tree != 0; m->use_prior = t.use_prior != 0;
-  m->unexplored_q_zero = t.unexplored_q_zero != 0; m->root_unexplored_q_zero = t.root_unexplored_q_zero != 0;
-  m->c_puct = t.c_puct; m->root_epsilon = t.root_epsilon; m->root_alpha = t.root_alpha; m->pick_method = t.pick_method;
-  m->max_num_moves = t.max_num_moves; m->ts_seed = t.seed; m->verbose = t.verbose != 0; m->verbose_time = t.verbose_time != 0;
-  m->log_prefix.assign(t.log_prefix, strnlen(t.log_prefix, sizeof(t.log_prefix)));
+SpRequest elfrec_request_of_options(const ElfSpOptions& o) {
+  SpRequest r;
+  r.q.black_ver = o.model_ver;   // self-play: one AI plays both colours (white_ver stays -1)
+  r.q.black_resign_thres = r.q.white_resign_thres = o.resign_thres; r.q.never_resign_prob = o.never_resign_prob;
+  r.q.num_game_thread_used = o.num_games;
+  sp_ts_from(&r.ts, o);          // the other TSOptions fields (max_num_moves, seed, verbose*, log_prefix) have no option: zero
+  return r;
 }
 
-// MsgRequest::setJsonFields (record.h:119-127): {"client_ctrl":{...},"vers":{...}} as nlohmann dumps it (keys in std::map order)
-static void put_request(std::string& o, const SpRecordMeta& m) {
+bool SpRequest::same_model_pair(const SpRequest& o) const {
+  const ElfTsOptions &a = ts, &b = o.ts;
+  return q.black_ver == o.q.black_ver && q.white_ver == o.q.white_ver && a.max_num_moves == b.max_num_moves &&
+         a.num_threads == b.num_threads && a.num_rollouts_per_thread == b.num_rollouts_per_thread &&
+         a.num_rollouts_per_batch == b.num_rollouts_per_batch && a.verbose == b.verbose && a.verbose_time == b.verbose_time &&
+         a.seed == b.seed && a.persistent_tree == b.persistent_tree && a.pick_method == b.pick_method &&
+         !strncmp(a.log_prefix, b.log_prefix, sizeof(a.log_prefix)) && a.root_epsilon == b.root_epsilon && a.root_alpha == b.root_alpha &&
+         a.virtual_loss == b.virtual_loss && a.use_prior == b.use_prior && a.c_puct == b.c_puct &&
+         a.unexplored_q_zero == b.unexplored_q_zero && a.root_unexplored_q_zero == b.root_unexplored_q_zero;
+}
+bool operator==(const SpRequest& a, const SpRequest& b) {
+  return a.same_model_pair(b) && a.q.black_resign_thres == b.q.black_resign_thres && a.q.white_resign_thres == b.q.white_resign_thres &&
+         a.q.never_resign_prob == b.q.never_resign_prob && a.q.num_game_thread_used == b.q.num_game_thread_used &&
+         a.q.player_swap == b.q.player_swap && a.q.async == b.q.async && a.q.client_type == b.q.client_type;
+}
+
+namespace {
+void put_json_string(std::string& o, const std::string& t);
+
+// TSOptions.pick_method by name, index = ELFSP_PICK_*
+const char* const kPickNames[] = {"most_visited", "strongest_prior", "uniform_random"};
+int pick_code(const std::string& name) {      // -1: the search would throw "Unknown pick method"
+  for (int i = 0; i < 3; ++i) if (name == kPickNames[i]) return i;
+  return -1;
+}
+const char* pick_name(int code) { return kPickNames[code == ELFSP_PICK_STRONGEST_PRIOR || code == ELFSP_PICK_UNIFORM_RANDOM ? code : 0]; }
+}  // namespace
+
+// MsgRequest::setJsonFields (record.h:119-127): {"client_ctrl":{...},"vers":{...}} as nlohmann dumps it (keys in std::map order);
+// an unknown pick_method prints as most_visited
+static void put_request(std::string& o, const SpRequest& m) {
+  const ElfSpRequest& q = m.q;
+  const ElfTsOptions& t = m.ts;
   o += "{\"client_ctrl\":{\"async\":";
-  put_bool(o, m.async);
+  put_bool(o, q.async);
   o += ",\"black_resign_thres\":";
-  put_float(o, m.black_resign_thres);
-  o += ",\"client_type\":" + std::to_string((uint32_t)m.client_type) + ",\"never_resign_prob\":"; put_float(o, m.never_resign_prob);
-  o += ",\"num_game_thread_used\":" + std::to_string(m.num_game_thread_used);
-  o += ",\"player_swap\":"; put_bool(o, m.player_swap);
-  o += ",\"white_resign_thres\":"; put_float(o, m.white_resign_thres);
-  o += "},\"vers\":{\"black_ver\":" + std::to_string(m.black_ver) + ",\"mcts_opt\":{\"alg_opt\":{\"c_puct\":"; put_float(o, m.c_puct);
-  o += ",\"root_unexplored_q_zero\":"; put_bool(o, m.root_unexplored_q_zero);
-  o += ",\"unexplored_q_zero\":"; put_bool(o, m.unexplored_q_zero);
-  o += ",\"use_prior\":"; put_bool(o, m.use_prior);
-  o += "},\"log_prefix\":"; put_json_string(o, m.log_prefix);
-  o += ",\"max_num_moves\":" + std::to_string(m.max_num_moves) + ",\"num_rollouts_per_batch\":" + std::to_string(m.num_rollouts_per_batch);
-  o += ",\"num_rollouts_per_thread\":" + std::to_string(m.num_rollouts_per_thread);
-  o += ",\"num_threads\":" + std::to_string(m.num_threads) + ",\"persistent_tree\":"; put_bool(o, m.persistent_tree);
-  o += std::string(",\"pick_method\":\"") + (m.pick_method == 1 ? "strongest_prior" : m.pick_method == 2 ? "uniform_random" : "most_visited") +
-       "\",\"root_alpha\":";
-  put_float(o, m.root_alpha);
-  o += ",\"root_epsilon\":"; put_float(o, m.root_epsilon);
-  o += ",\"seed\":" + std::to_string(m.ts_seed) + ",\"verbose\":"; put_bool(o, m.verbose);
-  o += ",\"verbose_time\":"; put_bool(o, m.verbose_time);
-  o += ",\"virtual_loss\":" + std::to_string(m.virtual_loss);
-  o += "},\"white_ver\":" + std::to_string(m.white_ver) + "}}";
+  put_float(o, q.black_resign_thres);
+  o += ",\"client_type\":" + std::to_string((uint32_t)q.client_type) + ",\"never_resign_prob\":"; put_float(o, q.never_resign_prob);
+  o += ",\"num_game_thread_used\":" + std::to_string(q.num_game_thread_used);
+  o += ",\"player_swap\":"; put_bool(o, q.player_swap);
+  o += ",\"white_resign_thres\":"; put_float(o, q.white_resign_thres);
+  o += "},\"vers\":{\"black_ver\":" + std::to_string(q.black_ver) + ",\"mcts_opt\":{\"alg_opt\":{\"c_puct\":"; put_float(o, t.c_puct);
+  o += ",\"root_unexplored_q_zero\":"; put_bool(o, t.root_unexplored_q_zero);
+  o += ",\"unexplored_q_zero\":"; put_bool(o, t.unexplored_q_zero);
+  o += ",\"use_prior\":"; put_bool(o, t.use_prior);
+  o += "},\"log_prefix\":"; put_json_string(o, std::string(t.log_prefix, strnlen(t.log_prefix, sizeof(t.log_prefix))));
+  o += ",\"max_num_moves\":" + std::to_string(t.max_num_moves) + ",\"num_rollouts_per_batch\":" + std::to_string(t.num_rollouts_per_batch);
+  o += ",\"num_rollouts_per_thread\":" + std::to_string(t.num_rollouts_per_thread);
+  o += ",\"num_threads\":" + std::to_string(t.num_threads) + ",\"persistent_tree\":"; put_bool(o, t.persistent_tree);
+  o += std::string(",\"pick_method\":\"") + pick_name(t.pick_method) + "\",\"root_alpha\":";
+  put_float(o, t.root_alpha);
+  o += ",\"root_epsilon\":"; put_float(o, t.root_epsilon);
+  o += ",\"seed\":" + std::to_string(t.seed) + ",\"verbose\":"; put_bool(o, t.verbose);
+  o += ",\"verbose_time\":"; put_bool(o, t.verbose_time);
+  o += ",\"virtual_loss\":" + std::to_string(t.virtual_loss);
+  o += "},\"white_ver\":" + std::to_string(q.white_ver) + "}}";
 }
 
-std::string elfrec_record_json(const SpRecordMeta& m, const SpRecord& r) {
+std::string elfrec_record_json(int board_size, const SpRequest& req, const SpRecord& r) {
   std::string o;
   o.reserve(4096 + r.policies.size() * 3);
-  const int P = (m.board_size + 2) * (m.board_size + 2);
+  const int P = (board_size + 2) * (board_size + 2);
   o += "{\"offline\":false,\"pri\":0.0,\"request\":";
-  put_request(o, m);
+  put_request(o, req);
   o += ",\"result\":{\"black_never_resign\":"; put_bool(o, r.never_resign);
   o += ",\"content\":\"";
   {
     std::vector<char> buf(r.moves.size() * 6 + 8);
-    const int len = elfrec_coords_to_sgfstr(m.board_size, r.moves.data(), (int)r.moves.size(), buf.data(), buf.size());
+    const int len = elfrec_coords_to_sgfstr(board_size, r.moves.data(), (int)r.moves.size(), buf.data(), buf.size());
     for (int i = 0; i < len; ++i) {   // coord2str of an off-board Coord can emit '`' or '\\'-range bytes; escape as nlohmann does
       const unsigned char ch = (unsigned char)buf[i];
       if (ch == '"') o += "\\\"";
@@ -300,7 +331,7 @@ std::string elfrec_record_json(const SpRecordMeta& m, const SpRecord& r) {
     if (!r.using_models.empty()) {
       for (int64_t v : r.using_models) { if (!first) o += ','; o += std::to_string(v); first = false; }
     } else {
-      int64_t a = m.black_ver, b = m.white_ver;
+      int64_t a = req.q.black_ver, b = req.q.white_ver;
       if (a > b) { int64_t t = a; a = b; b = t; }
       if (a >= 0) { o += std::to_string(a); first = false; }
       if (b >= 0 && b != a) { if (!first) o += ','; o += std::to_string(b); }
@@ -595,15 +626,10 @@ int elfrec_record_to_json2(const ElfSpOptions* opt, const ElfSpRequest* request,
   r.policies.assign(policies, policies + (size_t)num_policies * P);
   r.values.assign(values, values + num_values);
   r.reward = reward; r.never_resign = never_resign != 0; r.num_move = num_moves; r.seq = seq; r.thread_id = thread_id; r.timestamp = timestamp;
-  SpRecordMeta m = elfrec_meta_from_options(*opt);
-  if (request) {
-    m.black_ver = request->black_ver; m.white_ver = request->white_ver;
-    m.black_resign_thres = request->black_resign_thres; m.white_resign_thres = request->white_resign_thres;
-    m.never_resign_prob = request->never_resign_prob; m.num_game_thread_used = request->num_game_thread_used;
-    m.player_swap = request->player_swap != 0; m.async = request->async != 0;
-    m.client_type = request->client_type != 0 ? request->client_type : 1;
-  }
-  const std::string t = elfrec_record_json(m, r);
+  SpRequest m = elfrec_request_of_options(*opt);
+  if (m.ts.num_threads < 1) m.ts.num_threads = 1;   // these options were never validated (elfsp_create refuses num_threads < 1)
+  if (request) m = elfrec_request(*request, m.ts, SPREQ_DEFAULT_CLIENT_TYPE);
+  const std::string t = elfrec_record_json(opt->board_size, m, r);
   if (out && cap > t.size()) { memcpy(out, t.data(), t.size()); out[t.size()] = 0; }
   else if (out) return ELFGO_E_BADSIZE;
   return (int)t.size();
@@ -1101,8 +1127,7 @@ int elfrec_parse_request_seq(const char* text, ElfSpRequest* request, int64_t* s
     const JValue* pm = mo->get("pick_method");
     const JValue* lp = mo->get("log_prefix");
     if (!pm || pm->kind != JValue::STR || !lp || lp->kind != JValue::STR) return ELFGO_E_BADARG;
-    t.pick_method = pm->str == "most_visited" ? ELFSP_PICK_MOST_VISITED : pm->str == "strongest_prior" ? ELFSP_PICK_STRONGEST_PRIOR :
-                    pm->str == "uniform_random" ? ELFSP_PICK_UNIFORM_RANDOM : -1;   // -1: the search would throw "Unknown pick method"
+    t.pick_method = pick_code(pm->str);
     snprintf(t.log_prefix, sizeof(t.log_prefix), "%s", lp->str.c_str());
   }
   NEED_FLT(mo, "root_epsilon", t.root_epsilon); NEED_FLT(mo, "root_alpha", t.root_alpha); NEED_INT(mo, "virtual_loss", t.virtual_loss);
@@ -1165,16 +1190,8 @@ int64_t elfrec_record_to_sgf(const ElfSpOptions* opt, const char* record_json, c
 // MsgRequestSeq::dumpJsonString (record.h:167-171): {"request":{...},"seq":n} -- what the reference's server writes
 int64_t elfrec_request_seq_to_json(const ElfSpRequest* request, const ElfTsOptions* t, int64_t seq, char* out, size_t cap) {
   if (!request || !t) return ELFGO_E_BADARG;
-  SpRecordMeta m{};
-  m.board_size = 0;
-  m.black_ver = request->black_ver; m.white_ver = request->white_ver;
-  elfrec_meta_set_ts(&m, *t);
-  m.black_resign_thres = request->black_resign_thres; m.white_resign_thres = request->white_resign_thres;
-  m.never_resign_prob = request->never_resign_prob; m.num_game_thread_used = request->num_game_thread_used;
-  m.player_swap = request->player_swap != 0; m.async = request->async != 0;
-  m.client_type = request->client_type;          // as given (a parsed request is written back unchanged)
   std::string o = "{\"request\":";
-  put_request(o, m);
+  put_request(o, elfrec_request(*request, *t, SPREQ_AS_GIVEN));   // a parsed request is written back unchanged
   o += ",\"seq\":" + std::to_string(seq) + "}";
   if (!out) return (int64_t)o.size();
   if (cap <= o.size()) return ELFGO_E_BADSIZE;

@@ -43,26 +43,8 @@
 #include "host_workers.h"
 #include "record_host.h"
 
-struct ElfSpSearchRec {   // == ElfSpSearch in include/elf_amd.h
-  int32_t game, move_played, best_action, total_visits, n_edges;
-  float root_value, max_score, predicted_value;
-};
-
 enum { PH_WAIT = 0, PH_BARRIER = 1, PH_PLAY = 2 };
 enum { GMASK_IDLE = 0, GMASK_SEARCH = 1, GMASK_POLICY_ONLY = 2 };   // == GM_* of mcts.cuh
-
-struct SpRequest {          // MsgRequest (common/record.h:119-149): ModelPair + ClientCtrl
-  int64_t black_ver = -1, white_ver = -1;
-  float black_thres = 0.f, white_thres = 0.f, never_resign_prob = 0.f;
-  bool async = false, player_swap = false;
-  int thread_used = -1;
-  int client_type = 1;         // ClientCtrl.client_type: carried into the records only
-  ElfTsOptions ts;             // ModelPair.mcts_opt: the search options the AIs of this request are built with
-  int id = 0;
-  bool wait() const { return black_ver < 0; }                           // ModelPair::wait
-  bool is_selfplay() const { return black_ver >= 0 && white_ver == -1; }
-  void set_wait() { black_ver = white_ver = -1; }
-};
 
 struct SpPly {                // one move since the game (re)started, with what it appended to the pending Record
   uint16_t move;
@@ -106,8 +88,8 @@ struct SpGame {
   // unless the game was set up with White to move (elfsp_setup leaves the ply at 1)
   bool black_to_move() const { return ((ply & 1) == 1) != (set_up && setup_player == S_WHITE); }
   void add_current_model() {   // GoStateExt::addCurrentModel (go_state_ext.h:68-73)
-    if (req.black_ver >= 0) using_models.insert(req.black_ver);
-    if (req.white_ver >= 0) using_models.insert(req.white_ver);
+    if (req.q.black_ver >= 0) using_models.insert(req.q.black_ver);
+    if (req.q.white_ver >= 0) using_models.insert(req.q.white_ver);
   }
 };
 
@@ -178,7 +160,7 @@ struct ElfSelfPlay {
   // pipeline depth, not boundary work); boundary_ns = everything after it up to the end of the next search start
   int64_t boundary_ns = 0, boundary_wait_ns = 0, n_boundaries = 0;
   double sum_final = 0.0;
-  std::vector<ElfSpSearchRec> log_search;
+  std::vector<ElfSpSearch> log_search;
   std::vector<int32_t> log_coord, log_visits;
   std::vector<float> log_prior, log_reward;
   int log_cap = 0;
@@ -208,27 +190,7 @@ static void sp_for_games(const std::vector<int32_t>& ids, F fn) {
   HostWorkers::get().run(n, nt, [&](size_t i) { fn(ids[i]); });
 }
 
-// The twelve fields of a request's TSOptions that the tree pools are built from, each next to the field of ElfSpOptions it lives in
-// (`flag`: a bool of the reference, any non-zero value is true).  max_num_moves, seed, verbose*, log_prefix take part in
-// ModelPair::operator== (sp_ts_equal) but never in the shape of a pool.
-template <class T, class O, class F>   // ElfTsOptions, ElfSpOptions, either of them const or not
-static void sp_ts_fields(T& t, O& o, F f) {
-  f(t.num_threads, o.mcts.num_threads, false); f(t.num_rollouts_per_thread, o.num_rollouts_per_thread, false);
-  f(t.num_rollouts_per_batch, o.mcts.num_rollouts_per_batch, false); f(t.persistent_tree, o.persistent_tree, true);
-  f(t.pick_method, o.pick_method, false); f(t.root_epsilon, o.root_epsilon, false); f(t.root_alpha, o.root_alpha, false);
-  f(t.virtual_loss, o.mcts.virtual_loss, false); f(t.use_prior, o.mcts.use_prior, true); f(t.c_puct, o.mcts.c_puct, false);
-  f(t.unexplored_q_zero, o.mcts.unexplored_q_zero, true); f(t.root_unexplored_q_zero, o.mcts.root_unexplored_q_zero, true);
-}
-// TSOptions <-> the fields of ElfSpOptions they live in
-static void sp_ts_from(ElfTsOptions* t, const ElfSpOptions& o) {
-  sp_ts_fields(*t, o, [](auto& tf, const auto& of, bool flag) { tf = flag ? of != 0 : of; });
-}
-static ElfTsOptions sp_ts_of(const ElfSpOptions& o) {
-  ElfTsOptions t;
-  memset(&t, 0, sizeof(t));
-  sp_ts_from(&t, o);
-  return t;
-}
+// TSOptions (record_host.h: sp_ts_fields, sp_ts_from) -> the fields of ElfSpOptions they live in
 static void sp_ts_into(const ElfTsOptions& t, ElfSpOptions* o) {
   sp_ts_fields(t, *o, [](const auto& tf, auto& of, bool flag) { of = flag ? tf != 0 : tf; });
 }
@@ -238,30 +200,15 @@ static bool sp_ts_pool_equal(const ElfTsOptions& t, const ElfSpOptions& o) {
   sp_ts_fields(t, o, [&](const auto& tf, const auto& of, bool flag) { eq = eq && (flag ? (tf != 0) == (of != 0) : tf == of); });
   return eq;
 }
-static bool sp_ts_equal(const ElfTsOptions& a, const ElfTsOptions& b) {      // TSOptions::operator== (tree_search_options.h:133-180)
-  return a.max_num_moves == b.max_num_moves && a.num_threads == b.num_threads && a.num_rollouts_per_thread == b.num_rollouts_per_thread &&
-         a.num_rollouts_per_batch == b.num_rollouts_per_batch && (a.verbose != 0) == (b.verbose != 0) && (a.verbose_time != 0) == (b.verbose_time != 0) &&
-         a.seed == b.seed && (a.persistent_tree != 0) == (b.persistent_tree != 0) && a.pick_method == b.pick_method &&
-         !strncmp(a.log_prefix, b.log_prefix, sizeof(a.log_prefix)) && a.root_epsilon == b.root_epsilon && a.root_alpha == b.root_alpha &&
-         a.virtual_loss == b.virtual_loss && (a.use_prior != 0) == (b.use_prior != 0) && a.c_puct == b.c_puct &&
-         (a.unexplored_q_zero != 0) == (b.unexplored_q_zero != 0) && (a.root_unexplored_q_zero != 0) == (b.root_unexplored_q_zero != 0);
-}
 
-static SpRecordMeta sp_meta(const ElfSelfPlay* sp, const SpGame& gm) {
-  // Record.request = curr_request_ (go_state_ext.h:134): the game's own request incl. the mcts_opt it carried
-  SpRecordMeta m = elfrec_meta_from_options(sp->opt);
-  m.black_ver = gm.req.black_ver; m.white_ver = gm.req.white_ver;
-  m.black_resign_thres = gm.req.black_thres; m.white_resign_thres = gm.req.white_thres; m.never_resign_prob = gm.req.never_resign_prob;
-  m.num_game_thread_used = gm.req.thread_used;
-  m.player_swap = gm.req.player_swap; m.async = gm.req.async;
-  m.client_type = gm.req.client_type;
-  // vers.mcts_opt as the request carried it -- except where this game searched with OTHER options: a request that restarted only
-  // some games while the rest played on could not rebuild the context's tree pools (sp_poll_requests, "deferred"); those games'
-  // records carry the search options that were actually used, not the ones the request asked for
-  ElfTsOptions used = gm.req.ts;
-  if (!sp_ts_pool_equal(used, sp->opt)) sp_ts_from(&used, sp->opt);
-  elfrec_meta_set_ts(&m, used);
-  return m;
+// Record.request = curr_request_ (go_state_ext.h:134): the game's own request incl. the mcts_opt it carried -- except where this
+// game searched with OTHER options: a request that restarted only some games while the rest played on could not rebuild the
+// context's tree pools (sp_poll_requests, "deferred"); those games' records carry the search options that were actually used,
+// not the ones the request asked for.  Once per finished game.
+static SpRequest sp_record_request(const ElfSelfPlay* sp, const SpGame& gm) {
+  SpRequest used = gm.req;
+  if (!sp_ts_pool_equal(used.ts, sp->opt)) sp_ts_from(&used.ts, sp->opt);
+  return used;
 }
 
 static void sp_finish_record(ElfSelfPlay* sp, int g, float final_value, int final_ply) {
@@ -279,7 +226,7 @@ static void sp_finish_record(ElfSelfPlay* sp, int g, float final_value, int fina
     r.using_models.assign(gm.using_models.begin(), gm.using_models.end());
     r.timestamp = (uint64_t)std::chrono::duration_cast<std::chrono::seconds>(std::chrono::system_clock::now().time_since_epoch()).count();
     if ((int)sp->records.size() >= sp->opt.keep_records) sp->records.pop_front();
-    sp->records.push_back(elfrec_record_json(sp_meta(sp, gm), r));
+    sp->records.push_back(elfrec_record_json(sp->opt.board_size, sp_record_request(sp, gm), r));
   }
   gm.rec = SpRecord();                           // GoStateExt::restart(): _mcts_policies.clear(), _predicted_values.clear()
 }
@@ -378,24 +325,24 @@ static int sp_restart_games(ElfSelfPlay* sp, const std::vector<int32_t>& ids) {
   const int k = (int)ids.size();
   if (k == 0) return 0;
   bool need2 = false;
-  for (int g : ids) need2 = need2 || sp->games[g].req.white_ver >= 0;
+  for (int g : ids) need2 = need2 || sp->games[g].req.q.white_ver >= 0;
   if (need2) SPCHK(sp_pool_create(sp, 1));
   for (int g : ids) {
     SpGame& gm = sp->games[g];
-    const bool two = gm.req.white_ver >= 0;
+    const bool two = gm.req.q.white_ver >= 0;
     gm.actor_rng[0].seed(gm.rng());
     gm.actor_rng0[0] = gm.actor_rng[0];      // every search thread's actor starts from this state (the same params.seed)
     gm.thread_rng[0].clear();                // sized at the AI's first search (the pools may be rebuilt for the request's threads first)
-    gm.actor_ver[0] = gm.req.async ? -1 : gm.req.black_ver;
+    gm.actor_ver[0] = gm.req.q.async ? -1 : gm.req.q.black_ver;
     if (two) {
       gm.actor_rng[1].seed(gm.rng());
       gm.actor_rng0[1] = gm.actor_rng[1];
       gm.thread_rng[1].clear();
-      gm.actor_ver[1] = gm.req.async ? -1 : gm.req.white_ver;
+      gm.actor_ver[1] = gm.req.q.async ? -1 : gm.req.q.white_ver;
     }
     gm.pool_of_colour[0] = 0;
     gm.pool_of_colour[1] = two ? 1 : 0;
-    if (!gm.req.is_selfplay() && gm.req.player_swap && two) std::swap(gm.pool_of_colour[0], gm.pool_of_colour[1]);
+    if (!gm.req.is_selfplay() && gm.req.q.player_swap && two) std::swap(gm.pool_of_colour[0], gm.pool_of_colour[1]);
     sp_state_restart(gm);
     gm.sgf_iter = 0;
     gm.ai = -1;
@@ -410,15 +357,15 @@ static int sp_restart_games(ElfSelfPlay* sp, const std::vector<int32_t>& ids) {
 static bool sp_on_receive(ElfSelfPlay* sp, int g, const SpRequest& r, bool* model_changed) {
   SpGame& gm = sp->games[g];
   const bool is_waiting = r.wait(), is_prev_waiting = gm.req.wait();
-  const bool same_vers = r.black_ver == gm.req.black_ver && r.white_ver == gm.req.white_ver && sp_ts_equal(r.ts, gm.req.ts);   // ModelPair::operator==
-  const bool same_swap = r.player_swap == gm.req.player_swap;
-  const bool no_restart = (same_vers || r.async) && same_swap && !is_prev_waiting;
+  const bool same_vers = r.same_model_pair(gm.req);
+  const bool same_swap = r.q.player_swap == gm.req.q.player_swap;
+  const bool no_restart = (same_vers || r.q.async) && same_swap && !is_prev_waiting;
   gm.req = r;                                    // _state_ext.setRequest: thresholds follow the request (go_state_ext.h:57-66)
   gm.seen_req = r.id;
   if (is_waiting) { gm.phase = PH_WAIT; return false; }           // ONLY_WAIT
   if (!no_restart) { gm.phase = PH_BARRIER; *model_changed = true; return true; }   // UPDATE_MODEL
   gm.phase = PH_PLAY;
-  if (r.async) {                                 // setAsync :150-156
+  if (r.q.async) {                               // setAsync :150-156
     gm.actor_ver[0] = gm.actor_ver[1] = -1;
     gm.add_current_model();
     if (!same_vers) *model_changed = true;       // UPDATE_MODEL_ASYNC
@@ -466,7 +413,7 @@ static int sp_poll_requests(ElfSelfPlay* sp) {
       const bool looks = gm.phase == PH_WAIT || (gm.phase == PH_PLAY && gm.ai < 0 && gm.online_counter % 5 == 0);
       if (!looks) { ++pending; continue; }
       SpRequest r = sp->cur;
-      if (r.thread_used >= 0 && g >= r.thread_used) r.set_wait();   // DispatcherCallback::OnFirstSend :28-44
+      if (r.q.num_game_thread_used >= 0 && g >= r.q.num_game_thread_used) r.set_wait();   // DispatcherCallback::OnFirstSend :28-44
       if (sp_on_receive(sp, g, r, &sp->cur_restarted)) restart.push_back(g);
     }
     sp->cur_n_restart += (int)restart.size();
@@ -475,7 +422,7 @@ static int sp_poll_requests(ElfSelfPlay* sp) {
     // every game has replied: OnReply :46-103
     if (sp->cur_restarted) {
       sp->game_starts++;
-      sp->start_black = sp->cur.black_ver; sp->start_white = sp->cur.white_ver;
+      sp->start_black = sp->cur.q.black_ver; sp->start_white = sp->cur.q.white_ver;
       // the restarted games' AIs are built from the request's TSOptions (restart() :166-180).  The pools belong to the whole
       // context, so they are rebuilt for other options only when some game actually restarted (an async model update restarts
       // nobody: setAsync :150-156 only clears required_version, the AIs keep the TSOptions they were built with) and no game is
@@ -619,9 +566,9 @@ static int sp_restart_finished(ElfSelfPlay* sp, const std::vector<int32_t>& ids)
 // GoStateExt::setFinalValue (go_state_ext.h:76-103) with finish_game's cheat overrides (:122-129); `evaluated` = GoState::evaluate(komi)
 static float sp_final_value(ElfSelfPlay* sp, SpGame& gm, int reason, float evaluated) {
   if (!gm.req.is_selfplay() && sp->opt.cheat_eval_new_model_wins_half) {
-    const size_t h = std::hash<std::string>{}(std::to_string(gm.req.black_ver)) ^ std::hash<std::string>{}(std::to_string(gm.req.white_ver));
+    const size_t h = std::hash<std::string>{}(std::to_string(gm.req.q.black_ver)) ^ std::hash<std::string>{}(std::to_string(gm.req.q.white_ver));
     float fv = h % 2 == 0 ? 1.0f : -1.0f;
-    if (gm.req.player_swap) fv = -fv;
+    if (gm.req.q.player_swap) fv = -fv;
     return fv;
   }
   if (gm.req.is_selfplay() && sp->opt.cheat_selfplay_random_result) return gm.rng() % 2 == 0 ? 1.0f : -1.0f;
@@ -743,10 +690,10 @@ static SpDecision sp_decide_move(SpGame& gm, const ElfSpOptions& opt, const SpRo
     const float value = black ? predicted : -predicted;
     if (!gm.has_calculated_never_resign) {
       std::uniform_real_distribution<> dis(0.0, 1.0);
-      gm.never_resign = (dis(gm.rng) < gm.req.never_resign_prob);
+      gm.never_resign = (dis(gm.rng) < gm.req.q.never_resign_prob);
       gm.has_calculated_never_resign = true;
     }
-    const float thres = (gm.req.black_thres + gm.req.white_thres) / 2.0;   // setRequest, go_state_ext.h:62-66
+    const float thres = (gm.req.q.black_resign_thres + gm.req.q.white_resign_thres) / 2.0;   // setRequest, go_state_ext.h:62-66
     if (!gm.never_resign && !(value >= -1.0 + thres)) resign = true;
   }
   return SpDecision{c, best_action, total_visits, max_score, predicted, resign};
@@ -798,7 +745,7 @@ static int sp_finish_moves(ElfSelfPlay* sp, const std::vector<int32_t> (&done)[2
       const SpDecision d = sp_decide_move(gm, sp->opt, root, follow ? sp->val.h[di] : 0.0f,
                                           follow ? sp->binfo.h[di * ELFGO_INFO_WORDS + 2] : -1, sp->pick_rng);
       if (sp->log_cap > 0 && (int)sp->log_search.size() < sp->log_cap) {
-        ElfSpSearchRec r;
+        ElfSpSearch r;
         r.game = g; r.move_played = d.move; r.best_action = d.best_action; r.total_visits = d.total_visits; r.n_edges = root.n;
         r.root_value = root.root_value; r.max_score = d.max_score; r.predicted_value = d.predicted;
         sp->log_search.push_back(r);
@@ -943,15 +890,9 @@ int elfsp_create(const ElfSpOptions* o, int device, const uint64_t* zobrist_host
   if (e != hipSuccess) { elfsp_destroy(sp); return (int)e; }
   sp->log_cap = o->log_searches;
   // the request the games start under unless the caller sends one before the first step: self-play with ElfSpOptions.model_ver
-  SpRequest r;
-  r.black_ver = o->model_ver; r.white_ver = -1;
-  r.black_thres = r.white_thres = o->resign_thres; r.never_resign_prob = o->never_resign_prob;
-  r.thread_used = o->num_games;
+  // (num_threads >= 1 was checked on entry, so unlike the record writer's unvalidated options these need no clamp)
   sp->opt0 = *o;
-  r.ts = sp_ts_of(*o);
-  sp->cur.ts = r.ts;
-  for (SpGame& gm : sp->games) gm.req.ts = r.ts;
-  sp_push_request(sp, r);
+  sp_push_request(sp, elfrec_request_of_options(*o));
   *out = sp;
   return 0;
 }
@@ -1093,7 +1034,7 @@ int elfsp_set_request2(ElfSelfPlay* sp, const ElfSpRequest* q) { return elfsp_se
 int elfsp_set_request3(ElfSelfPlay* sp, const ElfSpRequest* q, const ElfTsOptions* mcts_opt) {
   if (!sp || !q) return ELFGO_E_BADARG;
   if (q->white_ver >= 0 && q->black_ver < 0) return ELFGO_E_BADARG;
-  const ElfTsOptions ts = mcts_opt ? *mcts_opt : sp_ts_of(sp->opt0);
+  const ElfTsOptions ts = mcts_opt ? *mcts_opt : elfrec_request_of_options(sp->opt0).ts;
   if (ts.num_threads < 1 || ts.num_rollouts_per_batch < 1 || ts.num_rollouts_per_thread < 1 || ts.pick_method < ELFSP_PICK_MOST_VISITED ||
       ts.pick_method > ELFSP_PICK_UNIFORM_RANDOM || (int64_t)ts.num_rollouts_per_batch * ts.num_threads > elfmcts_max_rollouts_per_step())
     return ELFGO_E_BADARG;
@@ -1105,14 +1046,7 @@ int elfsp_set_request3(ElfSelfPlay* sp, const ElfSpRequest* q, const ElfTsOption
     sp_pool_options(o2, 1, &mo, &rpt);
     if ((int64_t)mo.num_rollouts_per_batch * mo.num_threads > elfmcts_max_rollouts_per_step() || rpt <= 0) return ELFGO_E_BADARG;
   }
-  SpRequest r;
-  r.ts = ts;
-  r.black_ver = q->black_ver < 0 ? -1 : q->black_ver;
-  r.white_ver = q->black_ver < 0 ? -1 : (q->white_ver < 0 ? -1 : q->white_ver);
-  r.black_thres = q->black_resign_thres; r.white_thres = q->white_resign_thres; r.never_resign_prob = q->never_resign_prob;
-  r.async = q->async != 0; r.player_swap = q->player_swap != 0;
-  r.thread_used = q->num_game_thread_used;
-  r.client_type = q->client_type != 0 ? q->client_type : 1;
+  const SpRequest r = elfrec_request(*q, ts, SPREQ_DEFAULT_CLIENT_TYPE | SPREQ_WAIT_VERSIONS);
   if (!sp->explicit_request && sp->n_steps == 0 && !sp->step_open && !sp->mailbox.empty() && sp->cur_done) {
     // nothing has been played yet: this request replaces the implicit one of elfsp_create (the reference's games wait for their
     // first request, game_selfplay.cc:277-279)
@@ -1122,10 +1056,7 @@ int elfsp_set_request3(ElfSelfPlay* sp, const ElfSpRequest* q, const ElfTsOption
   // the dispatcher forwards a message only if it differs from the last one (dispatcher.h:92-100)
   const SpRequest& last = sp->mailbox.empty() ? sp->cur : sp->mailbox.back();
   const bool have_last = !sp->mailbox.empty() || sp->cur.id != 0;
-  if (have_last && last.black_ver == r.black_ver && last.white_ver == r.white_ver && last.black_thres == r.black_thres &&
-      last.white_thres == r.white_thres && last.never_resign_prob == r.never_resign_prob && last.async == r.async &&
-      last.player_swap == r.player_swap && last.thread_used == r.thread_used && last.client_type == r.client_type && sp_ts_equal(last.ts, r.ts))
-    return 0;
+  if (have_last && last == r) return 0;
   sp_push_request(sp, r);
   if (!sp->step_open) {                              // games between two searches may look at their mailbox now
     DevGuard _dg(sp->eng->device);
@@ -1165,8 +1096,8 @@ int elfsp_thread_states(const ElfSelfPlay* sp, ElfThreadState* out, int capacity
     t.seq = gm.seq;
     t.move_idx = gm.ply - 1;
     t.reserved = 0;
-    t.black = gm.req.black_ver;
-    t.white = gm.req.white_ver;
+    t.black = gm.req.q.black_ver;
+    t.white = gm.req.q.white_ver;
   }
   return sp->G;
 }
@@ -1348,9 +1279,8 @@ int elfsp_stats(ElfSelfPlay* sp, int64_t* out) {
 
 int elfsp_search_log(const ElfSelfPlay* sp, int first, int n, ElfSpSearch* rec, int32_t* coord, int32_t* visits, float* prior, float* reward) {
   if (!sp || first < 0 || n < 0 || first + n > (int)sp->log_search.size()) return ELFGO_E_BADARG;
-  static_assert(sizeof(ElfSpSearch) == sizeof(ElfSpSearchRec), "ElfSpSearch layout");
   const size_t NE = sp->NE;
-  if (rec) memcpy(rec, sp->log_search.data() + first, sizeof(ElfSpSearchRec) * n);
+  if (rec) memcpy(rec, sp->log_search.data() + first, sizeof(ElfSpSearch) * n);
   if (coord) memcpy(coord, sp->log_coord.data() + first * NE, 4 * NE * n);
   if (visits) memcpy(visits, sp->log_visits.data() + first * NE, 4 * NE * n);
   if (prior) memcpy(prior, sp->log_prior.data() + first * NE, 4 * NE * n);

@@ -864,3 +864,92 @@ def test_pipelined_groups_with_requests_and_evaluation_games(elf):
     assert pl.versions == [(2, -1), (2, -1)]
     pl.close()
     out.close()
+
+
+def test_request_equality_decides_what_is_forwarded_and_what_restarts(elf):
+    """The equality of two requests (MsgRequest: ModelPair incl. its TSOptions + ClientCtrl) on one 9x9 game of one-step searches.
+    A game looks at its mailbox at every fifth act, so a request has been received after at most 5 more searches.
+    1. An equivalent request -- flags given as 2 instead of 1, other bytes after log_prefix's NUL -- is not forwarded
+       (dispatcher.h:92-100): no game_start, the game plays on.
+    2. Every one of the 17 TSOptions fields takes part in ModelPair::operator== (tree_search_options.h:133-180), also the ones no
+       search reads: a request that differs in one of them restarts the game under the same versions.
+    3. Every ClientCtrl field travels into the game's request (its next Record shows it) and restarts nothing."""
+    import ctypes as C
+    import json
+    import torch
+    from elf_amd.client import TsOptions
+    from elf_amd.selfplay import SpRequest
+    n, ver = 9, 3
+    L = elf.lib()
+    bv, wv = C.c_int64(-5), C.c_int64(-5)
+
+    def context(**kw):
+        return elf.SelfPlay(board_size=n, num_games=1, mcts_rollout_per_thread=16, mcts_rollout_per_batch=16, nodes_per_game=1024,
+                            seed=11, model_ver=ver, **kw)
+
+    def play(sp, searches):
+        end = sp.progress()["searches"] + searches
+        while sp.progress()["searches"] < end:
+            rows = sp.begin_step()
+            assert rows > 0                                      # the one game never waits
+            pi, v = stub_net(n, sp.s[:rows].cpu().numpy(), 9, 0)
+            sp.end_step(torch.from_numpy(pi).to(sp.device), torch.from_numpy(v).to(sp.device))
+
+    def ply(sp):
+        return int(sp.board_engine().info_host()["ply"][0])      # GoState::getPly: 1 on the empty board
+
+    def game_starts(sp):
+        return L.elfsp_take_game_starts(sp._h, C.byref(bv), C.byref(wv))
+
+    # ---- 1 and 2: the TSOptions half
+    fields = dict(max_num_moves=0, num_threads=1, num_rollouts_per_thread=16, num_rollouts_per_batch=16, verbose=1, verbose_time=1,
+                  persistent_tree=1, pick_method=0, seed=0, root_epsilon=0.25, root_alpha=0.03, virtual_loss=1, use_prior=1,
+                  unexplored_q_zero=1, root_unexplored_q_zero=1, c_puct=1.5, log_prefix=b"abc")
+    assert list(fields) == [f[0] for f in TsOptions._fields_]
+    q = SpRequest(ver, -1, 0.0, 0.0, 0.0, 1, 1, 0, 1)            # player_swap set: a flag of the ClientCtrl half
+    sp = context()
+    sp.send_request(q, TsOptions(**fields))                      # nothing played yet: replaces the context's implicit request
+    play(sp, 1)
+    assert game_starts(sp) == 1 and (bv.value, wv.value) == (ver, -1)
+    flags = ("verbose", "verbose_time", "persistent_tree", "use_prior", "unexplored_q_zero", "root_unexplored_q_zero")
+    assert all(fields[k] == 1 for k in flags)
+    same = TsOptions(**{k: 2 if k in flags else v for k, v in fields.items()})
+    C.memmove(C.addressof(same) + TsOptions.log_prefix.offset, b"abc\0" + b"\x7f" * 56, 60)
+    before = ply(sp)
+    sp.send_request(SpRequest(ver, -1, 0.0, 0.0, 0.0, 1, 2, 0, 1), same)
+    play(sp, 6)
+    assert game_starts(sp) == 0 and ply(sp) == before + 6
+    changes = dict(max_num_moves=100, num_threads=2, num_rollouts_per_thread=32, num_rollouts_per_batch=8, verbose=0, verbose_time=0,
+                   persistent_tree=0, pick_method=1, seed=5, root_epsilon=0.2, root_alpha=0.05, virtual_loss=2, use_prior=0,
+                   unexplored_q_zero=0, root_unexplored_q_zero=0, c_puct=1.25, log_prefix=b"abd")
+    assert list(changes) == list(fields)
+    for k, v in changes.items():
+        assert fields[k] != v
+        fields[k] = v                                            # the current request with only this field changed
+        before = ply(sp)
+        sp.send_request(q, TsOptions(**fields))
+        play(sp, 6)
+        assert game_starts(sp) == 1 and (bv.value, wv.value) == (ver, -1), k
+        assert ply(sp) <= 1 + 6 and ply(sp) < before + 6, k      # back on the empty board at some point of the 6 searches
+    sp.close()
+
+    # ---- 3: the ClientCtrl half; games of 7 moves, every request sent at a game's first move: received before that game ends
+    sp = context(keep_records=4, move_cutoff=8)
+    play(sp, 1)
+    assert game_starts(sp) == 1 and (bv.value, wv.value) == (ver, -1)
+    ctrl = dict(black_ver=ver, white_ver=-1, black_resign_thres=0.0, white_resign_thres=0.0, never_resign_prob=0.0,
+                num_game_thread_used=1, player_swap=0, async_=0, client_type=1)      # the request of the context's options
+    while not sp.pop_records():
+        play(sp, 1)
+    for k, v in (("white_resign_thres", 0.0625), ("never_resign_prob", 0.125), ("client_type", 2), ("num_game_thread_used", -1)):
+        ctrl[k] = v
+        sp.send_request(SpRequest(**ctrl))
+        recs = []
+        while not recs:
+            play(sp, 1)
+            recs = sp.pop_records()
+        got = json.loads(recs[0])["request"]["client_ctrl"]
+        assert {f: got[f] for f in ("white_resign_thres", "never_resign_prob", "client_type", "num_game_thread_used", "black_resign_thres")} == \
+            {f: ctrl[f] for f in ("white_resign_thres", "never_resign_prob", "client_type", "num_game_thread_used", "black_resign_thres")}, k
+        assert game_starts(sp) == 0, k
+    sp.close()
