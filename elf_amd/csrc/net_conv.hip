@@ -11,8 +11,8 @@
 //         op; that op cannot take a bias: it indexes every D tensor with E's descriptor and its IsSupportedArgument refuses a D
 //         whose strides differ from E's, so a [K] bias would have to be expanded to a whole activation.  The ABD op builds the same
 //         gridwise GEMM (same K order y, x, c; same pipeline v1) and gives each D its own descriptor (G_K layout for the bias).
-// algo 1  DeviceGroupedConvFwdMultipleABD_Xdl_CShuffle_V3, 128 x 128 x 64, Intrawave pipeline v4 (the one f16 V3 instance CK's own
-//         list keeps for gfx950).  Another accumulation order: close to, not bit-equal with, algo 0.
+// algo 1  not CK: the hand-written 256 x 256 x 64 LDS-DMA kernel of net_conv3x3.hip, an object of its own that this file only
+//         calls (elfnet_conv3x3_native_f16, hidden: no new exported symbol).  Same K order and MFMA as algo 0.
 //
 // This translation unit is its own object (GNUmakefile): the CK templates take ~40 s each to compile and depend on none of the
 // project's .cuh files, which is also why it carries its own small device guard instead of including engine_host.h.
@@ -28,7 +28,6 @@
 #include "ck/tensor_operation/gpu/device/convolution_forward_specialization.hpp"
 #include "ck/tensor_operation/gpu/device/gemm_specialization.hpp"
 #include "ck/tensor_operation/gpu/device/impl/device_grouped_conv_fwd_multiple_abd_xdl_cshuffle.hpp"
-#include "ck/tensor_operation/gpu/device/impl/device_grouped_conv_fwd_multiple_abd_xdl_cshuffle_v3.hpp"
 #include "ck/tensor_operation/gpu/device/tensor_layout.hpp"
 #include "ck/tensor_operation/gpu/element/element_wise_operation.hpp"
 
@@ -76,14 +75,6 @@ using ConvA = ck::tensor_operation::device::DeviceGroupedConvFwdMultipleABD_Xdl_
     S<4, 64, 1>, S<1, 0, 2>, S<1, 0, 2>, 2, 8, 8, 1,
     S<4, 64, 1>, S<1, 0, 2>, S<1, 0, 2>, 2, 8, 8, 1,
     1, 1, S<1, 32, 1, 8>, 8>;
-
-template <typename DsLayout, typename DsTypes>
-using ConvB = ck::tensor_operation::device::DeviceGroupedConvFwdMultipleABD_Xdl_CShuffle_V3<
-    2, lay::NHWGC, lay::GKYXC, DsLayout, lay::NHWGK, F16, F16, F32, F16, DsTypes, F16, PassThrough, PassThrough, BiasResAct,
-    kConvDefault, kMNKPadding, 256, 128, 128, 64, 8, 8, 32, 32, 2, 2,
-    S<8, 32, 1>, S<1, 0, 2>, S<1, 0, 2>, 2, 8, 8, 0,
-    S<8, 32, 1>, S<1, 0, 2>, S<1, 0, 2>, 2, 8, 8, 0,
-    1, 1, S<1, 32, 1, 8>, 8, ck::BlockGemmPipelineScheduler::Intrawave, ck::BlockGemmPipelineVersion::v4>;
 // clang-format on
 
 using DsBias = ck::Tuple<lay::G_K>;
@@ -137,33 +128,12 @@ int run(const void* x, const void* w, const std::array<const void*, ND>& ds, voi
   return e == hipSuccess ? 0 : (int)e;
 }
 
-// Rows of a convolution do not mix, so a call may run as slices of rows.  algo 0 takes any size this entry point admits in one
-// launch (its device op splits N itself).  The V3 op of algo 1 refuses a problem whose implicit GEMM matrix [rows*H*W][9*C] would
-// hold more than 2^31 bytes were it ever written out (1290 rows of 19 x 19 x 256): it gets slices below that, every slice checked
-// before the first is launched.
-template <typename Op, int ND>
-int run_sliced(const void* x, const void* w, std::array<const void*, ND> ds, void* y, Shape s, int relu, hipStream_t stream,
-               int64_t max_rows) {
-  const int rows = s.n;
-  if (max_rows <= 0) return ELFGO_E_BADARG;
-  const int nsl = (int)((rows + max_rows - 1) / max_rows);
-  const int per = (rows + nsl - 1) / nsl;
-  const size_t xrow = (size_t)s.h * s.w * s.c * 2, yrow = (size_t)s.h * s.w * s.k * 2;
-  for (int pass = 0; pass < 2; ++pass) {
-    for (int r0 = 0; r0 < rows; r0 += per) {
-      Shape sl = s;
-      sl.n = rows - r0 < per ? rows - r0 : per;
-      if (pass == 0 && r0 != 0 && r0 + per < rows) continue;   // the support check depends on the slice's size alone
-      std::array<const void*, ND> d = ds;
-      if (ND == 2) d[ND - 1] = (const char*)ds[ND - 1] + r0 * yrow;
-      int rc = run<Op, ND>((const char*)x + r0 * xrow, w, d, (char*)y + r0 * yrow, sl, relu, stream, pass == 1);
-      if (rc != 0) return rc;
-    }
-  }
-  return 0;
-}
-
 }  // namespace
+
+// net_conv3x3.hip
+extern "C" __attribute__((visibility("hidden"))) int elfnet_conv3x3_native_f16(const void* x, const void* w, const void* bias,
+                                                                               const void* res, void* y, int64_t rows, int h, int wd,
+                                                                               int c, int k, int relu, hipStream_t stream);
 
 extern "C" int elfnet_conv3x3_f16(const void* x, const void* w, const void* bias, const void* res, void* y, int64_t rows, int h, int wd,
                                   int c, int k, int relu, int algo, void* stream) {
@@ -180,11 +150,8 @@ extern "C" int elfnet_conv3x3_f16(const void* x, const void* w, const void* bias
   DevGuard _dg(at.device);
   const Shape s{(int)rows, h, wd, c, k};
   hipStream_t st = (hipStream_t)stream;
-  if (algo == 0) {
-    if (res) return run_sliced<ConvA<DsBiasRes, T2>, 2>(x, w, {bias, res}, y, s, relu, st, rows);
-    return run_sliced<ConvA<DsBias, T1>, 1>(x, w, {bias}, y, s, relu, st, rows);
-  }
-  const int64_t v3_rows = (((int64_t)1 << 31) / 2) / ((int64_t)h * wd * 9 * cmax);
-  if (res) return run_sliced<ConvB<DsBiasRes, T2>, 2>(x, w, {bias, res}, y, s, relu, st, v3_rows);
-  return run_sliced<ConvB<DsBias, T1>, 1>(x, w, {bias}, y, s, relu, st, v3_rows);
+  if (algo == 1) return elfnet_conv3x3_native_f16(x, w, bias, res, y, rows, h, wd, c, k, relu, st);
+  // one launch whatever the size: the device op splits N itself
+  if (res) return run<ConvA<DsBiasRes, T2>, 2>(x, w, {bias, res}, y, s, relu, st, true);
+  return run<ConvA<DsBias, T1>, 1>(x, w, {bias}, y, s, relu, st, true);
 }

@@ -160,9 +160,11 @@ class FusedInferenceNet:
 
     Eager PyTorch issues conv -> bias add -> ReLU (-> residual add -> ReLU) as separate elementwise kernels, i.e. five HBM round
     trips of the [B,256,N,N] activation per residual block.  Here a 3x3 trunk convolution of an fp16 net is ONE kernel,
-    `elfnet_conv3x3_f16` (elf_amd/csrc/net_conv.hip): Composable Kernel's implicit-GEMM main loop with the tile configuration MIOpen's
-    tuned database picks for this shape, and our functor in its epilogue: relu(conv + b) for the lower conv of a block,
-    relu(conv + b + skip) for the upper.  Nothing passes over the activation a second time.
+    `elfnet_conv3x3_f16`: relu(conv + b) for the lower conv of a block, relu(conv + b + skip) for the upper, and nothing passes over
+    the activation a second time.  Behind it are two main loops with one epilogue sequence and the same output bits: algo 1, the
+    hand-written 256 x 256 x 64 LDS-DMA kernel (elf_amd/csrc/net_conv3x3.hip), where there are enough positions to fill the chip,
+    and algo 0, Composable Kernel's implicit GEMM with the tile configuration MIOpen's tuned database picks (elf_amd/csrc/
+    net_conv.hip), for small calls and for the channel counts algo 1 does not take (`_conv_algo`).
     Every other convolution (the 18-plane input conv, bf16 nets, a weight that is not channels_last) stays a bias-free PyTorch-ROCm
     op (MIOpen) followed by one in-place pass, `elfnet_bias_act_f16` / `_bf16` (elf_amd/csrc/net_epilogue.hip).
     (PyTorch's own fused MIOpen ops, miopen_convolution_relu / miopen_convolution_add_relu, were measured and rejected: for
@@ -170,7 +172,14 @@ class FusedInferenceNet:
     Same function as PolicyValueNet.forward (src_py/elfgames/go/df_model3.py:62-110,224-313) up to fp16 rounding: the conv result
     is rounded to fp16 once and the epilogue once, where the eager sequence rounds after every kernel."""
 
-    conv_algo = 0   # elfnet_conv3x3_f16's algo: 0 = MIOpen's tile configuration (DESIGN.md section 3 has the probe that chose it)
+    # elfnet_conv3x3_f16's algo.  None = by shape (_conv_algo); 0 or 1 pins one.  DESIGN.md section 3 has the probes.
+    conv_algo = None
+    # algo 1 from this many positions (rows * H * W) on.  The crossover measured on MI355X at 19 x 19 x 256 -> 256, us without /
+    # with skip (profiles/conv_native_probe.json): 80 rows, algo 0 56 / 55 against algo 1 56 / 60; 90 rows (32 490 positions) a tie,
+    # 60 / 58 against 57 / 61; 96 rows (34 656 positions) 74 / 74 against 57 / 60.  Algo 1 runs one 36-K-tile workgroup per 256
+    # positions, 55 to 60 us however few there are; algo 0's 256 x 128 tiles are two workgroups per 256 positions and start a
+    # second round over the 256 CUs above 128 * 256 positions, which is where it falls behind.
+    native_min_positions = 128 * 256 + 1
 
     def __init__(self, net):
         import ctypes as C
@@ -207,6 +216,12 @@ class FusedInferenceNet:
                 and cin % 8 == 0 and k % 8 == 0 and x.shape[1] == cin
                 and tuple(w.stride()) == (9 * cin, 1, 3 * cin, cin))
 
+    def _conv_algo(self, positions, cin, k):
+        """algo 1 where net_conv3x3.hip takes the shape (C a multiple of 64, K of 256) and measured faster, algo 0 elsewhere"""
+        if self.conv_algo is not None:
+            return self.conv_algo
+        return 1 if cin % 64 == 0 and k % 256 == 0 and positions >= self.native_min_positions else 0
+
     def _conv(self, x, c, res=None):
         if not self._fusable(x, c):
             y = torch.nn.functional.conv2d(x, c.weight, None, c.stride, c.padding)
@@ -221,7 +236,7 @@ class FusedInferenceNet:
         y = torch.empty((n, k, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
         self.check(self.L.elfnet_conv3x3_f16(C.c_void_p(x.data_ptr()), C.c_void_p(c.weight.data_ptr()), C.c_void_p(c.bias.data_ptr()),
                                              C.c_void_p(res.data_ptr()) if res is not None else None, C.c_void_p(y.data_ptr()),
-                                             n, h, w, cin, k, 1, self.conv_algo,
+                                             n, h, w, cin, k, 1, self._conv_algo(n * h * w, cin, k),
                                              C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
         return y
 

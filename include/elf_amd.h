@@ -664,15 +664,17 @@ int elfrec_quantise_policy(int board_size, const int32_t* coord, const float* pr
 int elfnet_bias_act_f16(void* x, const void* bias, const void* res, int64_t rows, int channels, int relu, void* stream);
 /* the same pass for a bfloat16 activation (round to nearest even) */
 int elfnet_bias_act_bf16(void* x, const void* bias, const void* res, int64_t rows, int channels, int relu, void* stream);
-/* The trunk convolution with that epilogue inside it (elf_amd/csrc/net_conv.hip): one kernel, no second pass over y.
+/* The trunk convolution with that epilogue inside it (elf_amd/csrc/net_conv.hip, net_conv3x3.hip): one kernel, no second pass over y.
  * y = relu?(conv3x3_same(x, w) + bias (+ res)), fp16 NHWC in, fp16 NHWC out, fp32 accumulation.
  *   x [rows,H,W,C], w [K,3,3,C] (a channels_last torch weight as it lies in memory), bias [K], res/y [rows,H,W,K];
- *   res may be NULL; y must not alias x or res.  algo: 0 = the tile configuration MIOpen's tuned database picks for the
- *   2048 x 19 x 19 x 256 trunk shape, 1 = Composable Kernel's V3 pipeline (128 x 128 x 64 tile, another accumulation order).
+ *   res may be NULL; y must not alias x or res.  algo: 0 = Composable Kernel's implicit GEMM with the tile configuration
+ *   MIOpen's tuned database picks for the 2048 x 19 x 19 x 256 trunk shape, 1 = the hand-written 256 x 256 x 64 LDS-DMA kernel, which
+ *   takes c % 64 == 0 and k % 256 == 0 only, keeps algo 0's accumulation order (the same output bits) and is the faster one from
+ *   about 33 000 positions (rows * H * W) on.
  * Rounding: the fp32 accumulator is rounded to fp16 (as a convolution that stores y does), then bias, res and the ReLU are applied
  * in fp32 in elfnet_bias_act_f16's order and the result is rounded once more: conv + elfnet_bias_act_f16, without the round trip.
  * ELFGO_E_BADARG -- and nothing is launched -- for a null x / w / bias / y, pointers that are not 16-B aligned, c % 8 or k % 8 != 0,
- * y == x or y == res, an unknown algo, a tensor of 2^31 bytes or more, or a shape the kernel's own support check refuses.
+ * y == x or y == res, an unknown algo, a tensor of 2^31 bytes or more, or a shape the chosen kernel does not take.
  * Runs on the device that owns x; allocates nothing and waits for nothing (it can be captured into a HIP graph). */
 int elfnet_conv3x3_f16(const void* x, const void* w, const void* bias, const void* res, void* y,
                        int64_t rows, int h, int wd, int c, int k, int relu, int algo, void* stream);

@@ -1,11 +1,14 @@
 """Times ONE trunk convolution of the benchmark net (rows = 2048, 19 x 19, 256 -> 256, fp16 NHWC), with and without the skip:
-    fused0 / fused1   elfnet_conv3x3_f16 with algo 0 / 1 (bias, skip and ReLU in the convolution's epilogue)
+    fused0 / fused1   elfnet_conv3x3_f16 with algo 0 (CK's main loop) / 1 (the hand-written kernel of net_conv3x3.hip); bias, skip
+                      and ReLU in the convolution's epilogue
     pair              what ran before: F.conv2d (MIOpen) followed by elfnet_bias_act_f16
 HIP events around `--launches` back-to-back launches after a warm-up, `--repeats` times; mean / min / max of the repeats in µs per
 convolution.  One process; run it under a time limit:
-    timeout -k 10 300 python tools/conv_probe.py [--algos 0,1] [--out profiles/conv_fused_probe.json]
+    timeout -k 10 300 python tools/conv_probe.py [--algos 0,1] [--rows 2048] [--out profiles/conv_fused_probe.json]
+For a counter pass (rocprofv3 --pmc, which replays every dispatch once per counter group) run one variant and nothing else:
+    ... python tools/conv_probe.py --algos 1 --no-pair --launches 4 --warmup 1 --repeats 1 --out /dev/null
 A variant the library refuses (a non-zero status, e.g. CK's IsSupportedArgument saying no on this device) is recorded with its
-status and not timed.  FusedInferenceNet.conv_algo changes to 1 only if algo 1's mean is below algo 0's by more than the spread
+status and not timed.  FusedInferenceNet routes to algo 1 only where its mean is below algo 0's by more than the spread
 (max - min over the repeats) of either."""
 import argparse
 import ctypes as C
@@ -27,6 +30,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--algos", default="0,1")
+    ap.add_argument("--no-pair", action="store_true", help="leave F.conv2d + elfnet_bias_act_f16 out: only the fused variants run")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "conv_fused_probe.json"))
     a = ap.parse_args()
     # the pair runs the convolution MIOpen's tuned database names for this shape, as the benchmark does: the committed entries go
@@ -83,11 +87,13 @@ def main():
                device=torch.cuda.get_device_name(0), method="HIP events around back-to-back launches, µs per convolution")
     with torch.no_grad():
         for skip, rr in (("noskip", None), ("skip", r)):
-            res["pair_" + skip] = timed(pair(rr))
+            if not a.no_pair:
+                res["pair_" + skip] = timed(pair(rr))
             for algo in [int(v) for v in a.algos.split(",") if v != ""]:
                 res["fused%d_%s" % (algo, skip)] = timed(fused(algo, rr))
                 print(skip, "algo", algo, res["fused%d_%s" % (algo, skip)], flush=True)
-            print(skip, "pair", res["pair_" + skip], flush=True)
+            if not a.no_pair:
+                print(skip, "pair", res["pair_" + skip], flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)

@@ -21,7 +21,7 @@ seen = {}
 out = {n: {"prologue": [], "after_net": []} for n in names}
 for i, r in enumerate(rows):
     nm = r["Kernel_Name"]
-    if "kernel_grouped_conv" in nm or "igemm" in nm or "naive_conv" in nm:
+    if "kernel_grouped_conv" in nm or "k_conv3x3" in nm or "igemm" in nm or "naive_conv" in nm:
         last_conv = i
         continue
     for n in names:
