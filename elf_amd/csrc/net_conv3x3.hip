@@ -7,9 +7,10 @@
 //             activation byte is staged once for every output channel.  512 threads, 8 waves as 2 (positions) x 4 (channels), each
 //             owning 128 positions x 64 channels = 4 x 2 MFMA tiles = 128 accumulator registers.  One workgroup per CU.
 //   staging   LDS-DMA (global_load_lds_dwordx4) straight into two 64-KiB LDS buffers (activation tile, weight tile: 256 rows of
-//             128 B each); the eight pieces of K tile t+1 go out behind the one barrier of K tile t, between the MFMAs of its first
-//             two 16-deep steps (their execution hides the issue), and land behind the rest.  One vmcnt(0) + barrier per K tile.
-//             Every staged piece is a full aligned 128-B line: 8 lanes per row.
+//             128 B each), in half-tiles of 128 rows of one operand, two 8-row pieces per wave; four half-tiles stay in flight
+//             across the loop's barriers, which are bare s_barriers behind counted vmcnt waits (the comment at the main loop has
+//             the counts).  vmcnt(0) only once the last half-tile is on its way.  Every staged piece is a full aligned 128-B
+//             line: 8 lanes per row.
 //   halo      a staging lane decodes its four rows once (position -> n, h, w) and keeps a 9-bit tap mask and a byte offset; for an
 //             off-board tap, and for a row at or beyond M, its source address is a zero-filled line in global memory.  LDS is never
 //             zeroed by a second path.
@@ -57,22 +58,44 @@ __device__ __forceinline__ void stage16(const char* src, char* lds_base) {
   __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)lds_base, 16, 0, 0);
 }
 
+// the counted wait of the main loop: at most kN of this wave's LDS-DMA loads (two per staged half-tile, in issue order) are
+// still in flight behind it; with kLgkm the wave's own ds_reads have retired too
+template <int kN, bool kLgkm>
+__device__ __forceinline__ void wait_staged() {
+  if constexpr (kLgkm) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(kN) : "memory");
+  else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kN) : "memory");
+}
+// the loop's barrier is the bare instruction: __syncthreads() would fence, and the fence waits for every LDS-DMA in flight
+__device__ __forceinline__ void raw_barrier() {
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+template <int kV> struct Mode { static constexpr int v = kV; };
+
 template <bool kHasRes>
 __global__ __launch_bounds__(kThreads, 2) void k_conv3x3_f16(const char* __restrict__ x, const char* __restrict__ w,
                                                              const _Float16* __restrict__ bias, const _Float16* __restrict__ res,
                                                              _Float16* __restrict__ y, int M, int H, int W, int Cin, int K, int relu) {
   __shared__ __attribute__((aligned(128))) char lds[kLdsBytes];   // ALL of the kernel's LDS: one array
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int tile = blockIdx.x, kbase = blockIdx.y * kTileN;
+  // wv through readfirstlane: the compiler then keeps everything that depends on the wave alone (LDS destinations, weight rows)
+  // in scalar registers, off the vector pipe the MFMAs issue through
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kbase = blockIdx.y * kTileN;
+  const int tile = blockIdx.x;
 
-  // ---- staging: wave wv writes the 8-row pieces i * 8 + wv (i = 0..3) of both operands; a lane is row (lane >> 3) of its
-  // piece and LDS slot (lane & 7) of that row
+  // ---- staging.  A K tile is staged as four half-tiles of 128 rows, in the order the fragment reads need them:
+  //   Xa  activation rows of the waves' position sub-tiles 0 and 1 (rows wm * 128 + 0..63)      Wa  weight rows of channel
+  //   Xb  ... of sub-tiles 2 and 3 (rows wm * 128 + 64..127)                                    sub-tile 0 (wn * 64 + 0..31)
+  //                                                                                             Wb  ... of sub-tile 1 (+ 32..63)
+  // Every wave issues two 8-row pieces of each half-tile (i = 0, 1): a lane is row (lane >> 3) of its piece and LDS slot
+  // (lane & 7) of that row.  Index hf * 2 + i below.
   uint32_t xoff[4], woff[4], xmask[4];
   const unsigned char* zsrc = g_zero_line + (lane & 7) * 16;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = (i * 8 + wv) * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((r >> 1) & 7);
+  for (int j = 0; j < 4; ++j) {
+    const int hf = j >> 1, i = j & 1;
+    const int r = i * 128 + hf * 64 + wv * 8 + (lane >> 3);
     const int p = tile * kTileM + r;
     uint32_t m = 0;
     if (p < M) {
@@ -83,20 +106,26 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv3x3_f16(const char* __restr
         if ((unsigned)(hh + dy) < (unsigned)H && (unsigned)(ww + dx) < (unsigned)W) m |= 1u << tap;
       }
     }
-    xmask[i] = m;
-    xoff[i] = (uint32_t)p * (uint32_t)(Cin * 2) + chunk * 16;            // below 2^31 wherever it is used (p < M)
-    woff[i] = (uint32_t)(kbase + r) * (uint32_t)(9 * Cin * 2) + chunk * 16;
+    xmask[j] = m;
+    xoff[j] = (uint32_t)p * (uint32_t)(Cin * 2) + (((lane & 7) ^ ((r >> 1) & 7)) << 4);   // below 2^31 wherever it is used (p < M)
+    const int rw = (i * 2 + (wv >> 2)) * 64 + hf * 32 + (wv & 3) * 8 + (lane >> 3);
+    woff[j] = (uint32_t)(kbase + rw) * (uint32_t)(9 * Cin * 2) + (((lane & 7) ^ ((rw >> 1) & 7)) << 4);
   }
-  // piece j of K tile (tap, kc) into buffer buf: j = 0..3 the activation rows, 4..7 the weight rows
-  auto piece = [&](int j, int tap, int kc, int buf) {
-    char* dst = lds + buf * kBufBytes + wv * 1024;
-    if (j < 4) {
-      const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
-      const uint32_t d = (uint32_t)((dy * W + dx) * Cin * 2 + kc * 128);
-      stage16(((xmask[j] >> tap) & 1) ? x + (uint32_t)(xoff[j] + d) : (const char*)zsrc, dst + j * 8192);
-    } else {
-      stage16(w + (uint32_t)(woff[j - 4] + (uint32_t)(tap * Cin * 2 + kc * 128)), dst + kOperandBytes + (j - 4) * 8192);
-    }
+  // the two pieces of one half-tile of K tile (tap, kc) into buffer buf
+  auto stage_x = [&](int hf, int tap, int kc, int buf) {
+    const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
+    const uint32_t d = (uint32_t)((dy * W + dx) * Cin * 2 + kc * 128);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      stage16(((xmask[hf * 2 + i] >> tap) & 1) ? x + (uint32_t)(xoff[hf * 2 + i] + d) : (const char*)zsrc,
+              lds + buf * kBufBytes + (i * 128 + hf * 64 + wv * 8) * 128);
+  };
+  auto stage_w = [&](int hf, int tap, int kc, int buf) {
+    const uint32_t d = (uint32_t)(tap * Cin * 2 + kc * 128);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      stage16(w + (uint32_t)(woff[hf * 2 + i] + d),
+              lds + buf * kBufBytes + kOperandBytes + ((i * 2 + (wv >> 2)) * 64 + hf * 32 + (wv & 3) * 8) * 128);
   };
 
   // ---- fragments: lane (fr = lane & 31, fh = lane >> 5) holds row fr of a 32-row MFMA tile and 8 of the 16 k of one MFMA
@@ -110,6 +139,8 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv3x3_f16(const char* __restr
   int cs[4];
 #pragma unroll
   for (int kk = 0; kk < 4; ++kk) cs[kk] = (((kk >> 1) * 4 + fh * 2 + (kk & 1)) ^ sw) << 4;
+  auto ldx = [&](const char* b, int mt, int kk) { return *(const half8*)(b + xrow + mt * 4096 + cs[kk]); };
+  auto ldw = [&](const char* b, int nt, int kk) { return *(const half8*)(b + wrow + nt * 4096 + cs[kk]); };
 
   floatx16 acc[4][2];
 #pragma unroll
@@ -119,56 +150,97 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv3x3_f16(const char* __restr
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[mt][nt][e] = 0.0f;
 
-  const int kchunks = Cin >> 6, ktiles = 9 * kchunks;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) piece(j, 0, 0, 0);
-  int tap = 0, kc = 0;
-  for (int t = 0; t < ktiles; ++t) {
-    // K tile t has landed (this wave's pieces by the count, the others' by the barrier), and every wave is done reading the
-    // other buffer (K tile t - 1)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int ntap = tap, nkc = kc + 1;
-    if (nkc == kchunks) { nkc = 0; ++ntap; }
-    const bool more = t + 1 < ktiles;
-    // K tile t + 1: its eight pieces go out in the first two 16-deep steps, two behind every four MFMAs
-    const int nbuf = (t + 1) & 1;
-    tap = ntap; kc = nkc;
-    const char* b = lds + (t & 1) * kBufBytes;
-    // the six fragments of 16-deep step kk + 1 are issued in front of the eight MFMAs of step kk and arrive behind them
-    half8 xf[2][4], wf[2][2];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) wf[0][nt] = *(const half8*)(b + wrow + nt * 4096 + cs[0]);
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) xf[0][mt] = *(const half8*)(b + xrow + mt * 4096 + cs[0]);
+  // ---- main loop.  K tile t lives in LDS buffer t & 1 and is spent in two halves of the wave's 128 x 64, each a load segment and
+  // an MFMA segment with a bare s_barrier behind every segment:
+  //   L1  reads Xa, Wa, Wb of K tile t (16 ds_read_b128)   stages Xb(t + 1)                 ends: vmcnt(8) lgkmcnt(0) barrier
+  //   M1  16 MFMAs: acc[0..1][0..1] over the whole BK = 64                                  ends: barrier
+  //   L2  reads Xb(t) over Xa (8 ds_read_b128)             stages Xa, Wa, Wb of t + 2       ends: vmcnt(8) lgkmcnt(0) barrier
+  //   M2  16 MFMAs: acc[2..3][0..1]                                                         ends: barrier
+  // Every accumulator still takes its K in ascending order.  Waves 4..7 (the second wave of every SIMD) pass one barrier more
+  // before the loop and waves 0..3 one more behind it, so the two waves of a SIMD run one segment apart: one issues its MFMAs while
+  // the other reads, stages and waits, and the matrix pipe does not stand still while both fetch.
+  // By the counts (a wave's loads retire in issue order, two per half-tile, half-tiles in the order Xa Wa Wb Xb of a K tile), for
+  // waves that may be one barrier apart:
+  //   landed   what a load segment reads was waited for, by every wave, in its load segment before: there are two barriers
+  //            between a wave's wait and its own next load segment, so at least one between anybody's wait and anybody's read.
+  //            L1(t)'s wait is for Xb(t), read in L2(t): the wave has issued up to Xb(t+1), that is Xa, Wa, Wb, Xb of t + 1 behind
+  //            it: 4 half-tiles, vmcnt(8).  L2(t)'s wait is for Xa, Wa, Wb of t + 1, read in L1(t+1): issued up to Wb(t+2), that
+  //            is Xb(t+1), Xa, Wa, Wb of t + 2 behind them: vmcnt(8) again.
+  //   free     a half-tile is restaged one load segment after the one that read it (lgkmcnt(0) in front of that one's barrier), two
+  //            barriers later for the wave itself and at least one for a wave that runs behind: Xb(t-1), read in L2(t-1), is
+  //            restaged in L1(t); Xa, Wa, Wb of t, read in L1(t), are restaged in L2(t).
+  // So four half-tiles (64 KiB) are in flight across every barrier, each for a whole K tile of MFMAs, and the loop never drains
+  // the queue; the last two K tiles issue nothing new and count it down (8, 2, then 0 in the last K tile's L1).
+  const int kchunks = Cin >> 6, ktiles = 9 * kchunks;   // at least 9
+  half8 xf[2][4], wa[4], wb[4];
+  int tap1 = 0, kc1 = 1, tap2 = 0, kc2 = 2;             // K tiles t + 1 and t + 2
+  if (kchunks == 1) { tap1 = 1; kc1 = 0; tap2 = 2; kc2 = 0; }
+  else if (kchunks == 2) { tap2 = 1; kc2 = 0; }
+  stage_x(0, 0, 0, 0); stage_w(0, 0, 0, 0); stage_w(1, 0, 0, 0); stage_x(1, 0, 0, 0);
+  stage_x(0, tap1, kc1, 1); stage_w(0, tap1, kc1, 1); stage_w(1, tap1, kc1, 1);
+  wait_staged<8, false>();      // Xa, Wa, Wb of K tile 0; behind them Xb(0), Xa(1), Wa(1), Wb(1)
+  raw_barrier();
+
+  // mode 0: a K tile with two more behind it; 1: the last but one; 2: the last
+  auto ktile = [&](auto mode, int t) {
+    constexpr int kMode = decltype(mode)::v;
+    const int cur = t & 1, nxt = cur ^ 1;
+    const char* b = lds + cur * kBufBytes;
+    // L1
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-      const int cur = kk & 1, nxt = cur ^ 1;
-      if (kk < 3) {
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) wf[nxt][nt] = *(const half8*)(b + wrow + nt * 4096 + cs[kk + 1]);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) xf[nxt][mt] = *(const half8*)(b + xrow + mt * 4096 + cs[kk + 1]);
-      }
-      __builtin_amdgcn_sched_barrier(0);   // the reads stay in front of the MFMAs they hide behind (the wait is a counted lgkmcnt)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[cur][nt], xf[cur][mt], acc[mt][nt], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (more && kk < 2) { piece(4 * kk, ntap, nkc, nbuf); piece(4 * kk + 1, ntap, nkc, nbuf); }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int mt = 2; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[cur][nt], xf[cur][mt], acc[mt][nt], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (more && kk < 2) { piece(4 * kk + 2, ntap, nkc, nbuf); piece(4 * kk + 3, ntap, nkc, nbuf); }
-      __builtin_amdgcn_sched_barrier(0);
+      wa[kk] = ldw(b, 0, kk);
+      xf[0][kk] = ldx(b, 0, kk);
+      xf[1][kk] = ldx(b, 1, kk);
+      wb[kk] = ldw(b, 1, kk);
     }
+    if constexpr (kMode <= 1) stage_x(1, tap1, kc1, nxt);
+    wait_staged<kMode == 2 ? 0 : 8, true>();
+    raw_barrier();
+    // M1
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[kk], xf[0][kk], acc[0][0], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[kk], xf[1][kk], acc[1][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[kk], xf[0][kk], acc[0][1], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[kk], xf[1][kk], acc[1][1], 0, 0, 0);
+    }
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);
+    raw_barrier();
+    // L2
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      xf[0][kk] = ldx(b, 2, kk);
+      xf[1][kk] = ldx(b, 3, kk);
+    }
+    if constexpr (kMode == 0) { stage_x(0, tap2, kc2, cur); stage_w(0, tap2, kc2, cur); stage_w(1, tap2, kc2, cur); }
+    wait_staged<kMode == 0 ? 8 : kMode == 1 ? 2 : 0, true>();
+    raw_barrier();
+    // M2
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      acc[2][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[kk], xf[0][kk], acc[2][0], 0, 0, 0);
+      acc[3][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[kk], xf[1][kk], acc[3][0], 0, 0, 0);
+      acc[2][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[kk], xf[0][kk], acc[2][1], 0, 0, 0);
+      acc[3][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[kk], xf[1][kk], acc[3][1], 0, 0, 0);
+    }
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);
+    raw_barrier();
+  };
+  const int late = __builtin_amdgcn_readfirstlane(tid >> 8);   // waves 4..7: the second wave of every SIMD
+  if (late) raw_barrier();
+  for (int t = 0; t < ktiles - 2; ++t) {
+    ktile(Mode<0>{}, t);
+    tap1 = tap2; kc1 = kc2;
+    if (++kc2 == kchunks) { kc2 = 0; ++tap2; }
   }
+  ktile(Mode<1>{}, ktiles - 2);
+  ktile(Mode<2>{}, ktiles - 1);
+  if (!late) raw_barrier();
 
   // ---- epilogue.  D = W X^T: the lane's column is position fr of the tile, its register e is channel (e & 3) + 8 (e >> 2) + 4 fh.
   // C tile in LDS: [256 positions][256 channels] fp16, the 16-B chunk q of position p at chunk q ^ (p & 31).

@@ -175,10 +175,11 @@ class FusedInferenceNet:
     # elfnet_conv3x3_f16's algo.  None = by shape (_conv_algo); 0 or 1 pins one.  DESIGN.md section 3 has the probes.
     conv_algo = None
     # algo 1 from this many positions (rows * H * W) on.  The crossover measured on MI355X at 19 x 19 x 256 -> 256, us without /
-    # with skip (profiles/conv_native_probe.json): 80 rows, algo 0 56 / 55 against algo 1 56 / 60; 90 rows (32 490 positions) a tie,
-    # 60 / 58 against 57 / 61; 96 rows (34 656 positions) 74 / 74 against 57 / 60.  Algo 1 runs one 36-K-tile workgroup per 256
-    # positions, 55 to 60 us however few there are; algo 0's 256 x 128 tiles are two workgroups per 256 positions and start a
-    # second round over the 256 CUs above 128 * 256 positions, which is where it falls behind.
+    # with skip (profiles/conv_pipeline_probe.json): 80 rows, algo 0 55 / 54 against algo 1 53 / 54, inside the spread; 90 rows
+    # (32 490 positions) 59 / 57 against 53 / 54, beyond the spread with skip only; 96 rows (34 656 positions) 73 / 73 against
+    # 53 / 54.  Algo 1 runs one 36-K-tile workgroup per 256 positions, 53 to 54 us however few there are; algo 0's 256 x 128 tiles
+    # are two workgroups per 256 positions and start a second round over the 256 CUs above 128 * 256 positions, which is where it
+    # falls behind.
     native_min_positions = 128 * 256 + 1
 
     def __init__(self, net):
