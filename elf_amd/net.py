@@ -170,7 +170,9 @@ class FusedInferenceNet:
     (PyTorch's own fused MIOpen ops, miopen_convolution_relu / miopen_convolution_add_relu, were measured and rejected: for
     fp16 channels_last MIOpen's fusion plan falls back to naive kernels, > 10x slower.)
     Same function as PolicyValueNet.forward (src_py/elfgames/go/df_model3.py:62-110,224-313) up to fp16 rounding: the conv result
-    is rounded to fp16 once and the epilogue once, where the eager sequence rounds after every kernel."""
+    is rounded to fp16 once and the epilogue once, where the eager sequence rounds after every kernel.
+    Unlike the eager net, a NaN in front of a ReLU becomes 0 (the kernels' max is fmaxf, torch.relu keeps the NaN): a diverged
+    activation does not show as NaN in pi or V."""
 
     # elfnet_conv3x3_f16's algo.  None = by shape (_conv_algo); 0 or 1 pins one.  DESIGN.md section 3 has the probes.
     conv_algo = None

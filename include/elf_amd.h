@@ -660,7 +660,9 @@ int elfrec_quantise_policy(int board_size, const int32_t* coord, const float* pr
  * relu(bn(conv(x))) and relu(bn(conv(h)) + x) with eval BatchNorm folded into the conv).
  *   x[r][c] <- act(x[r][c] + bias[c] + (res ? res[r][c] : 0)),  x/res fp16 [rows][channels] contiguous
  *   (channels % 8 == 0, 16-B aligned), bias fp16 [channels] or NULL, relu != 0 applies max(.,0).
- * fp32 arithmetic, one rounding to fp16. */
+ * fp32 arithmetic in the order (x + bias) + res, one rounding to fp16 (to nearest even); a sum beyond the largest finite value
+ * saturates to Inf, subnormals are kept.  The max is fmaxf: a NaN before the ReLU comes out as +0 (torch.relu would keep it), and
+ * -0 as a zero that compares equal to 0 (fmaxf does not promise its sign); without the ReLU NaN, Inf and -0 pass through. */
 int elfnet_bias_act_f16(void* x, const void* bias, const void* res, int64_t rows, int channels, int relu, void* stream);
 /* the same pass for a bfloat16 activation (round to nearest even) */
 int elfnet_bias_act_bf16(void* x, const void* bias, const void* res, int64_t rows, int channels, int relu, void* stream);
@@ -673,6 +675,8 @@ int elfnet_bias_act_bf16(void* x, const void* bias, const void* res, int64_t row
  *   about 33 000 positions (rows * H * W) on.
  * Rounding: the fp32 accumulator is rounded to fp16 (as a convolution that stores y does), then bias, res and the ReLU are applied
  * in fp32 in elfnet_bias_act_f16's order and the result is rounded once more: conv + elfnet_bias_act_f16, without the round trip.
+ * Both roundings saturate to Inf (an accumulator beyond 65 504 is Inf before the bias is added), and the ReLU is that pass's fmaxf:
+ * a NaN before it comes out as +0, and -0 as a zero of either sign; without the ReLU they pass through.
  * ELFGO_E_BADARG -- and nothing is launched -- for a null x / w / bias / y, pointers that are not 16-B aligned, c % 8 or k % 8 != 0,
  * y == x or y == res, an unknown algo, a tensor of 2^31 bytes or more, or a shape the chosen kernel does not take.
  * Runs on the device that owns x; allocates nothing and waits for nothing (it can be captured into a HIP graph). */
