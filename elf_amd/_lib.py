@@ -149,6 +149,9 @@ SIGNATURES = {
     "elfnet_bias_act_f16": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
     "elfnet_bias_act_bf16": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
     "elfnet_conv3x3_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp]),
+    "elfnet_conv3x3_in_f16": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
+    "elfnet_heads_workspace": (_sz, [_i64, _i, _i]),
+    "elfnet_heads_f16": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "elfgo_set_device": (_i, [_i]),
     "elfgo_get_device": (_i, [C.POINTER(_i)]),
     "elfgo_mem_info": (_i, [_i, C.POINTER(_sz), C.POINTER(_sz)]),
@@ -162,6 +165,12 @@ SIGNATURES = {
     "elfgo_error_string": (C.c_char_p, [_i]),
     "elfgo_version": (C.c_char_p, []),
 }
+
+
+class ElfNetHeads(C.Structure):
+    """include/elf_amd.h's ElfNetHeads: the head weights elfnet_heads_f16 reads (fp16 device pointers)"""
+    _fields_ = [(n, _vp) for n in ("pconv_w", "pconv_b", "vconv_w", "vconv_b", "pi_w", "pi_b", "v1_w", "v1_b", "v2_w", "v2_b")] + \
+               [("channels", C.c_int32), ("value_hidden", C.c_int32)]
 
 
 def lib():

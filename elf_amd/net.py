@@ -258,3 +258,92 @@ class FusedInferenceNet:
         v = torch.relu(net.value_linear1(net.value_final_conv(h).reshape(-1, net.d)))
         v = torch.tanh(net.value_linear2(v)).float().reshape(-1)
         return dict(pi=pi, V=v)
+
+
+class NativeInferenceNet(FusedInferenceNet):
+    """A BN-folded fp16 channels_last PolicyValueNet from feature rows to pi / V on this library's kernels only:
+
+        elfnet_conv3x3_in_f16  ->  2 x num_block elfnet_conv3x3_f16 (FusedInferenceNet's trunk, same `_conv_algo` routing)  ->  elfnet_heads_f16
+
+    No MIOpen convolution, no BLAS GEMM, no PyTorch softmax or tanh inside __call__: no find step on a cold database, no solver
+    choice behind the output bits, three launches instead of about fifteen around the trunk.  Same constructor checks and
+    {"s"} -> {"pi", "V"} contract as FusedInferenceNet, but fp16 only, and a net any part of which these kernels do not take is
+    refused with ValueError: there is no mixed path.
+    Same function as FusedInferenceNet up to rounding, with FEWER roundings: the heads run in fp32 from the trunk activation to pi
+    and V (elf_amd/csrc/net_io.hip), where the eager ops round to fp16 after the head convolutions and after every Linear."""
+
+    def __init__(self, net):
+        super().__init__(net)
+        if self.dtype != torch.float16:
+            raise ValueError("NativeInferenceNet needs an fp16 net")
+        from ._lib import ElfNetHeads
+
+        def conv_of(seq, what, ksize, pad):
+            c = seq[0]
+            if not (isinstance(c, nn.Conv2d) and tuple(c.kernel_size) == (ksize, ksize) and tuple(c.stride) == (1, 1)
+                    and tuple(c.padding) == (pad, pad) and tuple(c.dilation) == (1, 1) and c.groups == 1 and c.bias is not None):
+                raise ValueError("NativeInferenceNet: %s is not a plain %dx%d convolution with a bias" % (what, ksize, ksize))
+            return c
+
+        first = conv_of(net.init_conv, "init_conv", 3, 1)
+        k, cin = first.weight.shape[0], first.weight.shape[1]
+        if cin % 2 or not 2 <= cin <= 32 or k % 32 or tuple(first.weight.stride()) != (9 * cin, 1, 3 * cin, cin):
+            raise ValueError("NativeInferenceNet: elfnet_conv3x3_in_f16 takes an even number of 2 .. 32 input planes, a multiple of "
+                             "32 output channels and a channels_last weight")
+        dim = k
+        for i, b in enumerate(net.resnet):
+            for name in ("lower", "upper"):
+                c = conv_of(getattr(b, name), "resnet.%d.%s" % (i, name), 3, 1)
+                w = c.weight
+                if tuple(w.shape[:2]) != (dim, dim) or dim % 8 or tuple(w.stride()) != (9 * dim, 1, 3 * dim, dim):
+                    raise ValueError("NativeInferenceNet: resnet.%d.%s is not a channels_last %d -> %d convolution" % (i, name, dim, dim))
+        pc, vc = conv_of(net.pi_final_conv, "pi_final_conv", 1, 0), conv_of(net.value_final_conv, "value_final_conv", 1, 0)
+        d = net.d
+        vh = net.value_linear1.out_features
+        shapes = ((pc.weight, (2, dim, 1, 1)), (vc.weight, (1, dim, 1, 1)), (net.pi_linear.weight, (d + 1, 2 * d)),
+                  (net.value_linear1.weight, (vh, d)), (net.value_linear2.weight, (1, vh)))
+        for w, shape in shapes:
+            if tuple(w.shape) != shape:
+                raise ValueError("NativeInferenceNet: a head weight of shape %s where %s is expected" % (tuple(w.shape), shape))
+        if dim % 8 or any(lin.bias is None for lin in (net.pi_linear, net.value_linear1, net.value_linear2)):
+            raise ValueError("NativeInferenceNet: the heads need channels % 8 == 0 and Linear layers with a bias")
+        # the tensors elfnet_heads_f16 reads, dense ([2,C,1,1] is [2][C] in memory in either memory format once made contiguous);
+        # kept alive here, their addresses in the struct
+        flat = lambda t: t.detach().reshape(t.shape[0], -1).contiguous()
+        self._head_tensors = [flat(pc.weight), pc.bias.detach().contiguous(), flat(vc.weight), vc.bias.detach().contiguous(),
+                              flat(net.pi_linear.weight), net.pi_linear.bias.detach().contiguous(),
+                              flat(net.value_linear1.weight), net.value_linear1.bias.detach().contiguous(),
+                              flat(net.value_linear2.weight), net.value_linear2.bias.detach().contiguous()]
+        if any(t.dtype != torch.float16 or not t.is_cuda for t in self._head_tensors + [first.weight, first.bias]):
+            raise ValueError("NativeInferenceNet needs every parameter in fp16 on the GPU")
+        self.heads = ElfNetHeads(*[t.data_ptr() for t in self._head_tensors], dim, vh)
+        self.dim = dim
+
+    def _conv(self, x, c, res=None):
+        if not self._fusable(x, c):   # the constructor has checked the weights: this is a wrong input shape
+            raise ValueError("NativeInferenceNet: a convolution elfnet_conv3x3_f16 does not take")
+        return super()._conv(x, c, res)
+
+    @torch.no_grad()
+    def __call__(self, batch):
+        net, C, L = self.net, self.C, self.L
+        s = batch["s"] if isinstance(batch, dict) else batch
+        if s.dtype != self.dtype:
+            s = s.to(self.dtype)
+        s = s.contiguous(memory_format=torch.channels_last)   # no-op for SelfPlay(feature_format="f16_nhwc")
+        n, cin, hh, ww = s.shape
+        if cin != self.first.weight.shape[1] or hh * ww != net.d:
+            raise ValueError("NativeInferenceNet: input of shape %s" % (tuple(s.shape),))
+        st = C.c_void_p(torch.cuda.current_stream(s.device).cuda_stream)
+        h = torch.empty((n, self.dim, hh, ww), dtype=s.dtype, device=s.device, memory_format=torch.channels_last)
+        self.check(L.elfnet_conv3x3_in_f16(C.c_void_p(s.data_ptr()), C.c_void_p(self.first.weight.data_ptr()),
+                                           C.c_void_p(self.first.bias.data_ptr()), C.c_void_p(h.data_ptr()), n, hh, ww, cin, self.dim, 1, st))
+        for lo, up in self.blocks:
+            h = self._conv(self._conv(h, lo), up, res=h)
+        pi = torch.empty((n, net.d + 1), dtype=torch.float32, device=s.device)
+        v = torch.empty((n,), dtype=torch.float32, device=s.device)
+        ws_bytes = L.elfnet_heads_workspace(n, hh, ww)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=s.device)
+        self.check(L.elfnet_heads_f16(C.c_void_p(h.data_ptr()), C.byref(self.heads), n, hh, ww, C.c_void_p(pi.data_ptr()), net.d + 1,
+                                      C.c_void_p(v.data_ptr()), None, C.c_void_p(ws.data_ptr()), ws_bytes, st))
+        return dict(pi=pi, V=v)

@@ -683,6 +683,49 @@ int elfnet_bias_act_bf16(void* x, const void* bias, const void* res, int64_t row
 int elfnet_conv3x3_f16(const void* x, const void* w, const void* bias, const void* res, void* y,
                        int64_t rows, int h, int wd, int c, int k, int relu, int algo, void* stream);
 
+/* The two ends of the fp16 net on this library's kernels (elf_amd/csrc/net_io.hip).  A C host evaluates a BN-folded net as
+ *   elfnet_conv3x3_in_f16 (feature rows -> trunk activation), elfnet_conv3x3_f16 twice per residual block, elfnet_heads_f16
+ * with no other library in between: no find step, no solver choice, the same bits on every call.
+ *
+ * The input convolution: y = relu?(conv3x3_same(x, w) + bias), fp32 accumulation over the flattened (tap, channel) axis.
+ *   x fp16 [rows,H,W,C] -- for C = 18 exactly the rows ELFGO_FEAT_F16_NHWC writes (36 B per position; x needs 4-B alignment only),
+ *   w fp16 [K,3,3,C] (a channels_last torch weight as it lies in memory), bias fp16 [K], y fp16 [rows,H,W,K].
+ *   C even, 2 .. 32; K a multiple of 32.
+ * Rounding as elfnet_conv3x3_f16: the accumulator is rounded to fp16, bias and the ReLU (fmaxf) are applied in fp32, and the result
+ * is rounded once more.
+ * ELFGO_E_BADARG -- and nothing is launched -- for a null pointer, another c or k, y == x, a tensor of 2^31 bytes or more, or w /
+ * bias / y that are not 16-B aligned.  Runs on the device that owns x; allocates nothing and waits for nothing. */
+int elfnet_conv3x3_in_f16(const void* x, const void* w, const void* bias, void* y,
+                          int64_t rows, int h, int wd, int c, int k, int relu, void* stream);
+
+/* Both heads from the trunk activation act fp16 [rows,H,W,C], with d = H * W:
+ *   p[c][pos]  = relu(sum_i act[pos][i] * pconv_w[c][i] + pconv_b[c])         c = 0, 1
+ *   logits[j]  = sum_f pi_w[j][f] * p_flat[f] + pi_b[j],  p_flat[c * d + pos] = p[c][pos]   (torch's flattening of [B,2,H,W])
+ *   pi         = softmax(logits)                                               d + 1 entries
+ *   v0[pos]    = relu(sum_i act[pos][i] * vconv_w[i] + vconv_b)
+ *   v1         = relu(v1_w v0 + v1_b),   V = tanh(v2_w v1 + v2_b)
+ * The weights are fp16 as the folded modules hold them; ALL arithmetic is fp32 and nothing in between is rounded to fp16 (the eager
+ * net rounds after every op: this result differs from it by rounding only, and has fewer roundings).  pi, logits and value are fp32:
+ * what elfmcts_expand / elfsp_end_step take.  pi (and logits, if not NULL) rows are pi_stride floats apart; value is [rows].
+ * act is read once; the per-position head values go through `workspace` (elfnet_heads_workspace(rows, h, wd) bytes of device memory,
+ * > 0 and monotone in rows), which the call leaves in an unspecified state.  Two launches on `stream`, no atomics: repeated
+ * calls return the same bits.
+ * ELFGO_E_BADARG -- and nothing is launched -- for a null act / hd / pi / value / workspace or a null weight pointer, channels % 8
+ * != 0, value_hidden <= 0, workspace_bytes below elfnet_heads_workspace's, pi_stride < d + 1, act or the head-convolution weights
+ * not 16-B aligned, pi_w / pi / value / logits / workspace not 4-B aligned.  Allocates nothing and waits for nothing. */
+typedef struct ElfNetHeads {            /* fp16 device pointers */
+  const void *pconv_w, *pconv_b;        /* [2][C], [2]        pi_final_conv    */
+  const void *vconv_w, *vconv_b;        /* [1][C], [1]        value_final_conv */
+  const void *pi_w, *pi_b;              /* [d+1][2d], [d+1]   pi_linear        */
+  const void *v1_w, *v1_b;              /* [vh][d], [vh]      value_linear1    */
+  const void *v2_w, *v2_b;              /* [1][vh], [1]       value_linear2    */
+  int32_t channels, value_hidden;       /* C, vh */
+} ElfNetHeads;
+size_t elfnet_heads_workspace(int64_t rows, int h, int wd);
+int elfnet_heads_f16(const void* act, const ElfNetHeads* hd, int64_t rows, int h, int wd,
+                     float* pi, int64_t pi_stride, float* value, float* logits,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* convenience for callers without a HIP runtime of their own (tests, the pybind11/cgo/ctypes side); these act on the calling
  * thread's current device unless a device is named */
 int elfgo_set_device(int device);
