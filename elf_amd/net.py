@@ -270,7 +270,9 @@ class NativeInferenceNet(FusedInferenceNet):
     {"s"} -> {"pi", "V"} contract as FusedInferenceNet, but fp16 only, and a net any part of which these kernels do not take is
     refused with ValueError: there is no mixed path.
     Same function as FusedInferenceNet up to rounding, with FEWER roundings: the heads run in fp32 from the trunk activation to pi
-    and V (elf_amd/csrc/net_io.hip), where the eager ops round to fp16 after the head convolutions and after every Linear."""
+    and V (elf_amd/csrc/net_io.hip), where the eager ops round to fp16 after the head convolutions and after every Linear.
+    A row's pi and V do not depend on the batch it is evaluated in: every kernel sums a row in an order fixed by the shape of one
+    row, so one call, chunked_forward and row-by-row calls return the same bits (tests/test_gpu_net_native_io_edges.py, on an MI355X)."""
 
     def __init__(self, net):
         super().__init__(net)

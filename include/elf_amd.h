@@ -709,10 +709,18 @@ int elfnet_conv3x3_in_f16(const void* x, const void* w, const void* bias, void* 
  * what elfmcts_expand / elfsp_end_step take.  pi (and logits, if not NULL) rows are pi_stride floats apart; value is [rows].
  * act is read once; the per-position head values go through `workspace` (elfnet_heads_workspace(rows, h, wd) bytes of device memory,
  * > 0 and monotone in rows), which the call leaves in an unspecified state.  Two launches on `stream`, no atomics: repeated
- * calls return the same bits.
+ * calls return the same bits, and a row's bits do not depend on the number of rows in the call.
+ * Non-finite input: the three ReLUs of the head convolutions are fmaxf(sum + bias, 0), as the trunk's.  A NaN in act makes the three
+ * sums of its position NaN and therefore p[0][pos] = p[1][pos] = v0[pos] = 0: the row's pi and V are FINITE, those of the same
+ * weights with that position's head-convolution outputs at 0 -- a diverged trunk does not show as NaN here.  +Inf in act on a
+ * channel with a positive pconv_w makes p[c][pos] +Inf, the row's logits +Inf, -Inf or NaN (0 x Inf) by pi_w's column and every
+ * entry of the row's pi NaN, as torch.softmax of a row with an infinite logit is.  In both cases every other row is untouched.
  * ELFGO_E_BADARG -- and nothing is launched -- for a null act / hd / pi / value / workspace or a null weight pointer, channels % 8
- * != 0, value_hidden <= 0, workspace_bytes below elfnet_heads_workspace's, pi_stride < d + 1, act or the head-convolution weights
- * not 16-B aligned, pi_w / pi / value / logits / workspace not 4-B aligned.  Allocates nothing and waits for nothing. */
+ * != 0, value_hidden <= 0, workspace_bytes below rows * 3 * d * 4 (elfnet_heads_workspace's value, which is rounded up, always
+ * suffices), pi_stride < d + 1, act or the head-convolution weights not 16-B aligned, pi_w / pi / value / logits / workspace not
+ * 4-B aligned (the other weights need their 2 B only); and for a shape beyond the kernels' ranges: a row that does not fit the
+ * 64 KiB of LDS of a workgroup, (4 d + 1 + value_hidden) * 4 > 65 536 (a 64 x 64 board with 256 value neurons; 63 x 63 fits),
+ * rows * d >= 2^31, d > 2^20 or value_hidden > 2^20.  Allocates nothing and waits for nothing. */
 typedef struct ElfNetHeads {            /* fp16 device pointers */
   const void *pconv_w, *pconv_b;        /* [2][C], [2]        pi_final_conv    */
   const void *vconv_w, *vconv_b;        /* [1][C], [1]        value_final_conv */

@@ -87,3 +87,30 @@ def test_heads_workspace_is_positive_and_monotone_in_rows(L):
             prev = b
     assert L.elfnet_heads_workspace(0, 19, 19) > 0
     assert L.elfnet_heads_workspace(-1, 19, 19) == 0 and L.elfnet_heads_workspace(4, 0, 19) == 0
+
+
+def test_heads_refuse_a_row_beyond_the_lds(L):
+    """k_head_fc holds 4 d + 1 + value_hidden floats of a row in LDS and a workgroup has 64 KiB: a 64 x 64 board with 256 value
+    neurons is 66 564 B and refused, 63 x 63 (64 532 B) is not -- with rows = 0, which is accepted after every check and before
+    the first call into the GPU runtime"""
+    assert (4 * 64 * 64 + 1 + 256) * 4 > 65536 >= (4 * 63 * 63 + 1 + 256) * 4
+    assert _run_heads(L, _heads(), n=64) == BADARG
+    assert _run_heads(L, _heads(), rows=0, n=64) == BADARG
+    assert _run_heads(L, _heads(), rows=0, n=63) == 0
+    # value_hidden counts too: 9 x 9 takes 16 059 value neurons and not one more
+    assert (4 * 81 + 1 + 16059) * 4 == 65536
+    assert _run_heads(L, _heads(vh=16059), rows=0) == 0
+    assert _run_heads(L, _heads(vh=16060), rows=0) == BADARG
+
+
+def test_heads_refuse_sizes_beyond_their_index_range(L):
+    """rows * d at or above 2^31 (positions are indexed with an int), d or value_hidden above 2^20; the workspace size is passed
+    as a number that would be large enough"""
+    rows = 1 << 26
+    assert rows * 81 >= 1 << 31
+    assert _run_heads(L, _heads(), rows=rows, ws_bytes=rows * 3 * 81 * 4) == BADARG
+    rows = (1 << 31) // 81 + 1                                             # the first refused row count at 9 x 9
+    assert (rows - 1) * 81 < 1 << 31 <= rows * 81
+    assert _run_heads(L, _heads(), rows=rows, ws_bytes=rows * 3 * 81 * 4) == BADARG
+    assert _run_heads(L, _heads(), rows=0, n=1025, stride=1025 * 1025 + 1, ws_bytes=1 << 40) == BADARG     # d = 1 050 625 > 2^20
+    assert _run_heads(L, _heads(vh=(1 << 20) + 1), rows=0) == BADARG
