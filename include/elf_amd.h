@@ -628,7 +628,9 @@ int elfrq_set_threads(ElfReaderQueues* q, int num_threads, int64_t seed, uint64_
  * feed them to elftrain_extract.  ELFGO_E_BADARG while a queue holds fewer than queue_min_size records (the reference waits). */
 int elfrq_draw(ElfReaderQueues* q, int num_acts, int num_future_actions, int32_t* slot, int32_t* move_to, int32_t* d4);
 /* one launch: replay record rec[i] up to move_to[i] (switchBeforeMove), then every extractor of the "train" batch under
- * D4 code d4[i] (NULL = 0).  rec/move_to/d4 device int32 [n]; n <= elfgo_capacity(e) */
+ * D4 code d4[i] (NULL = 0).  rec/move_to/d4 device int32 [n].  n <= elfgo_capacity(e) only while keep_states is on (sample i
+ * replays in board slot i); with keep_states off n is not limited by the engine.  A move_to beyond the record is taken as its
+ * number of moves: the row of the fully replayed game (offline_a 0, mcts_scores 0, predicted_value 0 when no move was refused). */
 int elftrain_extract(ElfReplay* r, const int32_t* rec, const int32_t* move_to, const int32_t* d4, int n, const ElfTrainBatch* out,
                      void* stream);
 

@@ -25,7 +25,7 @@ def load_rows(n):
 
 
 # keep: the reference's own procedure (reset + forward x move_to; the replayed state stays in the engine) / the trainer's mode
-# (from the record's checkpoint, at most 31 forwards).  "9_superko": a record that continues past a positional repetition
+# (from the record's checkpoint, at most 15 forwards).  "9_superko": a record that continues past a positional repetition
 @pytest.mark.parametrize("n", [9, 19, "9_superko"])
 @pytest.mark.parametrize("fmt", ["f32_nchw", "f16_nhwc"])
 @pytest.mark.parametrize("keep", [False, True])
