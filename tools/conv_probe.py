@@ -8,7 +8,10 @@ convolution.  One process; run it under a time limit:
 For a counter pass (rocprofv3 --pmc, which replays every dispatch once per counter group) run one variant and nothing else:
     ... python tools/conv_probe.py --algos 1 --no-pair --launches 4 --warmup 1 --repeats 1 --out /dev/null
 A variant the library refuses (a non-zero status, e.g. CK's IsSupportedArgument saying no on this device) is recorded with its
-status and not timed.  FusedInferenceNet routes to algo 1 only where its mean is below algo 0's by more than the spread
+status and not timed.  --round-width W runs algo 1 through elfnet_conv3x3_f16_width: W work items at a time instead of the device's CU
+count, which decides whether the last round is split into half tiles; -1 (or any W above the number of tiles) never splits, which
+is the A/B of the split inside one build.  The rule needs one whole round in front of the split one, so at most a third of the
+tiles can be split: W = 2 * tiles / 3 gives one round of W full tiles and one of W half tiles.  FusedInferenceNet routes to algo 1 only where its mean is below algo 0's by more than the spread
 (max - min over the repeats) of either."""
 import argparse
 import ctypes as C
@@ -30,6 +33,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--algos", default="0,1")
+    ap.add_argument("--round-width", type=int, default=None,
+                    help="algo 1's round width (elfnet_conv3x3_f16_width): 0 = the CU count, -1 = never split the last round")
     ap.add_argument("--no-pair", action="store_true", help="leave F.conv2d + elfnet_bias_act_f16 out: only the fused variants run")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "conv_fused_probe.json"))
     a = ap.parse_args()
@@ -55,7 +60,11 @@ def main():
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
 
+    width = None if a.round_width is None else (1 << 30) if a.round_width < 0 else a.round_width
+
     def fused(algo, res):
+        if width is not None:
+            return lambda: L.elfnet_conv3x3_f16_width(p(x), p(w), p(b), p(res), p(y), rows, n, n, ch, ch, 1, algo, width, st)
         return lambda: L.elfnet_conv3x3_f16(p(x), p(w), p(b), p(res), p(y), rows, n, n, ch, ch, 1, algo, st)
 
     def pair(res):
@@ -83,7 +92,7 @@ def main():
         return dict(status=0, us=[round(u, 2) for u in us], mean_us=round(sum(us) / len(us), 2), min_us=round(min(us), 2),
                     max_us=round(max(us), 2))
 
-    res = dict(shape=dict(rows=rows, board_size=n, channels=ch), launches=a.launches, warmup=a.warmup, repeats=a.repeats,
+    res = dict(shape=dict(rows=rows, board_size=n, channels=ch), round_width=a.round_width, launches=a.launches, warmup=a.warmup, repeats=a.repeats,
                device=torch.cuda.get_device_name(0), method="HIP events around back-to-back launches, µs per convolution")
     with torch.no_grad():
         for skip, rr in (("noskip", None), ("skip", r)):
