@@ -20,14 +20,19 @@
 //             ds_read_b128 is served in).
 //   K order   tap-major (ky, kx, then c ascending); inside a 32-channel block the two MFMAs take channels {0..7, 16..23} and
 //             {8..15, 24..31}, as CK's blockwise GEMM hands them out: algo 0's accumulation chain per output element, bit for bit.
-//   epilogue  accumulators -> fp16 -> LDS (the staging buffers, reused) -> 16 B of consecutive channels per lane; bias and res are
-//             read in that shape, and the sequence is BiasResAct's of net_conv.hip: float(half(acc)) + bias (+ res), max(., 0), one
-//             rounding to fp16.  Rows at or beyond M are not stored.
+//   epilogue  accumulators -> fp16 -> LDS (4 KiB of the wave's own behind the staging buffers, 32 positions at a time) -> 16 B of
+//             consecutive channels per lane; bias and res are read in that shape, and the sequence is BiasResAct's of
+//             net_conv.hip: float(half(acc)) + bias (+ res), max(., 0), one rounding to fp16.  Rows at or beyond M are not stored.
+//             No workgroup barrier: a wave reads back what it wrote itself.
 //   tail      the work items of a launch (position tiles x channel columns of 256) run in rounds of one per CU.  Where the last
-//             round is at most half full, each of its items is launched as two workgroups of 256 positions x 128 channels (the
-//             half tile: the same waves at 128 x 32 each, three staged half-tiles per K tile instead of four), so that round takes
+//             round is at most half full, each of its items runs as two work ids of 256 positions x 128 channels (the half
+//             tile: the same waves at 128 x 32 each, three staged half-tiles per K tile instead of four), so that round takes
 //             a half tile's time.  Same kernel, same launch, same K chain per output element: the bits do not change.  The host
-//             entry decides (full_items below); a launch that is not split is the 2-D grid it always was.
+//             entry decides (full_items below).
+//   items     a launch is G = min(round width, work ids) workgroups; workgroup g runs the ids g, g + G, ... in ascending order,
+//             statically, depending on no other workgroup.  Behind an item's last barrier it decodes the next item's rows, issues
+//             that item's whole prologue into the staging buffers and only then runs its own epilogue: the stores drain, and the
+//             next first K tile lands, at the same time (finish_item has the order and the counts).
 //
 // The operands are swapped in the MFMA (A = weights, B = activations) so that a lane's accumulator registers run along the
 // channels: four consecutive channels of one position per register group, one ds_write_b64 each.
@@ -52,7 +57,8 @@ constexpr int kTileN = 256;                      // output channels per workgrou
 constexpr int kThreads = 512;
 constexpr int kOperandBytes = 256 * 128;         // one operand of one K tile: 256 rows x 64 fp16
 constexpr int kBufBytes = 2 * kOperandBytes;     // activations, then weights
-constexpr int kLdsBytes = 2 * kBufBytes;         // two K tiles: 128 KiB, and exactly the 256 x 256 fp16 C tile of the epilogue
+constexpr int kWaveCBytes = 4096;                // a wave's own piece of the epilogue: 32 positions x 64 channels fp16
+constexpr int kLdsBytes = 2 * kBufBytes + 8 * kWaveCBytes;   // two K tiles and the eight waves' epilogue pieces: 160 KiB, all a CU has
 
 // the line every off-board tap and every row beyond M is staged from
 __device__ __attribute__((aligned(128))) unsigned char g_zero_line[128] = {0};
@@ -79,8 +85,19 @@ __device__ __forceinline__ void raw_barrier() {
   __builtin_amdgcn_sched_barrier(0);
 }
 template <int kV> struct Mode { static constexpr int v = kV; };
+// The lane id, made opaque: what is derived from it (fragment and epilogue addresses) is then computed where it is used, per item,
+// and not hoisted out of the loop over a workgroup's items to be kept in registers across its main loops.
+__device__ __forceinline__ int fresh(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+// The same for a wave-uniform value: the reciprocals the decode's divisions go by are then made where an item is decoded
+__device__ __forceinline__ int fresh_uniform(int v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
 
-// Workgroup id -> work.  Work items are numbered tiles fastest, then channel column; ids below nfull are one full item each, and
+// Work id -> work.  Work items are numbered tiles fastest, then channel column; ids below nfull are one full item each, and
 // every item from nfull on is two consecutive ids: channel half 0, then half 1.  half < 0: the full 256 channels.
 struct WorkItem { int tile, col, half; };
 __host__ __device__ inline WorkItem work_item(int id, int tiles, int nfull) {
@@ -100,64 +117,96 @@ __host__ __device__ inline int full_items(int64_t total, int64_t width) {
   return (int)(total >= width && r > 0 && 2 * r <= width ? total - r : total);
 }
 
-// One work item: 256 positions from tile * 256 on, x kNT * 128 output channels from kbase on (kNT = 2: the full tile, 1: the half
-// tile).  Comments are written for the full tile; the half tile's differences stand at the `kNT == 1` branches.
-template <bool kHasRes, int kNT>
-__device__ __forceinline__ void conv_tile(char* lds, const char* __restrict__ x, const char* __restrict__ w,
-                                          const _Float16* __restrict__ bias, const _Float16* __restrict__ res,
-                                          _Float16* __restrict__ y, int M, int H, int W, int Cin, int K, int relu, int tile,
-                                          int kbase) {
-  // wv through readfirstlane: the compiler then keeps everything that depends on the wave alone (LDS destinations, weight rows)
-  // in scalar registers, off the vector pipe the MFMAs issue through
-  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+// What a wave knows about itself and the launch: everything the staging and the epilogue address by.
+struct Ctx {
+  char* lds;
+  const char* x;
+  const char* w;
+  int M, H, W, Cin, K, relu;
+  int lane, wv;                  // wv through readfirstlane: what depends on the wave alone stays in scalar registers
+  const unsigned char* zsrc;     // this lane's 16 B of the zero line
+};
+// The rows a staging lane feeds, decoded once per work item: byte offsets of its four activation rows and four weight rows, and
+// the 9-bit tap masks of the activation rows.
+struct Rows { uint32_t xoff[4], woff[4], xmask[4]; };
 
-  // ---- staging.  A K tile is staged as four half-tiles of 128 rows, in the order the fragment reads need them:
-  //   Xa  activation rows of the waves' position sub-tiles 0 and 1 (rows wm * 128 + 0..63)      Wa  weight rows of channel
-  //   Xb  ... of sub-tiles 2 and 3 (rows wm * 128 + 64..127)                                    sub-tile 0 (wn * 64 + 0..31)
-  //                                                                                             Wb  ... of sub-tile 1 (+ 32..63)
-  // Every wave issues two 8-row pieces of each half-tile (i = 0, 1): a lane is row (lane >> 3) of its piece and LDS slot
-  // (lane & 7) of that row.  Index hf * 2 + i below.
-  // The half tile has one weight half-tile per K tile, Wh: its 128 weight rows, LDS row = channel - kbase, wave (wm, wn) reads rows
-  // wn * 32 + fr; piece i of wave wv is rows i * 64 + wv * 8 .. + 7 (woff[0..1]).
-  uint32_t xoff[4], woff[4], xmask[4];
-  const unsigned char* zsrc = g_zero_line + (lane & 7) * 16;
+// ---- staging.  A K tile is staged as four half-tiles of 128 rows, in the order the fragment reads need them:
+//   Xa  activation rows of the waves' position sub-tiles 0 and 1 (rows wm * 128 + 0..63)      Wa  weight rows of channel
+//   Xb  ... of sub-tiles 2 and 3 (rows wm * 128 + 64..127)                                    sub-tile 0 (wn * 64 + 0..31)
+//                                                                                             Wb  ... of sub-tile 1 (+ 32..63)
+// Every wave issues two 8-row pieces of each half-tile (i = 0, 1): a lane is row (lane >> 3) of its piece and LDS slot
+// (lane & 7) of that row.  Index hf * 2 + i below.
+// The half tile (kNT == 1) has one weight half-tile per K tile, Wh: its 128 weight rows, LDS row = channel - kbase, wave (wm, wn)
+// reads rows wn * 32 + fr; piece i of wave wv is rows i * 64 + wv * 8 .. + 7 (woff[0..1]).
+template <int kNT>
+__device__ __forceinline__ void decode_rows(const Ctx& c, Rows& rw, int tile, int kbase) {
+  const int lane = c.lane, wv = c.wv;
+  const int hw = fresh_uniform(c.H * c.W), wd = fresh_uniform(c.W);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int hf = j >> 1, i = j & 1;
     const int r = i * 128 + hf * 64 + wv * 8 + (lane >> 3);
     const int p = tile * kTileM + r;
     uint32_t m = 0;
-    if (p < M) {
-      const int rem = p % (H * W), hh = rem / W, ww = rem - hh * W;
+    if (p < c.M) {
+      const int rem = p % hw, hh = rem / wd, ww = rem - hh * wd;
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
         const int dy = tap / 3 - 1, dx = tap % 3 - 1;
-        if ((unsigned)(hh + dy) < (unsigned)H && (unsigned)(ww + dx) < (unsigned)W) m |= 1u << tap;
+        if ((unsigned)(hh + dy) < (unsigned)c.H && (unsigned)(ww + dx) < (unsigned)c.W) m |= 1u << tap;
       }
     }
-    xmask[j] = m;
-    xoff[j] = (uint32_t)p * (uint32_t)(Cin * 2) + (((lane & 7) ^ ((r >> 1) & 7)) << 4);   // below 2^31 wherever it is used (p < M)
-    const int rw = kNT == 2 ? (i * 2 + (wv >> 2)) * 64 + hf * 32 + (wv & 3) * 8 + (lane >> 3) : i * 64 + wv * 8 + (lane >> 3);
-    woff[j] = (uint32_t)(kbase + rw) * (uint32_t)(9 * Cin * 2) + (((lane & 7) ^ ((rw >> 1) & 7)) << 4);
+    rw.xmask[j] = m;
+    rw.xoff[j] = (uint32_t)p * (uint32_t)(c.Cin * 2) + (((lane & 7) ^ ((r >> 1) & 7)) << 4);   // below 2^31 wherever it is used (p < M)
+    const int rwt = kNT == 2 ? (i * 2 + (wv >> 2)) * 64 + hf * 32 + (wv & 3) * 8 + (lane >> 3) : i * 64 + wv * 8 + (lane >> 3);
+    rw.woff[j] = (uint32_t)(kbase + rwt) * (uint32_t)(9 * c.Cin * 2) + (((lane & 7) ^ ((rwt >> 1) & 7)) << 4);
   }
-  // the two pieces of one half-tile of K tile (tap, kc) into buffer buf
-  auto stage_x = [&](int hf, int tap, int kc, int buf) {
-    const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
-    const uint32_t d = (uint32_t)((dy * W + dx) * Cin * 2 + kc * 128);
+}
+// the two pieces of one half-tile of K tile (tap, kc) into buffer buf
+__device__ __forceinline__ void stage_x(const Ctx& c, const Rows& rw, int hf, int tap, int kc, int buf) {
+  const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
+  const uint32_t d = (uint32_t)((dy * c.W + dx) * c.Cin * 2 + kc * 128);
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-      stage16(((xmask[hf * 2 + i] >> tap) & 1) ? x + (uint32_t)(xoff[hf * 2 + i] + d) : (const char*)zsrc,
-              lds + buf * kBufBytes + (i * 128 + hf * 64 + wv * 8) * 128);
-  };
-  auto stage_w = [&](int hf, int tap, int kc, int buf) {
-    const uint32_t d = (uint32_t)(tap * Cin * 2 + kc * 128);
+  for (int i = 0; i < 2; ++i)
+    stage16(((rw.xmask[hf * 2 + i] >> tap) & 1) ? c.x + (uint32_t)(rw.xoff[hf * 2 + i] + d) : (const char*)c.zsrc,
+            c.lds + buf * kBufBytes + (i * 128 + hf * 64 + c.wv * 8) * 128);
+}
+template <int kNT>
+__device__ __forceinline__ void stage_w(const Ctx& c, const Rows& rw, int hf, int tap, int kc, int buf) {
+  const uint32_t d = (uint32_t)(tap * c.Cin * 2 + kc * 128);
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-      stage16(w + (uint32_t)(woff[hf * 2 + i] + d),
-              lds + buf * kBufBytes + kOperandBytes +
-                  (kNT == 2 ? (i * 2 + (wv >> 2)) * 64 + hf * 32 + (wv & 3) * 8 : i * 64 + wv * 8) * 128);
-  };
+  for (int i = 0; i < 2; ++i)
+    stage16(c.w + (uint32_t)(rw.woff[hf * 2 + i] + d),
+            c.lds + buf * kBufBytes + kOperandBytes +
+                (kNT == 2 ? (i * 2 + (c.wv >> 2)) * 64 + hf * 32 + (c.wv & 3) * 8 : i * 64 + c.wv * 8) * 128);
+}
+// K tiles t + 1 and t + 2 of a work item, carried in scalars through its loop
+struct KPos { int tap1, kc1, tap2, kc2; };
+__device__ __forceinline__ KPos first_kpos(int kchunks) {
+  KPos k{0, 1, 0, 2};
+  if (kchunks == 1) { k.tap1 = 1; k.kc1 = 0; k.tap2 = 2; k.kc2 = 0; }
+  else if (kchunks == 2) { k.tap2 = 1; k.kc2 = 0; }
+  return k;
+}
+// An item's prologue, issue only: Xa Wa Wb Xb of K tile 0 and Xa Wa Wb of K tile 1 (seven half-tiles, 14 loads per wave; the half
+// tile: Xa Wh Xb, Xa Wh, five and 10).  Its wait is wait_staged<kFly> (+ what was issued behind it) and a barrier.
+template <int kNT>
+__device__ __forceinline__ void issue_prologue(const Ctx& c, const Rows& rw, int kchunks) {
+  const KPos k = first_kpos(fresh_uniform(kchunks));   // K tile 1's tap and chunk are made here, per item, not kept
+  stage_x(c, rw, 0, 0, 0, 0); stage_w<kNT>(c, rw, 0, 0, 0, 0);
+  if constexpr (kNT == 2) stage_w<kNT>(c, rw, 1, 0, 0, 0);
+  stage_x(c, rw, 1, 0, 0, 0);
+  stage_x(c, rw, 0, k.tap1, k.kc1, 1); stage_w<kNT>(c, rw, 0, k.tap1, k.kc1, 1);
+  if constexpr (kNT == 2) stage_w<kNT>(c, rw, 1, k.tap1, k.kc1, 1);
+}
 
+// The main loop of one work item: 256 positions x kNT * 128 output channels (kNT = 2: the full tile, 1: the half tile) over all
+// of K, into acc.  Entered with the item's prologue issued, waited for and behind its barrier.  Comments are written for the full
+// tile; the half tile's differences stand at the `kNT == 1` branches.
+template <int kNT>
+__device__ __forceinline__ void main_loop(const Ctx& c, const Rows& rw, floatx16 (&acc)[4][kNT]) {
+  char* const lds = c.lds;
+  const int lane = c.lane, wv = c.wv;
   // ---- fragments: lane (fr = lane & 31, fh = lane >> 5) holds row fr of a 32-row MFMA tile and 8 of the 16 k of one MFMA
   const int wm = wv >> 2, wn = wv & 3;
   const int fr = lane & 31, fh = lane >> 5;
@@ -172,7 +221,6 @@ __device__ __forceinline__ void conv_tile(char* lds, const char* __restrict__ x,
   auto ldx = [&](const char* b, int mt, int kk) { return *(const half8*)(b + xrow + mt * 4096 + cs[kk]); };
   auto ldw = [&](const char* b, int nt, int kk) { return *(const half8*)(b + wrow + nt * 4096 + cs[kk]); };
 
-  floatx16 acc[4][kNT];
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
@@ -180,7 +228,7 @@ __device__ __forceinline__ void conv_tile(char* lds, const char* __restrict__ x,
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[mt][nt][e] = 0.0f;
 
-  // ---- main loop.  K tile t lives in LDS buffer t & 1 and is spent in two halves of the wave's 128 x 64, each a load segment and
+  // K tile t lives in LDS buffer t & 1 and is spent in two halves of the wave's 128 x 64, each a load segment and
   // an MFMA segment with a bare s_barrier behind every segment:
   //   L1  reads Xa, Wa, Wb of K tile t (16 ds_read_b128)   stages Xb(t + 1)                 ends: vmcnt(8) lgkmcnt(0) barrier
   //   M1  16 MFMAs: acc[0..1][0..1] over the whole BK = 64                                  ends: barrier
@@ -210,18 +258,9 @@ __device__ __forceinline__ void conv_tile(char* lds, const char* __restrict__ x,
   // issues Xa Wh Xb of tile 0 and Xa Wh of tile 1 and waits for the first two: vmcnt(6).  The last but one K tile: 6 in L1 (it
   // still stages Xb of the last tile), 2 in L2 (only that Xb is behind Xa, Wh of the last tile); the last: 0 in L1.
   constexpr int kFly = 2 * (2 + kNT);   // two loads per half-tile x half-tiles in flight behind a counted wait: 8, or 6
-  const int kchunks = Cin >> 6, ktiles = 9 * kchunks;   // at least 9
+  const int kchunks = c.Cin >> 6, ktiles = 9 * kchunks;   // at least 9
   half8 xf[2][4], wa[4], wb[kNT == 2 ? 4 : 1];
-  int tap1 = 0, kc1 = 1, tap2 = 0, kc2 = 2;             // K tiles t + 1 and t + 2
-  if (kchunks == 1) { tap1 = 1; kc1 = 0; tap2 = 2; kc2 = 0; }
-  else if (kchunks == 2) { tap2 = 1; kc2 = 0; }
-  stage_x(0, 0, 0, 0); stage_w(0, 0, 0, 0);
-  if constexpr (kNT == 2) stage_w(1, 0, 0, 0);
-  stage_x(1, 0, 0, 0);
-  stage_x(0, tap1, kc1, 1); stage_w(0, tap1, kc1, 1);
-  if constexpr (kNT == 2) stage_w(1, tap1, kc1, 1);
-  wait_staged<kFly, false>();   // Xa, Wa, Wb of K tile 0; behind them Xb(0), Xa(1), Wa(1), Wb(1)
-  raw_barrier();
+  KPos k = first_kpos(kchunks);
 
   // mode 0: a K tile with two more behind it; 1: the last but one; 2: the last
   auto ktile = [&](auto mode, int t) {
@@ -236,7 +275,7 @@ __device__ __forceinline__ void conv_tile(char* lds, const char* __restrict__ x,
       xf[1][kk] = ldx(b, 1, kk);
       if constexpr (kNT == 2) wb[kk] = ldw(b, 1, kk);
     }
-    if constexpr (kMode <= 1) stage_x(1, tap1, kc1, nxt);
+    if constexpr (kMode <= 1) stage_x(c, rw, 1, k.tap1, k.kc1, nxt);
     wait_staged<kMode == 2 ? 0 : kFly, true>();
     raw_barrier();
     // M1
@@ -260,8 +299,8 @@ __device__ __forceinline__ void conv_tile(char* lds, const char* __restrict__ x,
       xf[1][kk] = ldx(b, 3, kk);
     }
     if constexpr (kMode == 0) {
-      stage_x(0, tap2, kc2, cur); stage_w(0, tap2, kc2, cur);
-      if constexpr (kNT == 2) stage_w(1, tap2, kc2, cur);
+      stage_x(c, rw, 0, k.tap2, k.kc2, cur); stage_w<kNT>(c, rw, 0, k.tap2, k.kc2, cur);
+      if constexpr (kNT == 2) stage_w<kNT>(c, rw, 1, k.tap2, k.kc2, cur);
     }
     wait_staged<kMode == 0 ? kFly : kMode == 1 ? 2 : 0, true>();
     raw_barrier();
@@ -280,108 +319,218 @@ __device__ __forceinline__ void conv_tile(char* lds, const char* __restrict__ x,
     __builtin_amdgcn_sched_barrier(0);
     raw_barrier();
   };
-  const int late = __builtin_amdgcn_readfirstlane(tid >> 8);   // waves 4..7: the second wave of every SIMD
+  const int late = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8);   // waves 4..7: the second wave of every SIMD
   if (late) raw_barrier();
   for (int t = 0; t < ktiles - 2; ++t) {
     ktile(Mode<0>{}, t);
-    tap1 = tap2; kc1 = kc2;
-    if (++kc2 == kchunks) { kc2 = 0; ++tap2; }
+    k.tap1 = k.tap2; k.kc1 = k.kc2;
+    if (++k.kc2 == kchunks) { k.kc2 = 0; ++k.tap2; }
   }
   ktile(Mode<1>{}, ktiles - 2);
   ktile(Mode<2>{}, ktiles - 1);
   if (!late) raw_barrier();
+  // Barriers of one item, per wave: the prologue's, 4 per K tile, and the stagger's one (in front of the loop for waves 4..7,
+  // behind it for waves 0..3): 4 ktiles + 2 for every wave, so the items of a workgroup stay paired whatever their kind.  Behind
+  // the last of them every wave is past its last fragment read: a wave 4..7 arrives there from its last M2, with the lgkmcnt(0) of
+  // L2 behind it, and a wave 0..3 has nothing left.  So whoever passes it may stage the next item into both K-tile buffers.
+}
 
-  // ---- epilogue.  D = W X^T: the lane's column is position fr of the tile, its register e is channel (e & 3) + 8 (e >> 2) + 4 fh.
-  // C tile in LDS: [256 positions][256 channels] fp16, the 16-B chunk q of position p at chunk q ^ (p & 31).
-  __syncthreads();   // the last K tile's fragment reads are done in every wave
-  // The half tile's C tile is [256][128]: 256-B rows, the chunk q of position p at chunk q ^ (p & 15), in the first 64 KiB.
-  // Banks (the lane groups and bank widths each instruction is served in): a ds_read_b128 group of 16 lanes is 16 chunks of one
-  // position (full tile) or 8 + 8 chunks of positions p, p + 1 with p even (half tile: q ^ p and q ^ (p + 1) differ in bit 0 only,
-  // and both lane sets are closed under that flip), so it covers all 64 banks once; a ds_write_b64 group is 16 consecutive
-  // positions writing the same half of the same chunk number, which the XOR spreads over 16 chunks: every one of the 16 banks
-  // that half can reach is used twice, in the half tile as in the full one (enumerated on the host from the two formulas below).
-  constexpr int kRowB = kNT * 256, kCm = kNT * 16 - 1;          // bytes per C row; chunk mask
-  constexpr int kQs = kNT == 2 ? 5 : 4, kIts = kNT * 8;         // lanes per row = 1 << kQs; passes of 512 >> kQs rows
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < kNT; ++nt) {
-      const int pos = wm * 128 + mt * 32 + fr;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int ch = wn * 32 * kNT + nt * 32 + g * 8 + fh * 4;
-        half4 hv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) hv[e] = (_Float16)acc[mt][nt][g * 4 + e];
-        *(half4*)(lds + pos * kRowB + (((ch >> 3) ^ (pos & kCm)) << 4) + ((ch >> 2) & 1) * 8) = hv;
-      }
-    }
-  const int q = tid & kCm;
-  const half8 bv = *(const half8*)(bias + kbase + q * 8);
+// ---- epilogue.  D = W X^T: the lane's column is position fr of an MFMA tile, its register e is channel (e & 3) + 8 (e >> 2) + 4 fh.
+// It is wave-private: the wave's own 4 KiB behind the K-tile buffers, no barrier, so it runs while the next item's prologue lands
+// in the K-tile buffers.  Four passes, one per mt: 32 positions x 64 channels of this wave (the half tile: x 32) as rows of kC = 8
+// (4) chunks of 16 B, the chunk q of position p at chunk q ^ ((p >> 1) & 7) (the half tile: q ^ ((p >> 2) & 3)); written as
+// ds_write_b64 by the lane that holds the four channels, lgkmcnt(0), read back as 16 B of consecutive channels per lane, kC lanes
+// per position, so a store instruction writes whole 128-B (64-B) runs of y.  Banks, by the lane groups each instruction is served
+// in and the 64 banks of 4 B (enumerated on the host from the two formulas below): a ds_write_b64 group is 16
+// consecutive positions writing the same half of the same chunk number: the 256-B bank row holds two (four) positions and the XOR
+// steps every second (fourth), so the 16 lanes land in 16 different 16-B slots; a ds_read_b128 group is four runs of 4 lanes (or two
+// of 8), each run a different position of a different slot quarter: all 64 banks once.
+template <bool kHasRes, int kNT>
+struct Skip { half8 bv; half8 rv[kHasRes ? 8 * kNT : 1]; };
+
+template <int kNT>
+struct EpiLane {
+  static constexpr int kC = 4 * kNT;           // chunks per row = lanes per position in the read-back
+  static constexpr int kPos = 64 / kC;         // positions per read-back instruction
+  static constexpr int kR = 32 / kPos;         // read-backs per pass
+  int pr, q, chan;                             // the lane's position in a read-back, its chunk, its first channel of the item
+  int row0;                                    // the wave's first position
+  __device__ __forceinline__ EpiLane(const Ctx& c, int tile, int kbase)
+      : pr(c.lane / kC), q(c.lane % kC), chan(kbase + (c.wv & 3) * 32 * kNT + (c.lane % kC) * 8),
+        row0(tile * kTileM + (c.wv >> 2) * 128) {}
+  static __device__ __forceinline__ int swz(int p) { return kNT == 2 ? (p >> 1) & 7 : (p >> 2) & 3; }
+};
+
+// bias and the skip's 16 B per (position, chunk), in the shape the read-back has.  A row beyond M reads the last valid row instead
+// (no branch around a load) and is not stored.
+template <bool kHasRes, int kNT>
+__device__ __forceinline__ void load_bias(const Ctx& c, Skip<kHasRes, kNT>& s, const _Float16* __restrict__ bias, int tile, int kbase) {
+  const EpiLane<kNT> e(c, tile, kbase);
+  s.bv = *(const half8*)(bias + e.chan);
+}
+template <bool kHasRes, int kNT>
+__device__ __forceinline__ void load_skip(const Ctx& c, Skip<kHasRes, kNT>& s, const _Float16* __restrict__ res, int tile, int kbase) {
+  using E = EpiLane<kNT>;
+  const E e(c, tile, kbase);
   if constexpr (kHasRes) {
-    // the skip's 16 B per (position, chunk) are requested before the barrier, now that the accumulators' registers are free: they
-    // arrive while the waves meet.  A row beyond M reads the last valid row instead (no branch around a load) and is not stored.
-    half8 rv[kIts];
 #pragma unroll
-    for (int it = 0; it < kIts; ++it) {
-      const int p = tile * kTileM + (it << (9 - kQs)) + (tid >> kQs);
-      rv[it] = *(const half8*)(res + (size_t)(p < M ? p : M - 1) * K + kbase + q * 8);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < kIts; ++it) {
-      const int pos = (it << (9 - kQs)) + (tid >> kQs);
-      const int p = tile * kTileM + pos;
-      const half8 cv = *(const half8*)(lds + pos * kRowB + ((q ^ (pos & kCm)) << 4));
-      half8 ov;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float v = (float)cv[e];
-        v += (float)bv[e];
-        v += (float)rv[it][e];
-        if (relu) v = fmaxf(v, 0.0f);
-        ov[e] = (_Float16)v;
-      }
-      if (p < M) *(half8*)(y + (size_t)p * K + kbase + q * 8) = ov;
-    }
-  } else {
-    __syncthreads();
-#pragma unroll 4
-    for (int it = 0; it < kIts; ++it) {
-      const int pos = (it << (9 - kQs)) + (tid >> kQs);
-      const int p = tile * kTileM + pos;
-      if (p < M) {
-        const half8 cv = *(const half8*)(lds + pos * kRowB + ((q ^ (pos & kCm)) << 4));
-        half8 ov;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float v = (float)cv[e];
-          v += (float)bv[e];
-          if (relu) v = fmaxf(v, 0.0f);
-          ov[e] = (_Float16)v;
-        }
-        *(half8*)(y + (size_t)p * K + kbase + q * 8) = ov;
-      }
+    for (int it = 0; it < 4 * E::kR; ++it) {
+      const int p = e.row0 + (it / E::kR) * 32 + (it % E::kR) * E::kPos + e.pr;
+      s.rv[it] = *(const half8*)(res + (size_t)(p < c.M ? p : c.M - 1) * c.K + e.chan);
     }
   }
 }
 
+// kAll: every row of the tile is below M, and every lane issues all its 8 kNT stores (the count the next item's first wait uses)
+template <bool kHasRes, int kNT, bool kAll>
+__device__ __forceinline__ void epilogue(const Ctx& c, const half4 (&hacc)[4][kNT][4], const Skip<kHasRes, kNT>& s,
+                                         _Float16* __restrict__ y, int tile, int kbase) {
+  using E = EpiLane<kNT>;
+  const E e(c, tile, kbase);
+  char* const cl = c.lds + 2 * kBufBytes + c.wv * kWaveCBytes;
+  const int fr = c.lane & 31, fh = c.lane >> 5;
+  constexpr int kRowB = 16 * E::kC;
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+#pragma unroll
+    for (int nt = 0; nt < kNT; ++nt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) *(half4*)(cl + fr * kRowB + (((nt * 4 + g) ^ E::swz(fr)) << 4) + fh * 8) = hacc[mt][nt][g];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the wave's own writes; nobody else's are read
+#pragma unroll
+    for (int j = 0; j < E::kR; ++j) {
+      const int pos = j * E::kPos + e.pr;
+      const int p = e.row0 + mt * 32 + pos;
+      const half8 cv = *(const half8*)(cl + pos * kRowB + ((e.q ^ E::swz(pos)) << 4));
+      half8 ov;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        float v = (float)cv[i];
+        v += (float)s.bv[i];
+        if constexpr (kHasRes) v += (float)s.rv[mt * E::kR + j][i];
+        if (c.relu) v = fmaxf(v, 0.0f);
+        ov[i] = (_Float16)v;
+      }
+      if (kAll || p < c.M) *(half8*)(y + (size_t)p * c.K + e.chan) = ov;
+    }
+    __builtin_amdgcn_wave_barrier();   // the next pass's writes stay behind this pass's read-backs
+  }
+}
+
+// The end of one item and the start of the next (kNext = 2: a full item follows, 1: a half item, 0: nothing).  Order:
+//   bias and skip loads of this item (1 + 16 plain loads with the skip, 1 without)
+//   the next item's rows decoded over this item's (dead since its last staging), its whole prologue issued (14 or 10 LDS-DMA loads)
+//   this item's epilogue: four passes, 4 stores each (the half tile: 2)
+//   the next item's first wait and barrier
+// vmcnt counts loads, LDS-DMA loads and stores together, in issue order.  The waits on this path:
+//   the epilogue's passes wait for bias / skip registers only, with counts the compiler places: the loads they wait for are older
+//   than the prologue, so nothing of the prologue is waited for (pass mt of a full item with the skip: its four skip loads have
+//   the later 12 - 4 mt skip loads, the 14 prologue loads and 4 mt stores behind them: vmcnt(26) every pass);
+//   the first wait needs Xa, Wa, Wb of K tile 0: behind them kFly = 8 loads of the prologue (6 for a half item next) and this
+//   item's 16 stores: vmcnt(24) (22).  Where the tile has rows at or beyond M a lane may issue fewer stores, and a count that is
+//   too high waits for too little: that tile waits with kFly alone, which is right for no store at all and stronger otherwise.
+template <bool kHasRes, int kNT, int kNext>
+__device__ __forceinline__ void finish_item(Ctx& c, int lane, Rows& rw, const floatx16 (&acc)[4][kNT], const _Float16* __restrict__ bias,
+                                            const _Float16* __restrict__ res, _Float16* __restrict__ y, int tile, int kbase,
+                                            int ntile, int nkbase) {
+  Skip<kHasRes, kNT> s;
+  load_bias<kHasRes, kNT>(c, s, bias, tile, kbase);
+  __builtin_amdgcn_sched_barrier(0);
+  // the accumulators' first rounding, at once: 64 registers instead of 128 under the skip's 64 and the prologue's addresses
+  half4 hacc[4][kNT][4];
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < kNT; ++nt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) hacc[mt][nt][g][i] = (_Float16)acc[mt][nt][g * 4 + i];
+        asm volatile("" : "+v"(hacc[mt][nt][g]));   // converted here, not where it is written out
+      }
+  c.lane = fresh(lane);   // behind the conversions: no address of what follows is made while all 192 registers are in use
+  __builtin_amdgcn_sched_barrier(0);
+  load_skip<kHasRes, kNT>(c, s, res, tile, kbase);
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (kNext != 0) {
+    decode_rows<kNext>(c, rw, ntile, nkbase);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  // The compiler's wait for the bias and skip registers is made to stand here, in front of the prologue: once LDS-DMA loads are
+  // pending it counts nothing and waits with vmcnt(0) for any register a plain load returns, which behind the prologue would be
+  // a wait for the prologue.  The conversions and the decode above are what these loads have to return in.
+  asm volatile("" ::"v"(s.bv));
+  if constexpr (kHasRes) {
+#pragma unroll
+    for (int it = 0; it < 8 * kNT; ++it) asm volatile("" ::"v"(s.rv[it]));
+  }
+  if constexpr (kNext != 0) {
+    issue_prologue<kNext>(c, rw, c.Cin >> 6);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  const bool all = __builtin_amdgcn_readfirstlane((tile + 1) * kTileM <= c.M);
+  if (all) epilogue<kHasRes, kNT, true>(c, hacc, s, y, tile, kbase);
+  else epilogue<kHasRes, kNT, false>(c, hacc, s, y, tile, kbase);
+  if constexpr (kNext != 0) {
+    constexpr int kFly = 2 * (2 + kNext);
+    if (all) wait_staged<kFly + 8 * kNT, false>();
+    else wait_staged<kFly, false>();
+    raw_barrier();
+  }
+}
+
+// One workgroup runs the work ids g, g + G, g + 2 G, ... of the launch (G = gridDim.x), in ascending order.  The host entry makes
+// G = min(round width, ids), so where the last round is split the full ids are a multiple of G: a workgroup's first item is a
+// full one and a half item, if it has one, is its last (at most one: there are at most G half ids).
 template <bool kHasRes>
 __global__ __launch_bounds__(kThreads, 2) void k_conv3x3_f16(const char* __restrict__ x, const char* __restrict__ w,
                                                              const _Float16* __restrict__ bias, const _Float16* __restrict__ res,
                                                              _Float16* __restrict__ y, int M, int H, int W, int Cin, int K, int relu,
-                                                             int tiles, int nfull) {
+                                                             int tiles, int nfull, int ids) {
   __shared__ __attribute__((aligned(128))) char lds[kLdsBytes];   // ALL of the kernel's LDS: one array
-  // The workgroup's id is in scalar registers, so this branch is uniform; an unsplit launch (nfull = every item) is the 2-D grid
-  // of tiles x columns, whose linear id is the item.  The half tile leaves by a return of its own: as if / else the two bodies met
-  // in one exit block, and the compiler, which then sees a path from the half tile's epilogue into the full tile, put an
-  // s_waitcnt vmcnt(0) between the full tile's prologue and its loop (with res), draining the four half-tiles in flight there.
-  const WorkItem wi = work_item((int)(blockIdx.y * gridDim.x + blockIdx.x), tiles, nfull);
-  if (__builtin_amdgcn_readfirstlane(wi.half) >= 0) {
-    conv_tile<kHasRes, 1>(lds, x, w, bias, res, y, M, H, W, Cin, K, relu, wi.tile, wi.col * kTileN + wi.half * (kTileN / 2));
-    return;
+  const int tid = threadIdx.x;
+  Ctx c;
+  c.lds = lds; c.x = x; c.w = w; c.M = M; c.H = H; c.W = W; c.Cin = Cin; c.K = K; c.relu = relu;
+  c.lane = tid & 63;
+  c.wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  c.zsrc = g_zero_line + (c.lane & 7) * 16;
+  const int G = (int)gridDim.x;
+  int id = (int)blockIdx.x;
+  WorkItem wi = work_item(id, tiles, nfull);   // a full item: see above
+  Rows rw;
+  decode_rows<2>(c, rw, wi.tile, wi.col * kTileN);
+  issue_prologue<2>(c, rw, Cin >> 6);
+  wait_staged<8, false>();   // Xa, Wa, Wb of K tile 0; behind them Xb(0), Xa(1), Wa(1), Wb(1)
+  raw_barrier();
+  // The three ends of a full item are uniform branches that do not meet again: each has its own epilogue, so the compiler's
+  // counts for the bias and skip registers are those of one path (joined, it would take the path without a prologue and wait
+  // for the other paths' prologues), and a return of its own.
+  const int lane = c.lane;
+  int hk = 0;
+  for (;;) {
+    floatx16 acc[4][2];
+    c.lane = fresh(lane);
+    main_loop<2>(c, rw, acc);
+    const int nid = id + G;
+    if (nid >= ids) {
+      finish_item<kHasRes, 2, 0>(c, lane, rw, acc, bias, res, y, wi.tile, wi.col * kTileN, 0, 0);
+      return;
+    }
+    const WorkItem nwi = work_item(nid, tiles, nfull);
+    if (__builtin_amdgcn_readfirstlane(nwi.half) >= 0) {
+      const int nkbase = nwi.col * kTileN + nwi.half * (kTileN / 2);
+      finish_item<kHasRes, 2, 1>(c, lane, rw, acc, bias, res, y, wi.tile, wi.col * kTileN, nwi.tile, nkbase);
+      wi = nwi; hk = nkbase;
+      break;
+    }
+    finish_item<kHasRes, 2, 2>(c, lane, rw, acc, bias, res, y, wi.tile, wi.col * kTileN, nwi.tile, nwi.col * kTileN);
+    id = nid;
+    wi = nwi;
   }
-  conv_tile<kHasRes, 2>(lds, x, w, bias, res, y, M, H, W, Cin, K, relu, wi.tile, wi.col * kTileN);
+  floatx16 acch[4][1];
+  c.lane = fresh(lane);
+  main_loop<1>(c, rw, acch);
+  finish_item<kHasRes, 1, 0>(c, lane, rw, acch, bias, res, y, wi.tile, hk, 0, 0);
 }
 
 // the CU count of the current device, asked for once per device
@@ -403,8 +552,9 @@ int round_width_of_device() {
 // tensor below 2^31 bytes) and set the device.  One launch on `stream`: no allocation, no memset, no synchronisation, no copy.
 // Shapes the kernel does not take are refused with nothing launched.
 // round_width is how many work items run at a time, 0 for the device's CU count (one workgroup per CU).  With total = tiles x
-// columns and r = total % width, the last round is split iff total >= width and 0 < 2 r <= width: a 1-D grid of total + r
-// workgroups, the last r items as two half tiles each (work_item).  Otherwise the launch is the 2-D grid of tiles x columns.
+// columns and r = total % width, the last round is split iff total >= width and 0 < 2 r <= width: total + r work ids, the last r
+// items as two half tiles each (work_item); otherwise total ids.  The launch is a 1-D grid of min(width, ids) workgroups, each
+// running every width-th id (a width above the ids, or an unknown CU count: one id per workgroup).
 extern "C" __attribute__((visibility("hidden"))) int elfnet_conv3x3_native_f16(const void* x, const void* w, const void* bias,
                                                                                const void* res, void* y, int64_t rows, int h, int wd,
                                                                                int c, int k, int relu, int round_width,
@@ -415,13 +565,14 @@ extern "C" __attribute__((visibility("hidden"))) int elfnet_conv3x3_native_f16(c
   const int64_t total = (int64_t)tiles * cols;       // below 2^31: m * k is below 2^30
   const int width = round_width > 0 ? round_width : round_width_of_device();
   const int nfull = width > 0 ? full_items(total, width) : (int)total;
-  const dim3 grid = nfull < total ? dim3((unsigned)(2 * total - nfull)) : dim3((unsigned)tiles, (unsigned)cols);
+  const int64_t ids = 2 * total - nfull;
+  const dim3 grid((unsigned)(width > 0 && width < ids ? width : ids));
   if (res)
     hipLaunchKernelGGL(k_conv3x3_f16<true>, grid, dim3(kThreads), 0, stream, (const char*)x, (const char*)w, (const _Float16*)bias,
-                       (const _Float16*)res, (_Float16*)y, (int)m, h, wd, c, k, relu, tiles, nfull);
+                       (const _Float16*)res, (_Float16*)y, (int)m, h, wd, c, k, relu, tiles, nfull, (int)ids);
   else
     hipLaunchKernelGGL(k_conv3x3_f16<false>, grid, dim3(kThreads), 0, stream, (const char*)x, (const char*)w, (const _Float16*)bias,
-                       (const _Float16*)nullptr, (_Float16*)y, (int)m, h, wd, c, k, relu, tiles, nfull);
+                       (const _Float16*)nullptr, (_Float16*)y, (int)m, h, wd, c, k, relu, tiles, nfull, (int)ids);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
@@ -440,4 +591,10 @@ extern "C" int64_t elfnet_conv3x3_f16_plan(int64_t tiles, int columns, int round
     if (half) *half = wi.half;
   }
   return groups;
+}
+
+// Host arithmetic only: the workgroups of that launch.  Workgroup g runs the work ids g, g + G, g + 2 G, ... of the plan.
+extern "C" int64_t elfnet_conv3x3_f16_grid(int64_t tiles, int columns, int round_width) {
+  const int64_t ids = elfnet_conv3x3_f16_plan(tiles, columns, round_width, 0, nullptr, nullptr, nullptr);
+  return ids < 0 ? ids : round_width < ids ? round_width : ids;
 }

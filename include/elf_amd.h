@@ -685,18 +685,23 @@ int elfnet_bias_act_bf16(void* x, const void* bias, const void* res, int64_t row
 int elfnet_conv3x3_f16(const void* x, const void* w, const void* bias, const void* res, void* y,
                        int64_t rows, int h, int wd, int c, int k, int relu, int algo, void* stream);
 /* elfnet_conv3x3_f16 with the round width of algo 1 named: how many of its work items (tiles of 256 positions x columns of 256
- * output channels) the device runs at a time.  Algo 1 launches the work items of a last round that is at most half full as two
- * workgroups of 256 positions x 128 channels each, so that round takes a half tile's time: with total = tiles * (k / 256) and
- * r = total % round_width, iff total >= round_width and 0 < 2 r <= round_width.  The output bits are the same either way.
+ * output channels) the device runs at a time.  Algo 1 runs the work items of a last round that is at most half full as two
+ * work ids of 256 positions x 128 channels each, so that round takes a half tile's time: with total = tiles * (k / 256) and
+ * r = total % round_width, iff total >= round_width and 0 < 2 r <= round_width.  The launch is min(round_width, work ids)
+ * workgroups, each running every round_width-th id one after the other.  The output bits are the same whatever the width.
  * round_width 0 = the device's CU count (one workgroup per CU), which is what elfnet_conv3x3_f16 passes; a value above total never
- * splits; a negative one is ELFGO_E_BADARG.  Algo 0 ignores it.  For tests and probes of the split at sizes of a few tiles. */
+ * splits and gives every work id a workgroup of its own; a negative one is ELFGO_E_BADARG.  Algo 0 ignores it.  For tests and
+ * probes of the split and of the chains at sizes of a few tiles. */
 int elfnet_conv3x3_f16_width(const void* x, const void* w, const void* bias, const void* res, void* y,
                              int64_t rows, int h, int wd, int c, int k, int relu, int algo, int round_width, void* stream);
-/* Host arithmetic: the launch elfnet_conv3x3_f16_width(algo 1) makes for tiles x columns work items and round_width > 0.  Returns the
- * number of workgroups (tiles * columns when the last round is not split), or ELFGO_E_BADARG.  With any of tile / column / half
- * non-NULL it also says what workgroup `id` computes: its tile, its column, and half = -1 for all 256 channels of the column or
- * 0 / 1 for the lower / upper 128. */
+/* Host arithmetic: the work ids of the launch elfnet_conv3x3_f16_width(algo 1) makes for tiles x columns work items and
+ * round_width > 0.  Returns the number of work ids (tiles * columns when the last round is not split, one more per split item),
+ * or ELFGO_E_BADARG.  With any of tile / column / half non-NULL it also says what work id `id` computes: its tile, its column,
+ * and half = -1 for all 256 channels of the column or 0 / 1 for the lower / upper 128.  A work id is not a workgroup: see _grid. */
 int64_t elfnet_conv3x3_f16_plan(int64_t tiles, int columns, int round_width, int64_t id, int* tile, int* column, int* half);
+/* Host arithmetic: the workgroups G of that launch, min(round_width, work ids), or ELFGO_E_BADARG for what _plan refuses.
+ * Workgroup g runs the work ids g, g + G, g + 2 G, ... in ascending order; a half id is the last one of its workgroup. */
+int64_t elfnet_conv3x3_f16_grid(int64_t tiles, int columns, int round_width);
 
 /* The two ends of the fp16 net on this library's kernels (elf_amd/csrc/net_io.hip).  A C host evaluates a BN-folded net as
  *   elfnet_conv3x3_in_f16 (feature rows -> trunk activation), elfnet_conv3x3_f16 twice per residual block, elfnet_heads_f16

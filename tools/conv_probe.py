@@ -9,8 +9,10 @@ For a counter pass (rocprofv3 --pmc, which replays every dispatch once per count
     ... python tools/conv_probe.py --algos 1 --no-pair --launches 4 --warmup 1 --repeats 1 --out /dev/null
 A variant the library refuses (a non-zero status, e.g. CK's IsSupportedArgument saying no on this device) is recorded with its
 status and not timed.  --round-width W runs algo 1 through elfnet_conv3x3_f16_width: W work items at a time instead of the device's CU
-count, which decides whether the last round is split into half tiles; -1 (or any W above the number of tiles) never splits, which
-is the A/B of the split inside one build.  The rule needs one whole round in front of the split one, so at most a third of the
+count, which decides whether the last round is split into half tiles and how many workgroups the launch has: min(W, work ids),
+each running every W-th id one after the other with the next item's prologue issued in front of its epilogue.  -1 (or any W above
+the number of tiles) never splits and gives every work id a workgroup of its own, which is the A/B of the split and of the chains
+inside one build.  The rule needs one whole round in front of the split one, so at most a third of the
 tiles can be split: W = 2 * tiles / 3 gives one round of W full tiles and one of W half tiles.  FusedInferenceNet routes to algo 1 only where its mean is below algo 0's by more than the spread
 (max - min over the repeats) of either."""
 import argparse
