@@ -7,10 +7,10 @@
 //             activation byte is staged once for every output channel.  512 threads, 8 waves as 2 (positions) x 4 (channels), each
 //             owning 128 positions x 64 channels = 4 x 2 MFMA tiles = 128 accumulator registers.  One workgroup per CU.
 //   staging   LDS-DMA (global_load_lds_dwordx4) straight into two 64-KiB LDS buffers (activation tile, weight tile: 256 rows of
-//             128 B each), in half-tiles of 128 rows of one operand, two 8-row pieces per wave; four half-tiles stay in flight
-//             across the loop's barriers, which are bare s_barriers behind counted vmcnt waits (the comment at the main loop has
-//             the counts).  vmcnt(0) only once the last half-tile is on its way.  Every staged piece is a full aligned 128-B
-//             line: 8 lanes per row.
+//             128 B each), in half-tiles of 128 rows of one operand, two 8-row pieces per wave, issued one at a time between the
+//             MFMAs of the MFMA segments; three or four half-tiles stay in flight across the loop's barriers, which are bare
+//             s_barriers behind counted vmcnt waits (the comment at the main loop has the slots and the counts).  vmcnt(0) only
+//             once the last half-tile is on its way.  Every staged piece is a full aligned 128-B line: 8 lanes per row.
 //   halo      a staging lane decodes its four rows once (position -> n, h, w) and keeps a 9-bit tap mask and a byte offset; for an
 //             off-board tap, and for a row at or beyond M, its source address is a zero-filled line in global memory.  LDS is never
 //             zeroed by a second path.
@@ -85,6 +85,11 @@ __device__ __forceinline__ void raw_barrier() {
   __builtin_amdgcn_sched_barrier(0);
 }
 template <int kV> struct Mode { static constexpr int v = kV; };
+// s_setprio in the main loop.  0: every wave raises its priority for its MFMA segments (shipped); the other two are what the probe
+// timed against it: 1 none, 2 the static form, waves 4..7 at priority 1 for the whole loop.
+#ifndef ELFNET_CONV3X3_PRIO
+#define ELFNET_CONV3X3_PRIO 0
+#endif
 // The lane id, made opaque: what is derived from it (fragment and epilogue addresses) is then computed where it is used, per item,
 // and not hoisted out of the loop over a workgroup's items to be kept in registers across its main loops.
 __device__ __forceinline__ int fresh(int v) {
@@ -162,23 +167,35 @@ __device__ __forceinline__ void decode_rows(const Ctx& c, Rows& rw, int tile, in
     rw.woff[j] = (uint32_t)(kbase + rwt) * (uint32_t)(9 * c.Cin * 2) + (((lane & 7) ^ ((rwt >> 1) & 7)) << 4);
   }
 }
-// the two pieces of one half-tile of K tile (tap, kc) into buffer buf
-__device__ __forceinline__ void stage_x(const Ctx& c, const Rows& rw, int hf, int tap, int kc, int buf) {
+// the byte offset of K tile (tap, kc) from a row's own position in x, and from the start of a weight row: wave-uniform
+__device__ __forceinline__ uint32_t x_delta(const Ctx& c, int tap, int kc) {
   const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
-  const uint32_t d = (uint32_t)((dy * c.W + dx) * c.Cin * 2 + kc * 128);
+  return (uint32_t)((dy * c.W + dx) * c.Cin * 2 + kc * 128);
+}
+__device__ __forceinline__ uint32_t w_delta(const Ctx& c, int tap, int kc) { return (uint32_t)(tap * c.Cin * 2 + kc * 128); }
+// piece i of one half-tile of the K tile at tap `tap` and offset d (x_delta, w_delta) into buffer buf; the two pieces of a
+// half-tile are issued in the order i = 0, 1
+__device__ __forceinline__ void stage_x_piece(const Ctx& c, const Rows& rw, int hf, int i, int tap, uint32_t d, int buf) {
+  stage16(((rw.xmask[hf * 2 + i] >> tap) & 1) ? c.x + (uint32_t)(rw.xoff[hf * 2 + i] + d) : (const char*)c.zsrc,
+          c.lds + buf * kBufBytes + (i * 128 + hf * 64 + c.wv * 8) * 128);
+}
+template <int kNT>
+__device__ __forceinline__ void stage_w_piece(const Ctx& c, const Rows& rw, int hf, int i, uint32_t d, int buf) {
+  stage16(c.w + (uint32_t)(rw.woff[hf * 2 + i] + d),
+          c.lds + buf * kBufBytes + kOperandBytes +
+              (kNT == 2 ? (i * 2 + (c.wv >> 2)) * 64 + hf * 32 + (c.wv & 3) * 8 : i * 64 + c.wv * 8) * 128);
+}
+// both pieces of a half-tile, back to back: the prologue's form
+__device__ __forceinline__ void stage_x(const Ctx& c, const Rows& rw, int hf, int tap, int kc, int buf) {
+  const uint32_t d = x_delta(c, tap, kc);
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
-    stage16(((rw.xmask[hf * 2 + i] >> tap) & 1) ? c.x + (uint32_t)(rw.xoff[hf * 2 + i] + d) : (const char*)c.zsrc,
-            c.lds + buf * kBufBytes + (i * 128 + hf * 64 + c.wv * 8) * 128);
+  for (int i = 0; i < 2; ++i) stage_x_piece(c, rw, hf, i, tap, d, buf);
 }
 template <int kNT>
 __device__ __forceinline__ void stage_w(const Ctx& c, const Rows& rw, int hf, int tap, int kc, int buf) {
-  const uint32_t d = (uint32_t)(tap * c.Cin * 2 + kc * 128);
+  const uint32_t d = w_delta(c, tap, kc);
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
-    stage16(c.w + (uint32_t)(rw.woff[hf * 2 + i] + d),
-            c.lds + buf * kBufBytes + kOperandBytes +
-                (kNT == 2 ? (i * 2 + (c.wv >> 2)) * 64 + hf * 32 + (c.wv & 3) * 8 : i * 64 + c.wv * 8) * 128);
+  for (int i = 0; i < 2; ++i) stage_w_piece<kNT>(c, rw, hf, i, d, buf);
 }
 // K tiles t + 1 and t + 2 of a work item, carried in scalars through its loop
 struct KPos { int tap1, kc1, tap2, kc2; };
@@ -230,43 +247,96 @@ __device__ __forceinline__ void main_loop(const Ctx& c, const Rows& rw, floatx16
 
   // K tile t lives in LDS buffer t & 1 and is spent in two halves of the wave's 128 x 64, each a load segment and
   // an MFMA segment with a bare s_barrier behind every segment:
-  //   L1  reads Xa, Wa, Wb of K tile t (16 ds_read_b128)   stages Xb(t + 1)                 ends: vmcnt(8) lgkmcnt(0) barrier
-  //   M1  16 MFMAs: acc[0..1][0..1] over the whole BK = 64                                  ends: barrier
-  //   L2  reads Xb(t) over Xa (8 ds_read_b128)             stages Xa, Wa, Wb of t + 2       ends: vmcnt(8) lgkmcnt(0) barrier
-  //   M2  16 MFMAs: acc[2..3][0..1]                                                         ends: barrier
+  //   L1  reads Xa, Wa, Wb of K tile t (16 ds_read_b128)                                    ends: vmcnt(6) lgkmcnt(0) barrier
+  //   M1  16 MFMAs: acc[0..1][0..1] over the whole BK = 64; stages Xb(t + 1) among them     ends: barrier
+  //   L2  reads Xb(t) over Xa (8 ds_read_b128)                                              ends: vmcnt(2) lgkmcnt(0) barrier
+  //   M2  16 MFMAs: acc[2..3][0..1]; stages Xa, Wa, Wb of t + 2 among them                  ends: barrier
   // Every accumulator still takes its K in ascending order.  Waves 4..7 (the second wave of every SIMD) pass one barrier more
   // before the loop and waves 0..3 one more behind it, so the two waves of a SIMD run one segment apart: one issues its MFMAs while
-  // the other reads, stages and waits, and the matrix pipe does not stand still while both fetch.
-  // By the counts (a wave's loads retire in issue order, two per half-tile, half-tiles in the order Xa Wa Wb Xb of a K tile), for
-  // waves that may be one barrier apart:
+  // the other reads and waits, and the matrix pipe does not stand still while both fetch.
+  // The LDS-DMA pieces are issued from the MFMA segments, one at a time between two MFMAs (kM1At, kM2At: after which MFMA of the
+  // segment; a sched_barrier on both sides keeps each where it is written): an issue costs the wave far less among MFMAs than in
+  // a segment that also carries the fragment reads, and there it is in the MFMAs' shadow, while in a load segment it made the
+  // slot longer for all eight waves.  The issue order is what it was: Xa Wa Wb Xb of a K tile.
+  // Slots (a slot is what lies between two barriers; early = waves 0..3, late = waves 4..7, one slot behind):
+  //   slot      4t          4t+1        4t+2        4t+3        4t+4        4t+5
+  //   early     L1(t)       M1(t)       L2(t)       M2(t)       L1(t+1)     M1(t+1)
+  //             r XaWaWb(t) s Xb(t+1)   r Xb(t)     s XaWaWb(t+2)
+  //   late      M2(t-1)     L1(t)       M1(t)       L2(t)       M2(t)       L1(t+1)
+  //             s XaWaWb(t+1) r XaWaWb(t) s Xb(t+1) r Xb(t)     s XaWaWb(t+2)
+  // By the counts (a wave's loads retire in issue order, two per half-tile), for waves that may be one barrier apart:
   //   landed   what a load segment reads was waited for, by every wave, in its load segment before: there are two barriers
   //            between a wave's wait and its own next load segment, so at least one between anybody's wait and anybody's read.
-  //            L1(t)'s wait is for Xb(t), read in L2(t): the wave has issued up to Xb(t+1), that is Xa, Wa, Wb, Xb of t + 1 behind
-  //            it: 4 half-tiles, vmcnt(8).  L2(t)'s wait is for Xa, Wa, Wb of t + 1, read in L1(t+1): issued up to Wb(t+2), that
-  //            is Xb(t+1), Xa, Wa, Wb of t + 2 behind them: vmcnt(8) again.
-  //   free     a half-tile is restaged one load segment after the one that read it (lgkmcnt(0) in front of that one's barrier), two
-  //            barriers later for the wave itself and at least one for a wave that runs behind: Xb(t-1), read in L2(t-1), is
-  //            restaged in L1(t); Xa, Wa, Wb of t, read in L1(t), are restaged in L2(t).
-  // So four half-tiles (64 KiB) are in flight across every barrier, each for a whole K tile of MFMAs, and the loop never drains
-  // the queue; the last two K tiles issue nothing new and count it down (8, 2, then 0 in the last K tile's L1).
+  //            L1(t)'s wait is for Xb(t), read in L2(t): the wave has issued up to Wb(t+1) (in M2(t-1), or in the prologue), that
+  //            is Xa, Wa, Wb of t + 1 behind it: 3 half-tiles, vmcnt(6).  L2(t)'s wait is for Xa, Wa, Wb of t + 1, read in
+  //            L1(t+1): issued up to Xb(t+1) (in M1(t)), one half-tile behind them: vmcnt(2).  A half-tile has three slots to land in.
+  //   free     a half-tile is restaged from the second segment after the load segment that read it (lgkmcnt(0) in front of that
+  //            one's barrier): Xb(t-1), read in L2(t-1) (slots 4t-2 and 4t-1), is restaged in M1(t) (slots 4t+1 and 4t+2);
+  //            Xa, Wa, Wb of t, read in L1(t) (slots 4t and 4t+1), are restaged in M2(t) (slots 4t+3 and 4t+4).  The closest pair
+  //            is the late half's read and the early half's restaging: two barriers apart.
+  // So the loop never drains the queue.  The last but one K tile stages Xb of the last in its M1 and nothing in its M2, the last
+  // nothing: the last but one waits as every tile before it (6, 2), the last for everything in its L1 (0; nothing is left for L2).
   // The half tile (kNT == 1) is the same loop with one weight half-tile, issue order Xa Wh Xb per K tile:
-  //   L1  reads Xa, Wh of K tile t (12 ds_read_b128)   stages Xb(t + 1)          M1  8 MFMAs: acc[0..1][0]
-  //   L2  reads Xb(t) over Xa (8)                      stages Xa, Wh of t + 2    M2  8 MFMAs: acc[2..3][0]
+  //   L1  reads Xa, Wh of K tile t (12 ds_read_b128)   M1  8 MFMAs: acc[0..1][0]; stages Xb(t + 1)
+  //   L2  reads Xb(t) over Xa (8)                      M2  8 MFMAs: acc[2..3][0]; stages Xa, Wh of t + 2
   // The segments, their barriers and the stagger are those above, so landed and free hold by the same barrier counts: neither
-  // depends on how long an MFMA segment is.  The counts: L1(t) waits for Xb(t) with Xa, Wh, Xb of t + 1 issued behind it, three
-  // half-tiles, vmcnt(6); L2(t) waits for Xa, Wh of t + 1 with Xb(t+1), Xa, Wh of t + 2 behind them, vmcnt(6) again; the prologue
-  // issues Xa Wh Xb of tile 0 and Xa Wh of tile 1 and waits for the first two: vmcnt(6).  The last but one K tile: 6 in L1 (it
-  // still stages Xb of the last tile), 2 in L2 (only that Xb is behind Xa, Wh of the last tile); the last: 0 in L1.
-  constexpr int kFly = 2 * (2 + kNT);   // two loads per half-tile x half-tiles in flight behind a counted wait: 8, or 6
+  // depends on how long an MFMA segment is.  The counts: L1(t) waits for Xb(t) with Xa, Wh of t + 1 behind it, vmcnt(4); L2(t)
+  // waits for Xa, Wh of t + 1 with Xb(t+1) behind them, vmcnt(2); the last K tile 0.
+  // The prologue's issue (Xa Wa Wb Xb of K tile 0, Xa Wa Wb of K tile 1) is what M1 and M2 of K tiles -2 and -1 would have issued,
+  // and its wait (kernel entry, finish_item) is for the first three with four behind them, as before.
+  constexpr int kWaitL1 = 2 * (1 + kNT), kWaitL2 = 2;   // loads in flight behind the counted waits: 6 (4), and 2
+  constexpr int kM1At[2] = {4 * kNT - 1, 6 * kNT - 1};                                        // 7, 11 (3, 5)
+  constexpr int kM2At[6] = {2 * kNT - 1, 2 * kNT + 1, 2 * kNT + 3, kNT == 2 ? 9 : 6, 11, 13};   // 3, 5, 7, 9, 11, 13 (1, 3, 5, 6)
   const int kchunks = c.Cin >> 6, ktiles = 9 * kchunks;   // at least 9
   half8 xf[2][4], wa[4], wb[kNT == 2 ? 4 : 1];
   KPos k = first_kpos(kchunks);
+  auto wfrag = [&](int nt, int kk) -> half8 {
+    if constexpr (kNT == 2) return nt ? wb[kk] : wa[kk];
+    else return wa[kk];
+  };
+
+  // An MFMA segment: the 8 kNT MFMAs of acc[2 kSeg .. 2 kSeg + 1][..] with that segment's kP staging pieces between them
+  auto mseg = [&](auto seg, auto pieces, int cur, int tap, uint32_t dx, uint32_t dw) {
+    constexpr int kSeg = decltype(seg)::v, kP = decltype(pieces)::v;
+#if ELFNET_CONV3X3_PRIO == 0
+    __builtin_amdgcn_s_setprio(1);
+#endif
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+      for (int nt = 0; nt < kNT; ++nt)
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+          acc[2 * kSeg + m][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wfrag(nt, kk), xf[m][kk], acc[2 * kSeg + m][nt], 0, 0, 0);
+          const int at = (kk * kNT + nt) * 2 + m;
+#pragma unroll
+          for (int p = 0; p < kP; ++p)
+            if (at == (kSeg == 0 ? kM1At[p] : kM2At[p])) {
+              __builtin_amdgcn_sched_barrier(0);
+              if constexpr (kSeg == 0) stage_x_piece(c, rw, 1, p, tap, dx, cur ^ 1);
+              else if (p < 2) stage_x_piece(c, rw, 0, p, tap, dx, cur);
+              else stage_w_piece<kNT>(c, rw, (p - 2) >> 1, p & 1, dw, cur);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+#if ELFNET_CONV3X3_PRIO == 0
+    __builtin_amdgcn_s_setprio(0);
+#endif
+    __builtin_amdgcn_sched_barrier(0);
+    raw_barrier();
+  };
 
   // mode 0: a K tile with two more behind it; 1: the last but one; 2: the last
   auto ktile = [&](auto mode, int t) {
     constexpr int kMode = decltype(mode)::v;
-    const int cur = t & 1, nxt = cur ^ 1;
+    const int cur = t & 1;
     const char* b = lds + cur * kBufBytes;
+    // the pieces' wave-uniform offsets are made here, in a load segment, so that among the MFMAs a piece is a select, an add and
+    // the load
+    uint32_t dx1 = 0, dx2 = 0, dw2 = 0;
+    if constexpr (kMode <= 1) dx1 = x_delta(c, k.tap1, k.kc1);
+    if constexpr (kMode == 0) { dx2 = x_delta(c, k.tap2, k.kc2); dw2 = w_delta(c, k.tap2, k.kc2); }
+    asm volatile("" : "+s"(dx1), "+s"(dx2), "+s"(dw2));
     // L1
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
@@ -275,52 +345,26 @@ __device__ __forceinline__ void main_loop(const Ctx& c, const Rows& rw, floatx16
       xf[1][kk] = ldx(b, 1, kk);
       if constexpr (kNT == 2) wb[kk] = ldw(b, 1, kk);
     }
-    if constexpr (kMode <= 1) stage_x(c, rw, 1, k.tap1, k.kc1, nxt);
-    wait_staged<kMode == 2 ? 0 : kFly, true>();
+    wait_staged<kMode == 2 ? 0 : kWaitL1, true>();
     raw_barrier();
     // M1
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[kk], xf[0][kk], acc[0][0], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[kk], xf[1][kk], acc[1][0], 0, 0, 0);
-      if constexpr (kNT == 2) {
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[kk], xf[0][kk], acc[0][1], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[kk], xf[1][kk], acc[1][1], 0, 0, 0);
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    raw_barrier();
+    mseg(Mode<0>{}, Mode<kMode <= 1 ? 2 : 0>{}, cur, k.tap1, dx1, 0);
     // L2
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
       xf[0][kk] = ldx(b, 2, kk);
       xf[1][kk] = ldx(b, 3, kk);
     }
-    if constexpr (kMode == 0) {
-      stage_x(c, rw, 0, k.tap2, k.kc2, cur); stage_w<kNT>(c, rw, 0, k.tap2, k.kc2, cur);
-      if constexpr (kNT == 2) stage_w<kNT>(c, rw, 1, k.tap2, k.kc2, cur);
-    }
-    wait_staged<kMode == 0 ? kFly : kMode == 1 ? 2 : 0, true>();
+    wait_staged<kMode == 2 ? 0 : kWaitL2, true>();
     raw_barrier();
     // M2
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      acc[2][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[kk], xf[0][kk], acc[2][0], 0, 0, 0);
-      acc[3][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[kk], xf[1][kk], acc[3][0], 0, 0, 0);
-      if constexpr (kNT == 2) {
-        acc[2][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[kk], xf[0][kk], acc[2][1], 0, 0, 0);
-        acc[3][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[kk], xf[1][kk], acc[3][1], 0, 0, 0);
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    raw_barrier();
+    mseg(Mode<1>{}, Mode<kMode == 0 ? 2 + 2 * kNT : 0>{}, cur, k.tap2, dx2, dw2);
   };
   const int late = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8);   // waves 4..7: the second wave of every SIMD
   if (late) raw_barrier();
+#if ELFNET_CONV3X3_PRIO == 2
+  if (late) __builtin_amdgcn_s_setprio(1);
+#endif
   for (int t = 0; t < ktiles - 2; ++t) {
     ktile(Mode<0>{}, t);
     k.tap1 = k.tap2; k.kc1 = k.kc2;
@@ -328,6 +372,9 @@ __device__ __forceinline__ void main_loop(const Ctx& c, const Rows& rw, floatx16
   }
   ktile(Mode<1>{}, ktiles - 2);
   ktile(Mode<2>{}, ktiles - 1);
+#if ELFNET_CONV3X3_PRIO == 2
+  __builtin_amdgcn_s_setprio(0);
+#endif
   if (!late) raw_barrier();
   // Barriers of one item, per wave: the prologue's, 4 per K tile, and the stagger's one (in front of the loop for waves 4..7,
   // behind it for waves 0..3): 4 ktiles + 2 for every wave, so the items of a workgroup stay paired whatever their kind.  Behind
