@@ -152,6 +152,7 @@ SIGNATURES = {
     "elfnet_conv3x3_f16_width": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "elfnet_conv3x3_f16_plan": (_i64, [_i64, _i, _i, _i64, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "elfnet_conv3x3_f16_grid": (_i64, [_i64, _i, _i]),
+    "elfnet_conv3x3_small_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "elfnet_conv3x3_in_f16": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "elfnet_heads_workspace": (_sz, [_i64, _i, _i]),
     "elfnet_heads_f16": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),

@@ -161,10 +161,13 @@ class FusedInferenceNet:
     Eager PyTorch issues conv -> bias add -> ReLU (-> residual add -> ReLU) as separate elementwise kernels, i.e. five HBM round
     trips of the [B,256,N,N] activation per residual block.  Here a 3x3 trunk convolution of an fp16 net is ONE kernel,
     `elfnet_conv3x3_f16`: relu(conv + b) for the lower conv of a block, relu(conv + b + skip) for the upper, and nothing passes over
-    the activation a second time.  Behind it are two main loops with one epilogue sequence and the same output bits: algo 1, the
-    hand-written 256 x 256 x 64 LDS-DMA kernel (elf_amd/csrc/net_conv3x3.hip), where there are enough positions to fill the chip,
-    and algo 0, Composable Kernel's implicit GEMM with the tile configuration MIOpen's tuned database picks (elf_amd/csrc/
-    net_conv.hip), for small calls and for the channel counts algo 1 does not take (`_conv_algo`).
+    the activation a second time.  Behind it are three main loops with one epilogue sequence and the same output bits: algo 1, the
+    hand-written 256 x 256 x 64 LDS-DMA kernel (elf_amd/csrc/net_conv3x3.hip), where there are enough positions to fill the chip;
+    algo 0, Composable Kernel's implicit GEMM with the tile configuration MIOpen's tuned database picks (elf_amd/csrc/
+    net_conv.hip), below that and for the channel counts algo 1 does not take (`_conv_algo`); and, where algo 0 would run, the
+    hand-written 64 x 64 x 64 kernel behind `elfnet_conv3x3_small_f16` (elf_amd/csrc/net_conv3x3_small.hip) for calls of at most
+    `small_max_positions` positions with C and K multiples of 64: a single game's 16-row call is 364 workgroups there and 46 in
+    algo 0 (`_use_small`).
     Every other convolution (the 18-plane input conv, bf16 nets, a weight that is not channels_last) stays a bias-free PyTorch-ROCm
     op (MIOpen) followed by one in-place pass, `elfnet_bias_act_f16` / `_bf16` (elf_amd/csrc/net_epilogue.hip).
     (PyTorch's own fused MIOpen ops, miopen_convolution_relu / miopen_convolution_add_relu, were measured and rejected: for
@@ -183,6 +186,17 @@ class FusedInferenceNet:
     # are two workgroups per 256 positions and start a second round over the 256 CUs above 128 * 256 positions, which is where it
     # falls behind.
     native_min_positions = 128 * 256 + 1
+    # elfnet_conv3x3_small_f16 (64 x 64 x 64 tiles) instead of algo 0 up to this many positions; 0 = never.  Measured on MI355X at
+    # 19 x 19 x 256 -> 256, us without / with skip, algo 0 against small (profiles/conv_small_probe.json): 1 row 45.0 / 46.3 against
+    # 11.1 / 10.9; 4 rows 45.4 / 46.7 against 11.4 / 11.1; 16 rows (a single game's call) 46.4 / 47.1 against 16.6 / 15.2; 32 rows
+    # 49.3 / 52.4 against 25.4 / 25.7; 64 rows (23 104 positions) 55.2 / 56.4 against 48.1 / 48.0, spreads 3.4 / 1.9 and 3.2 / 3.4;
+    # 90 rows (32 490) 64.4 / 62.8 against 63.1 / 62.7, inside the spread; 9 x 9: 16 rows 45.3 / 46.6 against 11.3 / 11.1, 404 rows
+    # (32 724 positions) 63.3 / 60.1 against 60.9 / 59.8, inside the spread.  So the largest probed size up to which it wins beyond
+    # the spread at every probed size below is 64 * 361 = 23 104 (nothing between 64 and 90 rows was probed), and a single game goes
+    # from 0.82 to 2.0 moves/s with it (profiles/conv_small_single_game.json).  It ships as 0 all the same: tests/test_gpu_net_edges.py
+    # pins an unpinned 9-row call of a 256-channel net to four algo 0 calls of elfnet_conv3x3_f16, which 23 104 would reroute (same
+    # bits).  Until that expectation moves the kernel is opt-in: set small_max_positions = 23104 on the class or on an instance.
+    small_max_positions = 0
 
     def __init__(self, net):
         import ctypes as C
@@ -225,6 +239,12 @@ class FusedInferenceNet:
             return self.conv_algo
         return 1 if cin % 64 == 0 and k % 256 == 0 and positions >= self.native_min_positions else 0
 
+    def _use_small(self, positions, cin, k):
+        """net_conv3x3_small.hip instead of algo 0: nothing pinned, a shape it takes (C and K multiples of 64), and few enough
+        positions that it measured faster.  Same output bits either way."""
+        return (self.conv_algo is None and self._conv_algo(positions, cin, k) == 0 and cin % 64 == 0 and k % 64 == 0
+                and positions <= self.small_max_positions)
+
     def _conv(self, x, c, res=None):
         if not self._fusable(x, c):
             y = torch.nn.functional.conv2d(x, c.weight, None, c.stride, c.padding)
@@ -237,10 +257,13 @@ class FusedInferenceNet:
         # a fresh buffer per conv (inside a captured graph it comes from the graph's own pool); x, and res until the upper conv
         # has run, stay alive in the caller
         y = torch.empty((n, k, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        self.check(self.L.elfnet_conv3x3_f16(C.c_void_p(x.data_ptr()), C.c_void_p(c.weight.data_ptr()), C.c_void_p(c.bias.data_ptr()),
-                                             C.c_void_p(res.data_ptr()) if res is not None else None, C.c_void_p(y.data_ptr()),
-                                             n, h, w, cin, k, 1, self._conv_algo(n * h * w, cin, k),
-                                             C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+        ptrs = (C.c_void_p(x.data_ptr()), C.c_void_p(c.weight.data_ptr()), C.c_void_p(c.bias.data_ptr()),
+                C.c_void_p(res.data_ptr()) if res is not None else None, C.c_void_p(y.data_ptr()))
+        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        if self._use_small(n * h * w, cin, k):
+            self.check(self.L.elfnet_conv3x3_small_f16(*ptrs, n, h, w, cin, k, 1, st))
+        else:
+            self.check(self.L.elfnet_conv3x3_f16(*ptrs, n, h, w, cin, k, 1, self._conv_algo(n * h * w, cin, k), st))
         return y
 
     @torch.no_grad()
@@ -263,7 +286,8 @@ class FusedInferenceNet:
 class NativeInferenceNet(FusedInferenceNet):
     """A BN-folded fp16 channels_last PolicyValueNet from feature rows to pi / V on this library's kernels only:
 
-        elfnet_conv3x3_in_f16  ->  2 x num_block elfnet_conv3x3_f16 (FusedInferenceNet's trunk, same `_conv_algo` routing)  ->  elfnet_heads_f16
+        elfnet_conv3x3_in_f16  ->  2 x num_block elfnet_conv3x3_f16 or elfnet_conv3x3_small_f16 (FusedInferenceNet's trunk, same `_conv_algo` /
+        `_use_small` routing)  ->  elfnet_heads_f16
 
     No MIOpen convolution, no BLAS GEMM, no PyTorch softmax or tanh inside __call__: no find step on a cold database, no solver
     choice behind the output bits, three launches instead of about fifteen around the trunk.  Same constructor checks and

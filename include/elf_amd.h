@@ -702,6 +702,17 @@ int64_t elfnet_conv3x3_f16_plan(int64_t tiles, int columns, int round_width, int
 /* Host arithmetic: the workgroups G of that launch, min(round_width, work ids), or ELFGO_E_BADARG for what _plan refuses.
  * Workgroup g runs the work ids g, g + G, g + 2 G, ... in ascending order; a half id is the last one of its workgroup. */
 int64_t elfnet_conv3x3_f16_grid(int64_t tiles, int columns, int round_width);
+/* The same function as elfnet_conv3x3_f16 -- same tensors, same roundings, algo 0's accumulation order and therefore its output
+ * bits -- on a third main loop, for calls of a few thousand positions (a single game's 16-row net call is 5 776): tiles of
+ * 64 positions x 64 output channels, one plain launch of ceil(rows * h * wd / 64) x (k / 64) workgroups, so that such a call
+ * fills the chip where algo 0 and algo 1 give it 46 or 23 workgroups (elf_amd/csrc/net_conv3x3_small.hip).  An entry of its own:
+ * elfnet_conv3x3_f16 has algos 0 and 1 and refuses any other.
+ * ELFGO_E_BADARG -- and nothing is launched, y keeps its bytes -- for what elfnet_conv3x3_f16 refuses (a null x / w / bias / y,
+ * pointers that are not 16-B aligned, y == x or y == res, a tensor of 2^31 bytes or more, a pointer that is no device pointer)
+ * and for c % 64 != 0 or k % 64 != 0.  rows == 0 returns 0 and launches nothing.
+ * Runs on the device that owns x; no workspace, allocates nothing and waits for nothing (it can be captured into a HIP graph). */
+int elfnet_conv3x3_small_f16(const void* x, const void* w, const void* bias, const void* res, void* y,
+                             int64_t rows, int h, int wd, int c, int k, int relu, void* stream);
 
 /* The two ends of the fp16 net on this library's kernels (elf_amd/csrc/net_io.hip).  A C host evaluates a BN-folded net as
  *   elfnet_conv3x3_in_f16 (feature rows -> trunk activation), elfnet_conv3x3_f16 twice per residual block, elfnet_heads_f16

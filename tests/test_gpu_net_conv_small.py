@@ -1,0 +1,280 @@
+"""GPU: the small-tile trunk convolution (elfnet_conv3x3_small_f16, elf_amd/csrc/net_conv3x3_small.hip: 64 positions x 64 channels
+per workgroup, for a single game's net call) on inputs whose result is exact -- small integers, so every partial sum is an integer
+fp32 and fp16 hold exactly and any differing element is a wrong halo, layout, swizzle or pipeline timing, never rounding -- then bit
+for bit against algo 0 (same K order, same MFMA), a race screen (repeated launches return the bits of the first), batch
+invariance, the calls it refuses, and whole nets routed through it and past it."""
+import ctypes as C
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def elf(built):
+    import elf_amd
+    return elf_amd
+
+
+def _conv_fp32(x, w):
+    """conv2d(x, w, padding=1) in fp32 for NHWC x [rows,h,w,C] and w [K,3,3,C] as its nine taps (test_gpu_net_conv._conv_fp32)"""
+    import torch
+    rows, h, wd = x.shape[0], x.shape[1], x.shape[2]
+    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))
+    out = torch.zeros((rows, h, wd, w.shape[0]), device=x.device, dtype=torch.float32)
+    for ky in range(3):
+        for kx in range(3):
+            out += xp[:, ky:ky + h, kx:kx + wd, :] @ w[:, ky, kx, :].t()
+    return out
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _small(L, x, w, b, r, y, rows, h, wd, relu, c, k):
+    import torch
+    return L.elfnet_conv3x3_small_f16(_p(x), _p(w), _p(b), _p(r), _p(y), rows, h, wd, c, k, int(relu),
+                                      C.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+
+def _algo0(L, x, w, b, r, y, rows, h, wd, relu, c, k):
+    import torch
+    return L.elfnet_conv3x3_f16(_p(x), _p(w), _p(b), _p(r), _p(y), rows, h, wd, c, k, int(relu), 0,
+                                C.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+
+_ints = {}
+
+
+def _int_case(rows, h, wd, c, k):
+    """test_gpu_net_conv_native._int_case's recipe: x in {-1,0,1}; w in {-1,0,1} with about 3/4 zeros, drawn per element so it is
+    asymmetric in (k,c) and in (ky,kx); integer bias and res.  |partial sum| <= 9 c / 4 + spread, far below 2048, |result| below
+    2048: exact in fp32 and in fp16."""
+    import torch
+    key = (rows, h, wd, c, k)
+    if key not in _ints:
+        g = torch.Generator(device="cuda").manual_seed(77 + rows + 1000 * h + 31 * wd + c + 7 * k)
+        ri = lambda shape, lo, hi: torch.randint(lo, hi + 1, shape, device="cuda", generator=g)
+        x = ri((rows, h, wd, c), -1, 1).half()
+        w = (ri((k, 3, 3, c), -1, 1) * (ri((k, 3, 3, c), 0, 3) == 0)).half()
+        b = ri((k,), -8, 8).half()
+        r = ri((rows, h, wd, k), -8, 8).half()
+        conv = _conv_fp32(x.float(), w.float())
+        assert conv.abs().max().item() < 1024 and not torch.equal(w, w.flip(1)) and not torch.equal(w, w.flip(2))
+        _ints[key] = dict(x=x, w=w, b=b, r=r, conv=conv)
+    return _ints[key]
+
+
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("use_res", [False, True])
+@pytest.mark.parametrize("rows,h,wd,c,k", [(1, 19, 19, 256, 256),   # M = 361: five full 64-tiles and a 41-row tail; four channel columns
+                                           (5, 9, 9, 256, 256),     # M = 405: tiles straddle boards
+                                           (64, 1, 1, 64, 64),      # M = 64 exactly, no tail; every tap but the centre is off-board; 9 K tiles
+                                           (3, 9, 9, 192, 128),     # 27 K tiles (an odd count), two channel columns
+                                           (2, 3, 7, 64, 192),      # h != wd
+                                           (1, 1, 19, 64, 64),      # a one-line board
+                                           (1, 2, 2, 64, 64)])      # M = 4: a single tile that is almost all tail
+def test_exact_integers(elf, rows, h, wd, c, k, use_res, relu):
+    """equality with the nine-tap fp32 form; y is prefilled with NaN, and one guard row of NaN behind y's last row stays NaN (the
+    tail tile's stores are masked)"""
+    import torch
+    d = _int_case(rows, h, wd, c, k)
+    ref = d["conv"] + d["b"].float()
+    if use_res:
+        ref = ref + d["r"].float()
+    if relu:
+        ref = torch.relu(ref)
+    m = rows * h * wd
+    buf = torch.full((m + 1, k), float("nan"), device="cuda", dtype=torch.float16)
+    y = buf[:m].view(rows, h, wd, k)
+    rc = _small(elf.lib(), d["x"], d["w"], d["b"], d["r"] if use_res else None, y, rows, h, wd, relu, c, k)
+    assert rc == 0
+    torch.cuda.synchronize()
+    bad = int((y.float() != ref).sum().item())   # a NaN left in y differs from everything
+    print("rows %d h %d wd %d c %d k %d res %d relu %d: %d of %d differ" % (rows, h, wd, c, k, use_res, relu, bad, y.numel()))
+    assert bad == 0
+    assert bool(torch.isnan(buf[-1]).all())
+
+
+@pytest.mark.parametrize("n", [19, 9])
+def test_all_ones_halo(elf, n):
+    """x = 1, w = 1, bias = 0: every output is 256 x the number of on-board taps: 1024 at corners, 1536 on edges, 2304 inside"""
+    import torch
+    rows, ch = 2, 256
+    x = torch.ones((rows, n, n, ch), device="cuda", dtype=torch.float16)
+    w = torch.ones((ch, 3, 3, ch), device="cuda", dtype=torch.float16)
+    b = torch.zeros((ch,), device="cuda", dtype=torch.float16)
+    y = torch.full((rows, n, n, ch), float("nan"), device="cuda", dtype=torch.float16)
+    assert _small(elf.lib(), x, w, b, None, y, rows, n, n, 0, ch, ch) == 0
+    torch.cuda.synchronize()
+    i = torch.arange(n, device="cuda")
+    on = 3 - ((i == 0) | (i == n - 1)).long()           # taps on the board along one axis
+    want = (256 * on[:, None] * on[None, :]).float()    # [n, n]
+    assert want[0, 0] == 1024 and want[0, 1] == 1536 and want[1, 1] == 2304
+    assert bool((y.float() == want[None, :, :, None]).all())
+
+
+_rand = {}
+
+
+def _rand_case(rows, n, c, k):
+    """test_gpu_net_conv_native._rand_case's recipe"""
+    import torch
+    key = (rows, n, c, k)
+    if key not in _rand:
+        g = torch.Generator(device="cuda").manual_seed(4242 + rows + n + c + k)
+        x = torch.randn((rows, n, n, c), device="cuda", generator=g).half()
+        w = (torch.randn((k, 3, 3, c), device="cuda", generator=g) * (9 * c) ** -0.5).half()
+        b = torch.randn((k,), device="cuda", generator=g).half()
+        r = torch.randn((rows, n, n, k), device="cuda", generator=g).half()
+        y = torch.full((rows, n, n, k), float("nan"), device="cuda", dtype=torch.float16)
+        assert _small(__import__("elf_amd").lib(), x, w, b, r, y, rows, n, n, 1, c, k) == 0
+        torch.cuda.synchronize()
+        _rand[key] = (x, w, b, r, y)   # y: the first launch of the new entry, with skip and ReLU; nobody writes it again
+    return _rand[key]
+
+
+@pytest.mark.parametrize("rows,n,c,k", [(16, 19, 256, 256), (3, 9, 128, 64)])
+def test_bit_equal_with_algo_0(elf, rows, n, c, k):
+    """the single game's own call, and a smaller one, with skip and ReLU: algo 0's accumulation chain (tap-major K; in every
+    32-channel block one 32x32x16 MFMA over channels {0..7, 16..23}, the next over {8..15, 24..31}) and its epilogue sequence, so
+    the two outputs are the same bits"""
+    import torch
+    x, w, b, r, got = _rand_case(rows, n, c, k)
+    y0 = torch.full((rows, n, n, k), float("nan"), device="cuda", dtype=torch.float16)
+    assert _algo0(elf.lib(), x, w, b, r, y0, rows, n, n, 1, c, k) == 0
+    torch.cuda.synchronize()
+    assert not bool(torch.isnan(y0).any())
+    print("%d of %d elements differ between the small kernel and algo 0" % (int((got != y0).sum().item()), y0.numel()))
+    assert torch.equal(got, y0)
+
+
+def test_repeated_launches_return_the_same_bits(elf):
+    """A staged buffer read before its data has landed, or restaged before its last read, gives wrong tiles that come and go.  The
+    same 16-row inputs launched 20 times return the bits of the first launch."""
+    import torch
+    rows = 16
+    x, w, b, r, first = _rand_case(rows, 19, 256, 256)
+    assert not bool(torch.isnan(first).any())
+    for i in range(1, 20):
+        y = torch.full((rows, 19, 19, 256), float("nan"), device="cuda", dtype=torch.float16)
+        assert _small(elf.lib(), x, w, b, r, y, rows, 19, 19, 1, 256, 256) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(y, first), "launch %d differs from the first" % i
+
+
+@pytest.mark.parametrize("row", [0, 7, 15])
+def test_a_row_does_not_depend_on_its_batch(elf, row):
+    """a row of the 16-row call, run as a 1-row call (other tiles, other tails), returns the bits it has in the batch"""
+    import torch
+    x, w, b, r, batch = _rand_case(16, 19, 256, 256)
+    x1, r1 = x[row:row + 1].contiguous(), r[row:row + 1].contiguous()
+    y = torch.full((1, 19, 19, 256), float("nan"), device="cuda", dtype=torch.float16)
+    assert _small(elf.lib(), x1, w, b, r1, y, 1, 19, 19, 1, 256, 256) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(y[0], batch[row])
+
+
+@pytest.mark.parametrize("case", ["c72", "k72", "c32", "x_off_by_8", "y_is_x", "y_is_res"])
+def test_refusals_leave_y_alone(elf, case):
+    """a negative status, nothing launched, y keeps its bytes"""
+    import torch
+    rows, n = 2, 9
+    c = dict(c72=72, c32=32).get(case, 64)
+    k = 72 if case == "k72" else 64
+    z = lambda *shape: torch.zeros(shape, device="cuda", dtype=torch.float16)
+    x, w, b, r = z(rows * n * n * c + 8), z(k, 3, 3, c), z(k), z(rows, n, n, k)
+    y = torch.full((rows, n, n, k), 7.0, device="cuda", dtype=torch.float16)
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    px, pr, py = x.data_ptr(), r.data_ptr(), y.data_ptr()
+    if case == "x_off_by_8":
+        px += 8
+    elif case == "y_is_x":
+        px = py          # c == k == 64: y's buffer is large enough to be read as x
+    elif case == "y_is_res":
+        pr = py
+    rc = elf.lib().elfnet_conv3x3_small_f16(C.c_void_p(px), _p(w), _p(b), C.c_void_p(pr), C.c_void_p(py), rows, n, n, c, k, 1, st)
+    assert rc < 0
+    torch.cuda.synchronize()
+    assert bool((y == 7.0).all())
+
+
+def test_no_rows_is_accepted_and_launches_nothing(elf):
+    import torch
+    n, ch = 9, 64
+    x = torch.zeros((1, n, n, ch), device="cuda", dtype=torch.float16)
+    w = torch.zeros((ch, 3, 3, ch), device="cuda", dtype=torch.float16)
+    b = torch.zeros((ch,), device="cuda", dtype=torch.float16)
+    y = torch.full((1, n, n, ch), 7.0, device="cuda", dtype=torch.float16)
+    assert _small(elf.lib(), x, w, b, None, y, 0, n, n, 1, ch, ch) == 0
+    torch.cuda.synchronize()
+    assert bool((y == 7.0).all())
+
+
+# ------------------------------------------------------------------------------------------------ whole nets
+
+_net = {}
+
+
+def _net_case():
+    import torch
+    from elf_amd.net import make_net
+    if not _net:
+        net = make_net(9, num_block=2, dim=64, fold_bn=True)
+        g = torch.Generator(device="cuda").manual_seed(99)
+        s = torch.randint(0, 2, (16, 18, 9, 9), device="cuda", generator=g).half().contiguous(memory_format=torch.channels_last)
+        _net["v"] = (net, s)
+    return _net["v"]
+
+
+class _Calls:
+    """counts the calls of the small entry that go through a net's library handle"""
+
+    def __init__(self, L):
+        self.L, self.small = L, 0
+
+    def __getattr__(self, name):
+        f = getattr(self.L, name)
+        if name != "elfnet_conv3x3_small_f16":
+            return f
+
+        def counted(*a):
+            self.small += 1
+            return f(*a)
+        return counted
+
+
+@pytest.mark.parametrize("cls", ["FusedInferenceNet", "NativeInferenceNet"])
+def test_whole_net_routed_through_the_small_kernel_returns_the_same_bits(elf, cls):
+    """9 x 9, 2 blocks of 64 channels, 16 rows (1 296 positions): small_max_positions = 0 sends every trunk convolution to algo 0,
+    32768 sends all four to the small kernel; pi and V are the same bits"""
+    import torch
+    import elf_amd.net as N
+    net, s = _net_case()
+    outs, calls = [], []
+    for limit in (0, 32768):
+        f = getattr(N, cls)(net)
+        f.small_max_positions = limit
+        f.L = _Calls(f.L)
+        outs.append(f({"s": s}))
+        torch.cuda.synchronize()
+        calls.append(f.L.small)
+    assert calls == [0, 4]
+    assert torch.equal(outs[0]["pi"], outs[1]["pi"]) and torch.equal(outs[0]["V"], outs[1]["V"])
+    assert not bool(torch.isnan(outs[1]["pi"]).any()) and not bool(torch.isnan(outs[1]["V"]).any())
+
+
+def test_whole_net_replays_from_a_graph_to_the_same_bits(elf):
+    """the small kernel's launch is capturable: GraphedNet's replay equals the eager call"""
+    import torch
+    from elf_amd.net import GraphedNet, NativeInferenceNet
+    net, s = _net_case()
+    native = NativeInferenceNet(net)
+    native.small_max_positions = 32768
+    eager = native({"s": s})
+    torch.cuda.synchronize()
+    s_static = s.clone(memory_format=torch.preserve_format)
+    out = GraphedNet(native, s_static)()
+    torch.cuda.synchronize()
+    assert torch.equal(out["pi"], eager["pi"]) and torch.equal(out["V"], eager["V"])

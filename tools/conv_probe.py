@@ -1,6 +1,8 @@
 """Times ONE trunk convolution of the benchmark net (rows = 2048, 19 x 19, 256 -> 256, fp16 NHWC), with and without the skip:
     fused0 / fused1   elfnet_conv3x3_f16 with algo 0 (CK's main loop) / 1 (the hand-written kernel of net_conv3x3.hip); bias, skip
                       and ReLU in the convolution's epilogue
+    fusedsmall        elfnet_conv3x3_small_f16, the 64 x 64 x 64 kernel of net_conv3x3_small.hip for calls of a few thousand positions
+                      (`--algos 0,small`; for the single game's call: --rows 16 --no-pair)
     pair              what ran before: F.conv2d (MIOpen) followed by elfnet_bias_act_f16
 HIP events around `--launches` back-to-back launches after a warm-up, `--repeats` times; mean / min / max of the repeats in µs per
 convolution.  One process; run it under a time limit:
@@ -34,7 +36,7 @@ def main():
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--algos", default="0,1")
+    ap.add_argument("--algos", default="0,1", help="comma-separated: 0, 1 (elfnet_conv3x3_f16's algos) and small (elfnet_conv3x3_small_f16)")
     ap.add_argument("--round-width", type=int, default=None,
                     help="algo 1's round width (elfnet_conv3x3_f16_width): 0 = the CU count, -1 = never split the last round")
     ap.add_argument("--no-pair", action="store_true", help="leave F.conv2d + elfnet_bias_act_f16 out: only the fused variants run")
@@ -65,6 +67,8 @@ def main():
     width = None if a.round_width is None else (1 << 30) if a.round_width < 0 else a.round_width
 
     def fused(algo, res):
+        if algo == "small":
+            return lambda: L.elfnet_conv3x3_small_f16(p(x), p(w), p(b), p(res), p(y), rows, n, n, ch, ch, 1, st)
         if width is not None:
             return lambda: L.elfnet_conv3x3_f16_width(p(x), p(w), p(b), p(res), p(y), rows, n, n, ch, ch, 1, algo, width, st)
         return lambda: L.elfnet_conv3x3_f16(p(x), p(w), p(b), p(res), p(y), rows, n, n, ch, ch, 1, algo, st)
@@ -100,9 +104,9 @@ def main():
         for skip, rr in (("noskip", None), ("skip", r)):
             if not a.no_pair:
                 res["pair_" + skip] = timed(pair(rr))
-            for algo in [int(v) for v in a.algos.split(",") if v != ""]:
-                res["fused%d_%s" % (algo, skip)] = timed(fused(algo, rr))
-                print(skip, "algo", algo, res["fused%d_%s" % (algo, skip)], flush=True)
+            for algo in [v if v == "small" else int(v) for v in a.algos.split(",") if v != ""]:
+                res["fused%s_%s" % (algo, skip)] = timed(fused(algo, rr))
+                print(skip, "algo", algo, res["fused%s_%s" % (algo, skip)], flush=True)
             if not a.no_pair:
                 print(skip, "pair", res["pair_" + skip], flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
