@@ -73,6 +73,7 @@ SIGNATURES = {
     "elfmcts_select": (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "elfmcts_expand": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp]),
     "elfmcts_root": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "elfmcts_analyze": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "elfmcts_advance": (_i, [_vp, _vp, _vp]),
     "elfmcts_validate": (_i, [_vp, _vp]),
     "elfmcts_node_visits": (_i, [_vp, _vp]),
@@ -129,6 +130,9 @@ SIGNATURES = {
     "elfsp_take_finished": (_i, [_vp, _vp, _i]),
     "elfsp_last_score": (_i, [_vp, _vp]),
     "elfsp_last_moves": (_i, [_vp, _vp]),
+    "elfsp_analyze": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "elfsp_set_analysis": (_i, [_vp, _i, _i]),
+    "elfsp_last_analysis": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "elfsp_records_pending": (_i, [_vp]),
     "elfsp_pop_record": (_i, [_vp, _vp, _sz, C.POINTER(_sz)]),
     "elftrain_create": (_i, [_vp, _i, _i, _i, C.c_uint32, C.POINTER(_vp)]),

@@ -169,7 +169,17 @@ struct ElfSelfPlay {
   std::deque<float> finished_values;   // final value of every finished game not yet taken (GameStats::feedWinRate, game_stats.h:41-44)
   std::vector<int32_t> sgf;   // GameOptions.preload_sgf as reference Coords (elfsp_preload)
   int sgf_move_to = -1;       // GameOptions.preload_sgf_move_to
+  // analysis snapshots of the move boundary (elfsp_set_analysis, analysis_host.h): an_moves == 0 = off
+  int an_moves = 0, an_pv = 0;
+  SpBuf<int32_t> an_info, an_coord, an_orig, an_visits, an_pvlen, an_pvs;   // one elfmcts_analyze of a pool: device arrays + mirrors
+  SpBuf<float> an_reward, an_prior;
+  std::vector<int32_t> la_info, la_coord, la_orig, la_visits, la_pvlen, la_pvs;   // per game: what its last finished search saw
+  std::vector<float> la_reward, la_prior;
 };
+// analysis_host.h (included at the end of this file): queue the analysis of pool a's trees behind the root fetch / keep the rows
+// of the games whose search has just finished
+static int sp_analysis_queue(ElfSelfPlay* sp, int a);
+static void sp_analysis_keep(ElfSelfPlay* sp, const std::vector<int32_t>& games);
 
 #define SPCHK(x)                  \
   do {                            \
@@ -717,8 +727,10 @@ static int sp_finish_moves(ElfSelfPlay* sp, const std::vector<int32_t> (&done)[2
     HIPCHK(sp->prior.down(GE, sp->stream));
     HIPCHK(sp->reward.down(GE, sp->stream));
     if (p.T > 1) SPCHK(elfmcts_thread_draws(p.mcts, p.h_tdraws.data(), sp->stream));
+    if (sp->an_moves > 0) SPCHK(sp_analysis_queue(sp, a));   // the finished searches' candidates and lines, before the move re-roots the trees
     HIPCHK(hipStreamSynchronize(sp->stream));
     if (first_wait) { sp->t_after_drain = std::chrono::steady_clock::now(); first_wait = false; }
+    if (sp->an_moves > 0) sp_analysis_keep(sp, done[a]);
     // online mode, following_pass (mcts_update_info :104-111): Tromp-Taylor score and last move of the game boards
     const bool follow = sp->opt.following_pass != 0;
     if (follow) {
@@ -1300,3 +1312,6 @@ int elfsp_search_log(const ElfSelfPlay* sp, int first, int n, ElfSpSearch* rec, 
 #include "setup_host.h"
 // Ladder reading (elfgo_ladder_map): device code in ladder.cuh, entry point in ladder_host.h, here for the same reason.
 #include "ladder_host.h"
+// Search analysis of the self-play context (elfsp_analyze, elfsp_set_analysis, elfsp_last_analysis): entry points in
+// analysis_host.h over elfmcts_analyze; here because they read this file's ElfSelfPlay.
+#include "analysis_host.h"

@@ -7,7 +7,8 @@ same replies ("= ..." / "? ..."), same coordinate letters (no 'I'): protocol_ver
 clear_board, play, genmove, showboard, final_score, list_commands, quit/exit.  On top of the reference's set (whose `u` / `h`
 commands are commented out, console_lib.py:196-204): undo, fixed_handicap, place_free_handicap, set_free_handicap, loadsgf,
 known_command -- what every GTP front-end sends -- over SelfPlay.setup / SelfPlay.undo; final_status_list and the private
-elf-ownership, elf-score_estimate and elf-ladders over the per-point answers of the board engine.
+elf-ownership, elf-score_estimate and elf-ladders over the per-point answers of the board engine; lz-genmove_analyze (Leela Zero's
+analysing genmove, what Sabaki and Lizzie send) and elf-analysis over the search's candidates and lines (SelfPlay.analyze).
 
     eng = GtpEngine(actor, board_size=19, mcts_rollout_per_thread=1600)     # actor(batch) -> dict(pi=..., V=...)
     eng.loop()                                                               # stdin/stdout, or eng.command("genmove b")
@@ -42,6 +43,27 @@ def xy2move(x, y):
     return chr(x + 65) + str(y + 1)
 
 
+def format_analysis(n, coord, visits, winrate, prior, pv_len, pv):
+    """One game's analysis (a row of each array of SelfPlay.analyze / last_analysis) as Leela-Zero-style text for an N x N board:
+    one `info move <v> visits <n> winrate <w> prior <p> order <k> pv <v> <v> ...` per candidate, in rank order, joined by single
+    spaces on one line.  winrate and prior are round(x * 10000); vertices are xy2move's, `pass` for M_PASS.  No `lcb` field: the
+    engine has no such bound.  An analysis without candidates is the empty string."""
+    S = n + 2
+
+    def vertex(c):
+        c = int(c)
+        return "pass" if c == M_PASS else xy2move(c % S - 1, c // S - 1)
+    out = []
+    for k in range(len(coord)):
+        if int(coord[k]) < 0 or int(visits[k]) <= 0:
+            break
+        line = [vertex(c) for c in pv[k][:int(pv_len[k])]]
+        out.append("info move %s visits %d winrate %d prior %d order %d pv %s" % (
+            vertex(coord[k]), int(visits[k]), int(round(float(winrate[k]) * 10000)), int(round(float(prior[k]) * 10000)), k,
+            " ".join(line)))
+    return " ".join(out)
+
+
 # the reference's HandicapTable (base/go_state.cc:36-45) as GTP vertices, 19x19 only (it has none for 9x9)
 _H4 = ("D4", "Q16", "D16", "Q4")
 _H6 = _H4 + ("D10", "Q10")
@@ -68,6 +90,12 @@ class GtpEngine:
         self.commands["elf-ownership"] = self.commands.pop("elf_ownership")
         self.commands["elf-score_estimate"] = self.commands.pop("elf_score_estimate")
         self.commands["elf-ladders"] = self.commands.pop("elf_ladders")
+        self.commands["elf-analysis"] = self.commands.pop("elf_analysis")
+        self.commands["lz-genmove_analyze"] = self.commands.pop("lz_genmove_analyze")
+        # every finished search leaves its candidates and lines behind (elf-analysis): one small launch per move of one game
+        self.analysis_moves, self.analysis_pv = 10, 16
+        self.sp.set_analysis(self.analysis_moves, self.analysis_pv)
+        self.info_out = None     # loop(): where lz-genmove_analyze streams its info lines while the search runs
 
     def close(self):
         self.boards.close()      # the ownership scratch goes before the engine it was made over
@@ -263,6 +291,50 @@ class GtpEngine:
             return True, "resign"
         return True, self.coord2move(c)
 
+    # ---- search analysis: candidate moves and principal variations (SelfPlay.analyze / last_analysis)
+    def _info_line(self, a):
+        return format_analysis(self.n, a["coord"][0], a["visits"][0], a["winrate"][0], a["prior"][0], a["pv_len"][0], a["pv"][0])
+
+    def on_lz_genmove_analyze(self, items):
+        """lz-genmove_analyze <color> [interval_centiseconds]: genmove that reports what the search is looking at -- an info line
+        whenever the interval has passed, the finished search's line at the end, then `play <vertex>` (or `play resign`).
+        Without an interval only the final line is reported."""
+        import time
+        ret, msg = self.check_player(items[1][0])
+        if not ret:
+            return False, msg
+        interval = float(items[2]) / 100.0 if len(items) > 2 else None
+        if interval is not None and not interval >= 0:
+            return False, "invalid interval"
+        lines = []
+
+        def emit(line):
+            if self.info_out is not None:        # streamed: the reply opens with its first line
+                self.info_out.write(("" if lines else "=\n") + line + "\n")
+                self.info_out.flush()
+            lines.append(line)
+        moves = self.sp.stats()["moves"]
+        last = time.monotonic()
+        while True:
+            self.sp.run()
+            if self.sp.stats()["moves"] != moves:
+                break
+            if interval is not None and time.monotonic() - last >= interval:
+                line = self._info_line(self.sp.analyze(self.analysis_moves, self.analysis_pv))
+                if line:
+                    emit(line)
+                last = time.monotonic()
+        line = self._info_line(self.sp.last_analysis())
+        if line:
+            emit(line)
+        c = int(self.sp.last_moves()[0])
+        emit("play " + ("resign" if c == M_RESIGN else self.coord2move(c)))
+        return True, "\n" + "\n".join(lines)
+
+    def on_elf_analysis(self, items):
+        """The info line of the last finished search (see lz-genmove_analyze); empty before the first one."""
+        return True, self._info_line(self.sp.last_analysis())
+
     def on_showboard(self, items):
         return True, "\n" + self.showboard()
 
@@ -334,7 +406,11 @@ class GtpEngine:
 
     def loop(self, fin=sys.stdin, fout=sys.stdout):
         for line in fin:
-            fout.write(self.command(line.strip()))
+            # lz-genmove_analyze writes its reply line by line while the search runs; what is left to write is the blank line
+            self.info_out = fout if line.split()[:1] == ["lz-genmove_analyze"] else None
+            reply = self.command(line.strip())
+            fout.write("\n" if self.info_out is not None and reply.startswith("= \n") else reply)
+            self.info_out = None
             fout.flush()
             if self.exit:
                 break

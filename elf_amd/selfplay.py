@@ -66,6 +66,21 @@ STAT_FIELDS = ("moves", "games", "rollouts", "rows", "steps", "logged", "steps_p
                "boundaries", "boundary_wait_ns")
 
 
+# the outputs of elfmcts_analyze / elfsp_analyze / elfsp_last_analysis, in argument order
+ANALYSIS_FIELDS = ("info", "coord", "orig", "visits", "reward", "prior", "pv_len", "pv")
+
+
+def with_winrate(a):
+    """adds winrate [G, max_moves] to the arrays of an analysis: the chance of the side to move at the root, (1 + q) / 2 for Black
+    and (1 - q) / 2 for White (info word 3, the root's flip), with q = reward / visits the edge's black-positive mean; 0 where
+    there is no candidate"""
+    vis = a["visits"].astype(np.float64)
+    q = np.divide(a["reward"].astype(np.float64), vis, out=np.zeros_like(vis), where=vis > 0)
+    sign = np.where(a["info"][:, 3:4] != 0, -1.0, 1.0)
+    a["winrate"] = np.where(vis > 0, (1.0 + sign * q) / 2.0, 0.0)
+    return a
+
+
 class SelfPlay:
     """G self-play games stepped together on one GPU; trees, boards and leaf features live in HBM.
 
@@ -351,6 +366,39 @@ class SelfPlay:
         out = np.zeros(self.num_games, np.int32)
         check(self.L.elfsp_last_moves(self._h, out.ctypes.data))
         return out
+
+    # ---- search analysis (elfmcts_analyze): candidate moves and principal variations
+    def analyze(self, max_moves=10, max_pv=16, actor=0):
+        """The candidates of every game's root in AI `actor`'s trees and the line the search expects below each, as a dict of
+        numpy arrays: info [G, 8], coord / orig / visits / reward / prior / pv_len [G, max_moves], pv [G, max_moves, max_pv]
+        (include/elf_amd.h, elfmcts_analyze) and winrate [G, max_moves].  Call it between two steps; waits for the device."""
+        G, mm, mp = self.num_games, int(max_moves), int(max_pv)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        t = dict(info=torch.zeros((G, 8), **i32), coord=torch.zeros((G, max(mm, 0)), **i32), orig=torch.zeros((G, max(mm, 0)), **i32),
+                 visits=torch.zeros((G, max(mm, 0)), **i32), reward=torch.zeros((G, max(mm, 0)), **f32),
+                 prior=torch.zeros((G, max(mm, 0)), **f32), pv_len=torch.zeros((G, max(mm, 0)), **i32),
+                 pv=torch.zeros((G, max(mm, 0), max(mp, 0)), **i32))
+        check(self.L.elfsp_analyze(self._h, int(actor), mm, mp, *(C.c_void_p(t[k].data_ptr()) for k in ANALYSIS_FIELDS), self._stream()))
+        (getattr(self, "stream", None) or torch.cuda.current_stream(self.device)).synchronize()
+        return with_winrate({k: a.cpu().numpy() for k, a in t.items()})
+
+    def set_analysis(self, max_moves=10, max_pv=16):
+        """Keep the analysis of every search that finishes at a move boundary (one small launch per boundary); 0, 0 = off, the
+        default.  last_analysis() reports it."""
+        check(self.L.elfsp_set_analysis(self._h, int(max_moves), int(max_pv)))
+        self._analysis = (int(max_moves), int(max_pv))
+
+    def last_analysis(self):
+        """per game: what its last finished search saw (arrays as analyze()); 0 candidates while analysis is off or before the
+        game's first search under it has finished.  The companion of last_moves()."""
+        G = self.num_games
+        mm, mp = getattr(self, "_analysis", (0, 0))
+        a = dict(info=np.zeros((G, 8), np.int32), coord=np.zeros((G, mm), np.int32), orig=np.zeros((G, mm), np.int32),
+                 visits=np.zeros((G, mm), np.int32), reward=np.zeros((G, mm), np.float32), prior=np.zeros((G, mm), np.float32),
+                 pv_len=np.zeros((G, mm), np.int32), pv=np.zeros((G, mm, mp), np.int32))
+        check(self.L.elfsp_last_analysis(self._h, *(a[k].ctypes.data if a[k].size else None for k in ANALYSIS_FIELDS)))
+        return with_winrate(a)
 
     def validate_trees(self):
         """elfmcts_validate: (violations, code, game, node, position) of the node-record invariants; synchronises (tests / debugging)"""

@@ -255,6 +255,31 @@ int elfmcts_expand(ElfMcts* m, const float* pi, int64_t pi_stride_floats, const 
 /* root edges in the reference's iteration order (what MCTSResultT::addActions walks, tree_search_base.h:237-294);
  * info device int32 [num_games][ELFMCTS_ROOT_WORDS]; the per-edge outputs ([num_games][edge_stride]) may be NULL */
 int elfmcts_root(ElfMcts* m, int32_t* info, int32_t* coord, int32_t* visits, float* prior, float* reward, int32_t* child, void* stream);
+/* Search analysis: the candidate moves of every game's root and the principal variation the search expects below each (what
+ * the reference shows with SearchTreeT::printTree, tree_search_node.h:479-528).  One read-only launch; nothing but the output
+ * arrays is written.
+ *   candidates  the root edges with visits > 0, ranked by visits descending, ties to the edge that comes first in the reference's
+ *               iteration order (lower `orig`): rank 0 is MCTSResultT::best_action under MOST_VISITED (tree_search_base.h:248-292).
+ *               The first max_moves of them are written.
+ *   pv          pv[0] is the candidate's own Coord; then, from the candidate's child node on, the most-visited edge of each node
+ *               (first in iteration order on ties) until a node has no followed edge, its most-visited edge has 0 visits, or
+ *               max_pv Coords are written.
+ * All outputs are device pointers.  info int32 [num_games][ELFMCTS_ANALYZE_WORDS]: 0 candidates written 1 root edges with
+ * visits > 0 (before the cut at max_moves) 2 root num_visits 3 root flip (1 = White to move at the root) 4 root V (float bits)
+ * 5 error bits, as word 6 of elfmcts_root 6 longest pv_len written 7 zero.  coord / orig / visits / reward / prior / pv_len are
+ * [num_games][max_moves] and pv is int32 [num_games][max_moves][max_pv]; any of them may be NULL.  reward is the raw black-positive
+ * sum and prior the stored prior: the bits elfmcts_root reports for that edge; orig is the edge's index in elfmcts_root's arrays.
+ * Unused entries: coord -1, orig -1, visits 0, reward 0, prior 0, pv_len 0, pv -1.
+ * 1 <= max_moves <= ELFMCTS_ANALYZE_MAX_MOVES, 1 <= max_pv <= ELFMCTS_ANALYZE_MAX_PV; anything else, or a NULL m / info, is
+ * ELFGO_E_BADARG and nothing is launched.
+ * Meaningful between an elfmcts_expand and the next elfmcts_select, when no virtual loss is outstanding.  At any other point of
+ * the stream the call is still safe (every walk is bounded and checks the ids it follows) but reports the statistics of the
+ * descents in flight. */
+#define ELFMCTS_ANALYZE_WORDS 8
+#define ELFMCTS_ANALYZE_MAX_MOVES 64
+#define ELFMCTS_ANALYZE_MAX_PV 32
+int elfmcts_analyze(ElfMcts* m, int max_moves, int max_pv, int32_t* info, int32_t* coord, int32_t* orig, int32_t* visits,
+                    float* reward, float* prior, int32_t* pv_len, int32_t* pv, void* stream);
 /* Test / debug service: checks the invariants of every live node record (scoring-order prefix sorted and linked to its child
    nodes, never-followed tail without statistics and by descending prior, visit counts add up).  Synchronises the device.
    out5_host: 0 number of violations, 1 code, 2 game, 3 node, 4 position of one of them.  No counterpart in the reference. */
@@ -485,6 +510,21 @@ int elfsp_last_score(const ElfSelfPlay* sp, float* out_host);
 /* what the last finished search of every game did: out_host[g] = the Coord it forwarded on the game board (after move sampling /
  * preload substitution), 1 (M_RESIGN) if the engine resigned instead of moving, -1 if no search of that game has finished yet */
 int elfsp_last_moves(const ElfSelfPlay* sp, int32_t* out_host);
+/* elfmcts_analyze on the tree pool of AI `actor` (ELFSP_ACTOR_*), same outputs (device pointers); ELFGO_E_BADARG if that pool does
+ * not exist (actor 1 before a request has created it).  Between two steps it shows the search in progress. */
+int elfsp_analyze(ElfSelfPlay* sp, int actor, int max_moves, int max_pv, int32_t* info, int32_t* coord, int32_t* orig,
+                  int32_t* visits, float* reward, float* prior, int32_t* pv_len, int32_t* pv, void* stream);
+/* Analysis snapshots at the move boundary.  With max_moves, max_pv > 0 (limits as elfmcts_analyze) every search that finishes in
+ * elfsp_end_step / elfsp_end_step2 leaves its analysis behind -- taken where the boundary fetches the root, before the tree is
+ * re-rooted by the move -- and elfsp_last_analysis reports, per game, what the last finished search of that game saw: the
+ * companion of elfsp_last_moves.  0, 0 = off (the default): the boundary launches and copies what it did without this call.
+ * Every call forgets the snapshots taken so far.  ELFGO_E_BADARG for other values or while a step is open. */
+int elfsp_set_analysis(ElfSelfPlay* sp, int max_moves, int max_pv);
+/* host arrays, laid out as elfmcts_analyze's with the max_moves / max_pv of elfsp_set_analysis; any may be NULL.  A game whose
+ * search has not finished since elfsp_set_analysis reports 0 candidates and the unused-entry values; with analysis off only info
+ * is written (zeros). */
+int elfsp_last_analysis(const ElfSelfPlay* sp, int32_t* info, int32_t* coord, int32_t* orig, int32_t* visits, float* reward,
+                        float* prior, int32_t* pv_len, int32_t* pv);
 /* Self-play records: with ElfSpOptions.keep_records > 0 every finished game leaves the Record the reference's
  * GameNotifier::OnGameEnd would send (GoStateExt::dumpRecord go_state_ext.h:131-148, Record::setJsonFields record.h:246-254),
  * as the JSON text nlohmann::json::dump() produces.  elfsp_pop_record copies the oldest pending record (NUL-terminated) into buf
