@@ -2,7 +2,10 @@
 per workgroup, for a single game's net call) on inputs whose result is exact -- small integers, so every partial sum is an integer
 fp32 and fp16 hold exactly and any differing element is a wrong halo, layout, swizzle or pipeline timing, never rounding -- then bit
 for bit against algo 0 (same K order, same MFMA), a race screen (repeated launches return the bits of the first), batch
-invariance, the calls it refuses, and whole nets routed through it and past it."""
+invariance, the calls it refuses, and whole nets routed through it and past it.  Then what only this kernel has: a grid larger
+than one residency, tail tiles on either side of the wave split, poison beside the tail, the skip's clamped rows behind M, both
+size limits and one launch at the top of the accepted range (its 32-bit byte offsets at their largest), and a single game's search
+served through it.  The battery it shares with algos 0 and 1 is sections B and C of test_gpu_net_edges.py."""
 import ctypes as C
 
 import pytest
@@ -74,7 +77,11 @@ def _int_case(rows, h, wd, c, k):
                                            (3, 9, 9, 192, 128),     # 27 K tiles (an odd count), two channel columns
                                            (2, 3, 7, 64, 192),      # h != wd
                                            (1, 1, 19, 64, 64),      # a one-line board
-                                           (1, 2, 2, 64, 64)])      # M = 4: a single tile that is almost all tail
+                                           (1, 2, 2, 64, 64),       # M = 4: a single tile that is almost all tail
+                                           (5, 9, 9, 128, 256),     # two K chunks per tap: the prologue's K tile 2 is (tap 1, chunk 0)
+                                           (1, 5, 7, 64, 64),       # M = 35: the tail spills 3 rows into the second wave row
+                                           (1, 19, 19, 64, 512),    # eight channel columns
+                                           (1, 3, 11, 64, 64)])     # M = 33: a second wave row with one valid position
 def test_exact_integers(elf, rows, h, wd, c, k, use_res, relu):
     """equality with the nine-tap fp32 form; y is prefilled with NaN, and one guard row of NaN behind y's last row stays NaN (the
     tail tile's stores are masked)"""
@@ -278,3 +285,206 @@ def test_whole_net_replays_from_a_graph_to_the_same_bits(elf):
     out = GraphedNet(native, s_static)()
     torch.cuda.synchronize()
     assert torch.equal(out["pi"], eager["pi"]) and torch.equal(out["V"], eager["V"])
+
+
+# ------------------------------------------------------------------------------------------------ what only this kernel has
+
+NAN = float("nan")
+
+
+def _guarded(rows, h, wd, k):
+    """y prefilled with NaN, and one guard row of NaN behind its last row (test_gpu_net_edges._guarded)"""
+    import torch
+    buf = torch.full((rows * h * wd + 1, k), NAN, device="cuda", dtype=torch.float16)
+    return buf, buf[:rows * h * wd].view(rows, h, wd, k)
+
+
+def _carve(t, guard):
+    """test_gpu_net_edges._carve: a copy of t inside a larger NaN-filled fp16 buffer, at least `guard` elements of NaN in front and
+    behind, at an address that is 16-byte and not 32-byte aligned.  -> (the copy, front guard, back guard)"""
+    import torch
+    n = t.numel()
+    buf = torch.full((guard + n + guard + 32,), NAN, device="cuda", dtype=torch.float16)
+    o = guard
+    while (buf.data_ptr() + 2 * o) % 32 != 16:
+        o += 1
+    v = buf[o:o + n].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 32 == 16 and o >= guard and buf.numel() - (o + n) >= guard
+    return v, buf[:o], buf[o + n:]
+
+
+def test_more_workgroups_than_are_resident(elf):
+    """Three workgroups of 48 KiB LDS fit a CU, 768 on the chip's 256 CUs.  200 rows of 9 x 9 are 16 200 positions = 254 tiles x
+    4 channel columns = 1 016 workgroups: with and without skip, with and without ReLU, the result is the integer nine-tap form and
+    algo 0's output bit for bit; the guard row behind y stays NaN (test_gpu_net_edges.test_algo_1_beyond_one_round_of_workgroups)."""
+    import torch
+    rows, h, wd, c, k = 200, 9, 9, 64, 256
+    d = _int_case(rows, h, wd, c, k)
+    assert (rows * h * wd + 63) // 64 == 254 and 254 * (k // 64) == 1016 > 3 * 256
+    for use_res in (False, True):
+        for relu in (0, 1):
+            r = d["r"] if use_res else None
+            ref = d["conv"] + d["b"].float()
+            if use_res:
+                ref = ref + r.float()
+            if relu:
+                ref = torch.relu(ref)
+            buf, y = _guarded(rows, h, wd, k)
+            assert _small(elf.lib(), d["x"], d["w"], d["b"], r, y, rows, h, wd, relu, c, k) == 0
+            buf0, y0 = _guarded(rows, h, wd, k)
+            assert _algo0(elf.lib(), d["x"], d["w"], d["b"], r, y0, rows, h, wd, relu, c, k) == 0
+            torch.cuda.synchronize()
+            bad = int((y.float() != ref).sum().item())   # a NaN left in y differs from everything
+            bits = int((y.view(torch.int16) != y0.view(torch.int16)).sum().item())
+            print("res %d relu %d: %d of %d differ from the integer form, %d from algo 0's bits" % (use_res, relu, bad, y.numel(), bits))
+            assert bad == 0
+            assert bits == 0
+            assert bool(torch.isnan(buf[-1]).all()) and bool(torch.isnan(buf0[-1]).all())
+
+
+@pytest.mark.parametrize("pos", [360, 351, 352])
+def test_one_nan_next_to_the_tail(elf, pos):
+    """1 x 19 x 19 is M = 361: five full tiles and a tail tile of 41 rows, positions 320 .. 360, whose wave split lies between 351
+    and 352.  One x element at position 360 (the last valid row: the rows behind it are staged from the zero line), 351 or 352 set
+    to NaN, no ReLU, no skip: the output is NaN at exactly the 3 x 3 neighbourhood of that cell on the board, in all K channels,
+    and the clean result everywhere else (test_gpu_net_edges.test_one_poisoned_input_element); the guard row stays NaN."""
+    import torch
+    rows, h, wd, c, k = 1, 19, 19, 256, 256
+    assert rows * h * wd == 5 * 64 + 41 and 5 * 64 + 32 == 352
+    i, j = divmod(pos, wd)
+    assert (i, j) in ((18, 18), (18, 9), (18, 10))
+    d = _int_case(rows, h, wd, c, k)
+    clean = d["conv"] + d["b"].float()
+    x = d["x"].clone()
+    touched = torch.zeros((rows, h, wd), device="cuda", dtype=torch.bool)
+    touched[0, max(i - 1, 0):i + 2, max(j - 1, 0):j + 2] = True
+    assert int(touched.sum().item()) == (4 if pos == 360 else 6)
+    for ch in (0, 100, c - 1):
+        keep = x[0, i, j, ch].item()
+        x[0, i, j, ch] = NAN
+        buf, y = _guarded(rows, h, wd, k)
+        assert _small(elf.lib(), x, d["w"], d["b"], None, y, rows, h, wd, 0, c, k) == 0
+        torch.cuda.synchronize()
+        yf = y.float()
+        assert bool(torch.isfinite(yf[~touched]).all()), ch
+        assert bool((yf[~touched] == clean[~touched]).all()), ch
+        assert bool(torch.isnan(yf[touched]).all()), ch
+        assert bool(torch.isnan(buf[-1]).all())
+        x[0, i, j, ch] = keep
+    assert torch.equal(x, d["x"])
+
+
+@pytest.mark.parametrize("rows,h,wd,c,k", [(1, 5, 7, 64, 64),        # M = 35: 29 rows of the one tile lie behind M
+                                           (5, 9, 9, 256, 256)])     # M = 405: 43 rows of the tail tile do
+def test_res_behind_the_last_row(elf, rows, h, wd, c, k):
+    """For a row at or beyond M the kernel loads the skip of row M - 1 and stores nothing.  res and y lie between NaN guards
+    (16-byte, not 32-byte aligned); no ReLU, so a skip value taken from behind res would reach the result as NaN: the result is
+    the integer form exactly and both guards of y are still all NaN."""
+    import torch
+    d = _int_case(rows, h, wd, c, k)
+    guard = (wd + 2) * max(c, k)
+    assert rows * h * wd % 64 != 0    # there are rows behind M in the last tile
+    r, _, _ = _carve(d["r"], guard)
+    y, front, back = _carve(torch.full((rows, h, wd, k), NAN, device="cuda", dtype=torch.float16), guard)
+    ref = d["conv"] + d["b"].float() + d["r"].float()
+    assert _small(elf.lib(), d["x"], d["w"], d["b"], r, y, rows, h, wd, 0, c, k) == 0
+    torch.cuda.synchronize()
+    bad = int((y.float() != ref).sum().item())
+    print("%s: %d of %d differ" % ((rows, h, wd, c, k), bad, y.numel()))
+    assert bad == 0
+    assert bool(torch.isnan(front).all()) and bool(torch.isnan(back).all())
+
+
+def test_the_first_refused_weight_size(elf):
+    """k * 9 * c >= 2^30 elements is refused (the weight's byte offsets are 32-bit): c = k = 10 944 = 171 x 64 is the first square
+    size at or above it, 10 880 = 170 x 64 the last below.  A negative status, nothing launched, y keeps its bytes (the buffers
+    here are tiny: the call must not touch them).  The accepted side is not launched."""
+    import torch
+    ck = 10944
+    assert ck % 64 == 0 and ck * ck * 9 == 1077940224 >= 2 ** 30 > (ck - 64) * (ck - 64) * 9
+    z = lambda *shape: torch.zeros(shape, device="cuda", dtype=torch.float16)
+    x, w, b = z(1, 1, 1, ck), z(64, 3, 3, 64), z(ck)
+    y = torch.full((1, 1, 1, ck), 7.0, device="cuda", dtype=torch.float16)
+    assert _small(elf.lib(), x, w, b, None, y, 1, 1, 1, 1, ck, ck) < 0
+    torch.cuda.synchronize()
+    assert bool((y == 7.0).all())
+
+
+def test_the_top_of_the_accepted_range(elf):
+    """The largest call the entry takes at c = k = 64 on 19 x 19: rows * 361 * 64 < 2^30 elements, x and y just below 2^31 bytes
+    each, so the kernel's 32-bit byte offsets (position * 128 plus a tap's distance) are as large as they get.  One more row is
+    refused.  x in {-1, 0, 1}, the integer weights and bias of _int_case; one launch, no skip, no ReLU.  Three slices of two boards
+    each -- the first two, the two around byte offset 2^30 of x, the last two -- equal the integer nine-tap form of those boards
+    alone; no row of y is left NaN and the guard row behind y still is."""
+    import time
+    import torch
+    h = wd = 19
+    c = k = 64
+    rows = (2 ** 30 - 1) // (h * wd * c)
+    assert rows * h * wd * c < 2 ** 30 <= (rows + 1) * h * wd * c and rows == 46474
+    m = rows * h * wd
+    assert 2 ** 31 - 2 * h * wd * c <= m * c * 2 < 2 ** 31
+    d = _int_case(2, h, wd, c, k)
+    w, b = d["w"], d["b"]
+    g = torch.Generator(device="cuda").manual_seed(2 ** 30)
+    x = torch.randint(-1, 2, (rows, h, wd, c), device="cuda", dtype=torch.int8, generator=g).half()
+    buf = torch.full((m + 1, k), NAN, device="cuda", dtype=torch.float16)
+    y = buf[:m].view(rows, h, wd, k)
+    assert _small(elf.lib(), x, w, b, None, y, rows + 1, h, wd, 0, c, k) < 0      # refused: nothing is launched
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(buf[0]).all()) and bool(torch.isnan(buf[-2]).all())
+    t0 = time.perf_counter()
+    assert _small(elf.lib(), x, w, b, None, y, rows, h, wd, 0, c, k) == 0
+    torch.cuda.synchronize()
+    print("the launch of %d rows (%d tiles): %.1f ms" % (rows, (m + 63) // 64, 1e3 * (time.perf_counter() - t0)))
+    mid = 2 ** 30 // (h * wd * c * 2)            # the board that holds byte 2^30 of x, or begins there
+    assert (mid - 1) * h * wd * c * 2 < 2 ** 30 < (mid + 1) * h * wd * c * 2 and 2 < mid - 1 and mid + 1 < rows - 2
+    for lo in (0, mid - 1, rows - 2):
+        xs = x[lo:lo + 2]
+        assert bool((xs != 0).any())
+        ref = _conv_fp32(xs.float(), w.float()) + b.float()
+        bad = int((y[lo:lo + 2].float() != ref).sum().item())
+        print("boards %d and %d: %d of %d differ" % (lo, lo + 1, bad, ref.numel()))
+        assert bad == 0
+    assert not bool(torch.isnan(y).any())
+    assert bool(torch.isnan(buf[-1]).all())
+
+
+def test_a_single_games_search_through_the_small_kernel(elf):
+    """What the kernel is for: one 9 x 9 game searched with 32 rollouts per move in batches of at most 8, every net call evaluated
+    twice -- NativeInferenceNet with small_max_positions = 0 (algo 0) and with 23 104 (the small kernel, four calls per
+    evaluation) -- on the feature rows the search really produces, at the row counts it really produces.  pi and V are the same
+    bits at every step; the search is fed the small kernel's; four searches are logged and the trees keep their invariants."""
+    import torch
+    from elf_amd.net import NativeInferenceNet
+    net, _ = _net_case()
+    base, small = NativeInferenceNet(net), NativeInferenceNet(net)
+    base.small_max_positions = 0
+    small.small_max_positions = 23104
+    base.L, small.L = _Calls(base.L), _Calls(small.L)
+    sp = elf.SelfPlay(board_size=9, num_games=1, mcts_rollout_per_thread=32, mcts_rollout_per_batch=8, feature_format="f16_nhwc",
+                      seed=5, log_searches=4)
+    steps, evals, seen = 0, 0, set()
+    try:
+        while sp.stats()["logged"] < 4 and steps < 200:
+            rows = sp.begin_step()
+            if rows:
+                s = sp.s[:rows]
+                a, o = base({"s": s}), small({"s": s})
+                torch.cuda.synchronize()
+                assert torch.equal(a["pi"], o["pi"]) and torch.equal(a["V"], o["V"]), (steps, rows)
+                assert bool(torch.isfinite(o["pi"]).all()) and bool(torch.isfinite(o["V"]).all())
+                seen.add(int(rows))
+                evals += 1
+                sp.end_step(o["pi"], o["V"])
+            else:
+                sp.end_step(None, None)
+            steps += 1
+        assert sp.stats()["logged"] >= 4
+        assert sp.validate_trees()[0] == 0
+    finally:
+        sp.close()
+    print("%d steps, %d evaluations, row counts %s" % (steps, evals, sorted(seen)))
+    assert base.L.small == 0 and small.L.small == 4 * evals and evals > 0
+    assert len(seen) > 1

@@ -1,6 +1,8 @@
-"""GPU: the edges of the three net kernels (k_bias_act of net_epilogue.hip, elfnet_conv3x3_f16's algo 0 of net_conv.hip and algo 1 of
-net_conv3x3.hip) that the other test_gpu_net*.py files do not reach, every comparison exact (equal as values, NaN in the same
-places; no tolerance anywhere):
+"""GPU: the edges of the four net kernels (k_bias_act of net_epilogue.hip and the three trunk convolution entries: elfnet_conv3x3_f16's
+algo 0 of net_conv.hip and algo 1 of net_conv3x3.hip, and elfnet_conv3x3_small_f16 of net_conv3x3_small.hip) that the other
+test_gpu_net*.py files do not reach, every comparison exact (equal as values, NaN in the same places; no tolerance anywhere).
+Sections B and C run every convolution case through all three entries (algo 0, algo 1, "small"), and their poison sites sit on
+the seams of both tilings: 256 positions for algos 0 and 1; 64 (tile), 32 (wave split) and 8 (staging piece) for the small kernel:
   A  algo 1 with more workgroups than the chip has CUs (a second and a third round), against the integer nine-tap form and,
      bit for bit, against algo 0;
   B  which cells a cell influences (one poisoned input element, one poisoned weight), operands that lie between NaN guards at
@@ -9,7 +11,8 @@ places; no tolerance anywhere):
      k_bias_act (f16 and bf16, all four variants) over a grid-stride loop that runs more than once and over a table of special
      values, and the size limit;
   D  algo 0 at the channel counts FusedInferenceNet._fusable sends it (8, 40, 72, 264);
-  E  FusedInferenceNet's trunk routed to algo 1 by size, a chunked call's mix of the two algos, and algo 1 inside a captured graph.
+  E  FusedInferenceNet's trunk routed to algo 1 by size, a chunked call's mix of the two algos (algo 1 and algo 0 by default, algo 1
+     and the small kernel with small_max_positions set), and algo 1 inside a captured graph.
 References are plain torch fp32 formulas written out here, or algo 0 where bit equality is the claim."""
 import ctypes as C
 
@@ -27,9 +30,17 @@ def elf(built):
     return elf_amd
 
 
+ENTRIES = [0, 1, "small"]   # elfnet_conv3x3_f16's two algos and elfnet_conv3x3_small_f16
+
+
 def _run(L, x, w, b, r, y, rows, h, wd, c, k, relu, algo):
+    """one call of the entry `algo` names: the small entry takes the same arguments but for the algo"""
     import torch
     p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    if algo == "small":
+        return L.elfnet_conv3x3_small_f16(p(x), p(w), p(b), p(r), p(y), rows, h, wd, c, k, int(relu),
+                                          C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert algo in (0, 1)
     return L.elfnet_conv3x3_f16(p(x), p(w), p(b), p(r), p(y), rows, h, wd, c, k, int(relu), algo,
                                 C.c_void_p(torch.cuda.current_stream().cuda_stream))
 
@@ -147,7 +158,7 @@ def _carve(t, guard):
     return v, buf[:o], buf[o + n:]
 
 
-@pytest.mark.parametrize("algo", [0, 1])
+@pytest.mark.parametrize("algo", ENTRIES)
 @pytest.mark.parametrize("rows,h,wd,c,k,res", [(5, 9, 9, 256, 256, None), (5, 9, 9, 256, 256, "r"), (5, 9, 9, 256, 256, "x"),
                                                (11, 5, 7, 64, 256, None), (11, 5, 7, 64, 256, "r")])
 def test_guarded_operands_at_16_byte_alignment(elf, rows, h, wd, c, k, res, algo):
@@ -175,7 +186,7 @@ def test_guarded_operands_at_16_byte_alignment(elf, rows, h, wd, c, k, res, algo
     assert _run(elf.lib(), x, w, b, r, y, rows, h, wd, c, k, 0, algo) == 0
     torch.cuda.synchronize()
     bad = int((y.float() != ref).sum().item())
-    print("%s res %s algo %d: %d of %d differ" % ((rows, h, wd, c, k), res, algo, bad, y.numel()))
+    print("%s res %s algo %s: %d of %d differ" % ((rows, h, wd, c, k), res, algo, bad, y.numel()))
     assert bad == 0
     assert bool(torch.isnan(front).all()) and bool(torch.isnan(back).all())
 
@@ -184,10 +195,16 @@ def test_guarded_operands_at_16_byte_alignment(elf, rows, h, wd, c, k, res, algo
 POISON_SITES = [(0, 0, 0), (0, 0, 8), (0, 8, 0), (0, 8, 8),   # the four corners of one board
                 (1, 8, 8), (2, 0, 0),                         # neighbours in memory and not on the board
                 (3, 1, 3), (3, 1, 4),                         # positions 255 and 256: the tile seam
-                (4, 8, 8)]                                    # position 404: the last valid row of the tail tile
+                (4, 8, 8),                                    # position 404: the last valid row of the tail tile
+                # the small kernel's seams (64-position tiles, two wave rows of 32, staging pieces of 8 rows)
+                (0, 0, 7),                                    # position 7: with the corner (0, 0, 8) above, a staging-piece seam
+                (0, 3, 4), (0, 3, 5),                         # positions 31 and 32: the wave split
+                (0, 7, 0), (0, 7, 1),                         # positions 63 and 64: the 64-tile seam
+                (4, 6, 5), (4, 6, 6)]                         # positions 383 and 384: the last row of the last full 64-tile and the
+                                                              # first of its 21-row tail tile
 
 
-@pytest.mark.parametrize("algo", [0, 1])
+@pytest.mark.parametrize("algo", ENTRIES)
 @pytest.mark.parametrize("c", [64, 256])
 @pytest.mark.parametrize("poison", [NAN, INF])
 def test_one_poisoned_input_element(elf, poison, c, algo):
@@ -197,7 +214,8 @@ def test_one_poisoned_input_element(elf, poison, c, algo):
     has them."""
     import torch
     rows, h, wd, k = 5, 9, 9, 256
-    assert [(b * h + i) * wd + j for b, i, j in POISON_SITES[6:]] == [255, 256, 404]
+    assert [(b * h + i) * wd + j for b, i, j in POISON_SITES[6:]] == [255, 256, 404, 7, 31, 32, 63, 64, 383, 384]
+    assert (0 * h + 0) * wd + 8 == 8 and (0, 0, 8) in POISON_SITES and rows * h * wd == 6 * 64 + 21
     d = _int_case(rows, h, wd, c, k)
     clean = d["conv"] + d["b"].float()
     x = d["x"].clone()
@@ -224,17 +242,36 @@ def test_one_poisoned_input_element(elf, poison, c, algo):
     assert torch.equal(x, d["x"])
 
 
-@pytest.mark.parametrize("algo", [0, 1])
+@pytest.mark.parametrize("algo", ENTRIES)
 @pytest.mark.parametrize("c", [64, 256])
 @pytest.mark.parametrize("k0,ky,kx,last_ch", [(0, 0, 0, False), (255, 2, 1, True), (77, 1, 1, True), (130, 1, 2, False)])
 def test_one_poisoned_weight(elf, k0, ky, kx, last_ch, c, algo):
     """One w[k0, ky, kx, ch] set to +Inf, no ReLU, no skip: every channel but k0 is the unpoisoned result, and channel k0 is the
     nine-tap fp32 form of the same inputs -- +Inf, -Inf or NaN (x = 0) where the tap is on the board, NaN where it is off the
     board, because zero padding times Inf is NaN."""
+    _one_poisoned_weight(elf, k0, ky, kx, c - 1 if last_ch else 0, c, algo)
+
+
+@pytest.mark.parametrize("algo", ENTRIES)
+@pytest.mark.parametrize("c", [64, 256])
+@pytest.mark.parametrize("k0,ky,kx,where", [(31, 0, 2, "mid"), (32, 2, 0, "mid"), (63, 1, 0, "mid"), (64, 0, 1, "mid"),
+                                            (31, 2, 2, "last"), (32, 0, 0, "first"), (63, 1, 1, "first"), (64, 2, 1, "last")])
+def test_one_poisoned_weight_at_the_k_seams(elf, k0, ky, kx, where, c, algo):
+    """test_one_poisoned_weight on the output-channel seams of the small kernel: k0 = 31 | 32 is the split between its two wave
+    columns, 63 | 64 the edge of its first channel column.  "mid" is an input channel other than 0 and C - 1 that the second MFMA
+    of a 32-channel block takes ({8..15, 24..31}): channel 72 for C = 256, in the second 64-channel K chunk of its tap, and
+    channel 40 for C = 64, which has one chunk per tap.  The sign of channel k0 follows x[..., ch] at the tap's source cell, so a
+    weight channel multiplied with another activation channel (the two operands' swizzles or MFMA halves disagreeing) shows."""
+    ch = {"first": 0, "last": c - 1, "mid": 72 if c == 256 else 40}[where]
+    assert 0 < ch < c - 1 or where != "mid"
+    assert where != "mid" or ((ch % 32) // 8 in (1, 3) and (c == 64 or ch // 64 >= 1))
+    _one_poisoned_weight(elf, k0, ky, kx, ch, c, algo)
+
+
+def _one_poisoned_weight(elf, k0, ky, kx, ch, c, algo):
     import torch
     rows, h, wd, k = 5, 9, 9, 256
     d = _int_case(rows, h, wd, c, k)
-    ch = c - 1 if last_ch else 0
     w = d["w"].clone()
     w[k0, ky, kx, ch] = INF
     ref = _conv_fp32(d["x"].float(), w.float()) + d["b"].float()
@@ -269,7 +306,7 @@ def _cell_kinds(n):
     return on[:, None] * on[None, :]
 
 
-@pytest.mark.parametrize("algo", [0, 1])
+@pytest.mark.parametrize("algo", ENTRIES)
 def test_two_roundings_not_one_at_a_tie(elf, algo):
     """x = 1, w = 1 but for the centre tap of one input channel per output channel, which is 2; bias = 1; no skip.  A cell sums
     256 per tap on the board and 1 more: 2305 inside, 1537 on an edge, 1025 at a corner.  The header's sequence gives
@@ -291,12 +328,12 @@ def test_two_roundings_not_one_at_a_tie(elf, algo):
         buf, y = _guarded(rows, n, n, ch)
         assert _run(elf.lib(), x, w, b, None, y, rows, n, n, ch, ch, relu, algo) == 0
         torch.cuda.synchronize()
-        print("algo %d relu %d: interior %s edge %s corner %s" % (algo, relu, y[0, 4, 4, 0].item(), y[0, 0, 4, 0].item(), y[0, 0, 0, 0].item()))
+        print("algo %s relu %d: interior %s edge %s corner %s" % (algo, relu, y[0, 4, 4, 0].item(), y[0, 0, 4, 0].item(), y[0, 0, 0, 0].item()))
         assert bool((y.float() == want[None, :, :, None]).all())
         assert bool(torch.isnan(buf[-1]).all())
 
 
-@pytest.mark.parametrize("algo", [0, 1])
+@pytest.mark.parametrize("algo", ENTRIES)
 def test_the_first_rounding_overflows_to_inf(elf, algo):
     """x = 32, w = 1, bias = -16384: a cell sums 8192 per tap on the board, 73 728 inside, 49 152 on an edge, 32 768 at a corner.
     half(73 728) is Inf before the bias is added, so the interior is +Inf (one rounding of 73 728 - 16 384 = 57 344 would be
@@ -329,7 +366,7 @@ def _scaled(ints, shift):
     return (i.double() * 2.0 ** -shift).half()
 
 
-@pytest.mark.parametrize("algo", [0, 1])
+@pytest.mark.parametrize("algo", ENTRIES)
 @pytest.mark.parametrize("wshift,oshift", [(10, 14), (0, 24)])
 def test_subnormal_inputs_and_outputs(elf, wshift, oshift, algo):
     """The integer case scaled by powers of two: x = xi * 2^-24 (every nonzero x is the smallest fp16 subnormal), w = wi * 2^10,
@@ -362,13 +399,13 @@ def test_subnormal_inputs_and_outputs(elf, wshift, oshift, algo):
             got = y.cpu()
             bad = int((got.double() != want.double()).sum().item())
             sub = int(((want != 0) & (want.abs() < 2.0 ** -14)).sum().item())
-            print("algo %d shifts %d/%d res %d relu %d: %d of %d differ; %d expected values are subnormal"
+            print("algo %s shifts %d/%d res %d relu %d: %d of %d differ; %d expected values are subnormal"
                   % (algo, wshift, oshift, use_res, relu, bad, got.numel(), sub))
             assert bad == 0
             assert bool(torch.isnan(buf[-1]).all())
 
 
-@pytest.mark.parametrize("algo", [0, 1])
+@pytest.mark.parametrize("algo", ENTRIES)
 @pytest.mark.parametrize("use_res", [False, True])
 def test_relu_turns_nan_into_zero(elf, use_res, algo):
     """Pins what the three epilogues do: max(v, 0) is fmaxf, so with relu = 1 a NaN before the activation comes out as +0 (the
@@ -405,10 +442,10 @@ def test_relu_turns_nan_into_zero(elf, use_res, algo):
         assert bool(torch.isnan(buf[-1]).all())
 
 
-@pytest.mark.parametrize("algo", [0, 1])
+@pytest.mark.parametrize("algo", ENTRIES)
 def test_the_first_refused_size(elf, algo):
-    """rows * h * w * max(c, k) = 4096 * 32 * 32 * 256 = 2^30 elements is the first size refused: a negative status from both
-    algos, nothing launched, y keeps its bytes (the buffers here are small: the call must not touch them)"""
+    """rows * h * w * max(c, k) = 4096 * 32 * 32 * 256 = 2^30 elements is the first size refused: a negative status from every
+    entry, nothing launched, y keeps its bytes (the buffers here are small: the call must not touch them)"""
     import torch
     ch = 256
     x = torch.zeros((1, 32, 32, ch), device="cuda", dtype=torch.float16)
@@ -582,13 +619,19 @@ def test_algo_0_at_channel_counts_that_need_padding(elf, c, k, use_res):
 # E. the routed path
 
 class _Recording:
-    """forwards everything to libelf_amd.so and keeps the algo argument of every elfnet_conv3x3_f16 call"""
+    """forwards everything to libelf_amd.so, keeps the algo argument of every elfnet_conv3x3_f16 call and counts the
+    elfnet_conv3x3_small_f16 calls"""
 
     def __init__(self, lib):
-        self._lib, self.algos = lib, []
+        self._lib, self.algos, self.small = lib, [], 0
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
+        if name == "elfnet_conv3x3_small_f16":
+            def small(*args):
+                self.small += 1
+                return fn(*args)
+            return small
         if name != "elfnet_conv3x3_f16":
             return fn
 
@@ -616,22 +659,28 @@ def _routed_net():
         with torch.no_grad():
             h0 = f._conv(s16, f.first)
         torch.cuda.synchronize()
-        assert f.L.algos == [] and h0.shape == (bs, ch, n, n) and bool(torch.isfinite(h0).all())
+        assert f.L.algos == [] and f.L.small == 0 and h0.shape == (bs, ch, n, n) and bool(torch.isfinite(h0).all())
         _routed.update(f=f, h0=h0)
     return _routed["f"], _routed["h0"]
 
 
-def _trunk(f, h, conv_algo=None):
-    """the residual blocks of f on h with f.conv_algo set for the call -> (output, the algos of its elfnet_conv3x3_f16 calls)"""
+def _trunk(f, h, conv_algo=None, small_max_positions=None):
+    """the residual blocks of f on h with f.conv_algo (and, where given, f.small_max_positions) set for the call -> (output, the
+    algos of its elfnet_conv3x3_f16 calls); f.L.small is the number of its elfnet_conv3x3_small_f16 calls"""
     import torch
     f.L.algos.clear()
+    f.L.small = 0
     f.conv_algo = conv_algo
+    if small_max_positions is not None:
+        f.small_max_positions = small_max_positions
     try:
         with torch.no_grad():
             for lo, up in f.blocks:
                 h = f._conv(f._conv(h, lo), up, res=h)
     finally:
         del f.conv_algo
+        if small_max_positions is not None:
+            del f.small_max_positions
     return h, list(f.L.algos)
 
 
@@ -666,6 +715,25 @@ def test_fused_net_chunks_through_both_algos(elf):
     assert algos == [0, 0, 0, 0]
     assert torch.equal(whole[:91], head)
     assert torch.equal(whole[91:], tail)
+
+
+def test_fused_net_chunks_through_algo_1_and_the_small_kernel(elf):
+    """The same chunked call with small_max_positions = 23 104, the value the default is meant to move to: 91 rows still go through
+    four algo 1 calls, and the 9 that remain (3 249 positions) through four elfnet_conv3x3_small_f16 calls and no
+    elfnet_conv3x3_f16 call; both are, row for row, the bits of all 100 at once"""
+    import torch
+    f, h0 = _routed_net()
+    assert type(f).small_max_positions == 0 and 9 * 361 == 3249 <= 23104 < f.native_min_positions
+    whole, algos = _trunk(f, h0)
+    assert algos == [1, 1, 1, 1] and f.L.small == 0
+    head, algos = _trunk(f, h0[:91], small_max_positions=23104)
+    assert algos == [1, 1, 1, 1] and f.L.small == 0
+    tail, algos = _trunk(f, h0[91:], small_max_positions=23104)
+    assert algos == [] and f.L.small == 4
+    assert f.small_max_positions == 0      # the instance attribute is gone: the class default shows again
+    assert torch.equal(whole[:91], head)
+    assert torch.equal(whole[91:], tail)
+    assert bool(torch.isfinite(tail).all()) and float(tail.float().abs().max().item()) > 0
 
 
 def test_algo_1_captured_equals_uncaptured(elf):
