@@ -11,9 +11,10 @@
 //             MFMAs of the MFMA segments; three or four half-tiles stay in flight across the loop's barriers, which are bare
 //             s_barriers behind counted vmcnt waits (the comment at the main loop has the slots and the counts).  vmcnt(0) only
 //             once the last half-tile is on its way.  Every staged piece is a full aligned 128-B line: 8 lanes per row.
-//   halo      a staging lane decodes its four rows once (position -> n, h, w) and keeps a 9-bit tap mask and a byte offset; for an
-//             off-board tap, and for a row at or beyond M, its source address is a zero-filled line in global memory.  LDS is never
-//             zeroed by a second path.
+//   halo      a staging lane decodes its four rows once (position -> n, h, w: two divisions by launch constants, each a multiply
+//             by a multiplier the host entry made and a shift) and keeps a 9-bit tap mask (a 3-bit row mask times a 3-bit column
+//             mask) and a byte offset; for an off-board tap, and for a row at or beyond M, its source address is a zero-filled
+//             line in global memory.  LDS is never zeroed by a second path.
 //   LDS image lane-linear, as the DMA writes it; the 16-B slot s of row r holds the row's chunk s ^ ((r >> 1) & 7): the XOR is on
 //             the source address when staging and on the read address of the fragment ds_read_b128s, which are then conflict-free
 //             (rows r and r + 1 share a 256-B bank row, so the swizzle steps every second row; checked against the 16-lane groups
@@ -21,9 +22,11 @@
 //   K order   tap-major (ky, kx, then c ascending); inside a 32-channel block the two MFMAs take channels {0..7, 16..23} and
 //             {8..15, 24..31}, as CK's blockwise GEMM hands them out: algo 0's accumulation chain per output element, bit for bit.
 //   epilogue  accumulators -> fp16 -> LDS (4 KiB of the wave's own behind the staging buffers, 32 positions at a time) -> 16 B of
-//             consecutive channels per lane; bias and res are read in that shape, and the sequence is BiasResAct's of
-//             net_conv.hip: float(half(acc)) + bias (+ res), max(., 0), one rounding to fp16.  Rows at or beyond M are not stored.
-//             No workgroup barrier: a wave reads back what it wrote itself.
+//             consecutive channels per lane; bias and res are read in that shape, and the values are BiasResAct's of
+//             net_conv.hip: float(half(acc)) + bias (+ res), max(., 0), one rounding to fp16, computed as one v_fma_mix_f32 per
+//             addition (it converts its fp16 operands itself), the rounding, and the ReLU on the packed fp16 pair behind it under
+//             a uniform branch (max and a monotone rounding commute; NaN gives +0 either way).  Rows at or beyond M are not
+//             stored.  No workgroup barrier: a wave reads back what it wrote itself.
 //   tail      the work items of a launch (position tiles x channel columns of 256) run in rounds of one per CU.  Where the last
 //             round is at most half full, each of its items runs as two work ids of 256 positions x 128 channels (the half
 //             tile: the same waves at 128 x 32 each, three staged half-tiles per K tile instead of four), so that round takes
@@ -96,7 +99,7 @@ __device__ __forceinline__ int fresh(int v) {
   asm volatile("" : "+v"(v));
   return v;
 }
-// The same for a wave-uniform value: the reciprocals the decode's divisions go by are then made where an item is decoded
+// The same for a wave-uniform value
 __device__ __forceinline__ int fresh_uniform(int v) {
   asm volatile("" : "+s"(v));
   return v;
@@ -122,12 +125,27 @@ __host__ __device__ inline int full_items(int64_t total, int64_t width) {
   return (int)(total >= width && r > 0 && 2 * r <= width ? total - r : total);
 }
 
+// floor(n / d) for every 0 <= n < 2^31 as one multiply and one shift: with l = ceil(log2 d), s = max(32, 31 + l) and
+// mul = floor((2^s - 1) / d), which is below 2^32, e = 2^s - mul d lies in [1, d] and (n + 1) mul / 2^s = (n + 1) / d -
+// (n + 1) e / (d 2^s); (n + 1) e <= 2^31 2^l <= 2^s, so the second term is above 0 and at most 1 / d: the floor is floor(n / d)
+// whether d divides n + 1 or not.  The rounded-up multiplier would need 33 bits at d = 1.  The host makes (mul, shift = s - 32)
+// once per launch; a launch's divisors are H W and W.
+struct Recip { uint32_t mul, shift; };
+inline Recip recip_of(uint32_t d) {   // 1 <= d <= 2^31
+  int l = 0;
+  while (((uint64_t)1 << l) < d) ++l;
+  const int s = l == 0 ? 32 : 31 + l;
+  return Recip{(uint32_t)((((uint64_t)1 << s) - 1) / d), (uint32_t)(s - 32)};
+}
+__device__ __forceinline__ uint32_t div_by(uint32_t n, Recip r) { return __umulhi(n + 1, r.mul) >> r.shift; }
+
 // What a wave knows about itself and the launch: everything the staging and the epilogue address by.
 struct Ctx {
   char* lds;
   const char* x;
   const char* w;
   int M, H, W, Cin, K, relu;
+  Recip dhw, dw;                 // the decode's divisions by H W and by W
   int lane, wv;                  // wv through readfirstlane: what depends on the wave alone stays in scalar registers
   const unsigned char* zsrc;     // this lane's 16 B of the zero line
 };
@@ -146,22 +164,20 @@ struct Rows { uint32_t xoff[4], woff[4], xmask[4]; };
 template <int kNT>
 __device__ __forceinline__ void decode_rows(const Ctx& c, Rows& rw, int tile, int kbase) {
   const int lane = c.lane, wv = c.wv;
-  const int hw = fresh_uniform(c.H * c.W), wd = fresh_uniform(c.W);
+  const uint32_t hw = (uint32_t)(c.H * c.W), wd = (uint32_t)c.W;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int hf = j >> 1, i = j & 1;
     const int r = i * 128 + hf * 64 + wv * 8 + (lane >> 3);
     const int p = tile * kTileM + r;
-    uint32_t m = 0;
-    if (p < c.M) {
-      const int rem = p % hw, hh = rem / wd, ww = rem - hh * wd;
-#pragma unroll
-      for (int tap = 0; tap < 9; ++tap) {
-        const int dy = tap / 3 - 1, dx = tap % 3 - 1;
-        if ((unsigned)(hh + dy) < (unsigned)c.H && (unsigned)(ww + dx) < (unsigned)c.W) m |= 1u << tap;
-      }
-    }
-    rw.xmask[j] = m;
+    // tap 3 ky + kx is on the board iff row hh + ky - 1 and column ww + kx - 1 are: the rows' three bits stand at 0, 3 and 6, the
+    // columns' at 0, 1 and 2, and their product has bit 3 ky + kx set iff both are (no carries: the column mask is below 8)
+    const uint32_t rem = (uint32_t)p - div_by((uint32_t)p, c.dhw) * hw, hh = div_by(rem, c.dw), ww = rem - hh * wd;
+    const uint32_t rowm = (hh > 0 ? 1u : 0u) | 8u | ((int)hh + 1 < c.H ? 64u : 0u);
+    const uint32_t colm = (ww > 0 ? 1u : 0u) | 2u | ((int)ww + 1 < c.W ? 4u : 0u);
+    uint32_t m = __umul24(rowm, colm);
+    asm("" : "+v"(m));   // made for every row and selected, with no branch around the arithmetic for the rows at or beyond M
+    rw.xmask[j] = p < c.M ? m : 0u;
     rw.xoff[j] = (uint32_t)p * (uint32_t)(c.Cin * 2) + (((lane & 7) ^ ((r >> 1) & 7)) << 4);   // below 2^31 wherever it is used (p < M)
     const int rwt = kNT == 2 ? (i * 2 + (wv >> 2)) * 64 + hf * 32 + (wv & 3) * 8 + (lane >> 3) : i * 64 + wv * 8 + (lane >> 3);
     rw.woff[j] = (uint32_t)(kbase + rwt) * (uint32_t)(9 * c.Cin * 2) + (((lane & 7) ^ ((rwt >> 1) & 7)) << 4);
@@ -392,6 +408,35 @@ __device__ __forceinline__ void main_loop(const Ctx& c, const Rows& rw, floatx16
 // consecutive positions writing the same half of the same chunk number: the 256-B bank row holds two (four) positions and the XOR
 // steps every second (fourth), so the 16 lanes land in 16 different 16-B slots; a ds_read_b128 group is four runs of 4 lanes (or two
 // of 8), each run a different position of a different slot quarter: all 64 banks once.
+// The epilogue's arithmetic on two fp16 values per register.  BiasResAct's sequence is float(half(acc)) + float(bias), + float(res),
+// max(., 0), one rounding to fp16; v_fma_mix_f32 converts its fp16 sources exactly and rounds the fp32 fused multiply-add once, and
+// float(h) * 1.0 + c rounded once is float(h) + c rounded once, so one instruction is the conversion (of both operands, for the
+// bias) and the addition: the same fp32 value, NaN, infinities, zeros' signs and subnormals included.  kHi: the upper half.
+typedef uint32_t uint32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+template <int kHi>
+__device__ __forceinline__ float add_h_h(uint32_t a, uint32_t b, Mode<kHi>) {   // float(a.half) + float(b.half)
+  float d;
+  if constexpr (kHi) asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(d) : "v"(a), "v"(b));
+  else asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,1]" : "=v"(d) : "v"(a), "v"(b));
+  return d;
+}
+template <int kHi>
+__device__ __forceinline__ float add_h_f(uint32_t a, float c, Mode<kHi>) {      // float(a.half) + c
+  float d;
+  if constexpr (kHi) asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(a), "v"(c));
+  else asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(a), "v"(c));
+  return d;
+}
+// ReLU behind the last rounding, on both halves: rounding to fp16 is monotone and keeps zero, so max(round(v), 0) is
+// round(max(v, 0)) for every v that is not NaN, and for NaN both give +0 (the maximum returns the operand that is a number).
+// The instruction itself: the compiler's own maximum first canonicalises its operand with a second v_pk_max_f16; volatile, so
+// that the uniform branch around it stays a branch and is not turned back into selects.
+__device__ __forceinline__ uint32_t relu_h2(uint32_t v) {
+  asm volatile("v_pk_max_f16 %0, %0, 0" : "+v"(v));
+  return v;
+}
+
 template <bool kHasRes, int kNT>
 struct Skip { half8 bv; half8 rv[kHasRes ? 8 * kNT : 1]; };
 
@@ -428,7 +473,7 @@ __device__ __forceinline__ void load_skip(const Ctx& c, Skip<kHasRes, kNT>& s, c
   }
 }
 
-// kAll: every row of the tile is below M, and every lane issues all its 8 kNT stores (the count the next item's first wait uses)
+// kAll: every row of the tile is below M, and every lane issues all its 8 kNT stores (the count the next item's first wait uses).
 template <bool kHasRes, int kNT, bool kAll>
 __device__ __forceinline__ void epilogue(const Ctx& c, const half4 (&hacc)[4][kNT][4], const Skip<kHasRes, kNT>& s,
                                          _Float16* __restrict__ y, int tile, int kbase) {
@@ -444,21 +489,39 @@ __device__ __forceinline__ void epilogue(const Ctx& c, const half4 (&hacc)[4][kN
 #pragma unroll
       for (int g = 0; g < 4; ++g) *(half4*)(cl + fr * kRowB + (((nt * 4 + g) ^ E::swz(fr)) << 4) + fh * 8) = hacc[mt][nt][g];
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the wave's own writes; nobody else's are read
+    auto readback = [&](int j) {
+      const int pos = j * E::kPos + e.pr;
+      return *(const uint32x4*)(cl + pos * kRowB + ((e.q ^ E::swz(pos)) << 4));
+    };
+    // The branch below ends the compiler's own look-ahead, so the next read-back is issued in front of this one's arithmetic by
+    // hand: four registers more, which the kernel with the skip does not have (at 254 it spills with them, in any pass).
+    constexpr bool ahead = !kHasRes;
+    uint32x4 nv;
+    if (ahead) nv = readback(0);
 #pragma unroll
     for (int j = 0; j < E::kR; ++j) {
-      const int pos = j * E::kPos + e.pr;
-      const int p = e.row0 + mt * 32 + pos;
-      const half8 cv = *(const half8*)(cl + pos * kRowB + ((e.q ^ E::swz(pos)) << 4));
-      half8 ov;
+      const uint32x4 cv = ahead ? nv : readback(j);
+      if (ahead && j + 1 < E::kR) nv = readback(j + 1);
+      uint32x4 ov;
+      const uint32x4 bv = __builtin_bit_cast(uint32x4, s.bv);
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        float v = (float)cv[i];
-        v += (float)s.bv[i];
-        if constexpr (kHasRes) v += (float)s.rv[mt * E::kR + j][i];
-        if (c.relu) v = fmaxf(v, 0.0f);
-        ov[i] = (_Float16)v;
+      for (int i = 0; i < 4; ++i) {
+        float lo = add_h_h(cv[i], bv[i], Mode<0>{}), hi = add_h_h(cv[i], bv[i], Mode<1>{});
+        if constexpr (kHasRes) {
+          const uint32_t rv = __builtin_bit_cast(uint32x4, s.rv[mt * E::kR + j])[i];
+          lo = add_h_f(rv, lo, Mode<0>{});
+          hi = add_h_f(rv, hi, Mode<1>{});
+        }
+        ov[i] = __builtin_bit_cast(uint32_t, h2_t{(_Float16)lo, (_Float16)hi});
       }
-      if (kAll || p < c.M) *(half8*)(y + (size_t)p * c.K + e.chan) = ov;
+      // a uniform branch around four instructions (the comparison is made here, on the scalar argument: a flag kept across the
+      // passes ends up in a VGPR), not a select per element: relu = 0 executes nothing and passes NaN, -0 and negative values
+      if (fresh_uniform(c.relu)) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ov[i] = relu_h2(ov[i]);
+      }
+      const int p = e.row0 + mt * 32 + j * E::kPos + e.pr;
+      if (kAll || p < c.M) *(uint32x4*)(y + (size_t)p * c.K + e.chan) = ov;
     }
     __builtin_amdgcn_wave_barrier();   // the next pass's writes stay behind this pass's read-backs
   }
@@ -533,11 +596,11 @@ template <bool kHasRes>
 __global__ __launch_bounds__(kThreads, 2) void k_conv3x3_f16(const char* __restrict__ x, const char* __restrict__ w,
                                                              const _Float16* __restrict__ bias, const _Float16* __restrict__ res,
                                                              _Float16* __restrict__ y, int M, int H, int W, int Cin, int K, int relu,
-                                                             int tiles, int nfull, int ids) {
+                                                             int tiles, int nfull, int ids, Recip dhw, Recip dw) {
   __shared__ __attribute__((aligned(128))) char lds[kLdsBytes];   // ALL of the kernel's LDS: one array
   const int tid = threadIdx.x;
   Ctx c;
-  c.lds = lds; c.x = x; c.w = w; c.M = M; c.H = H; c.W = W; c.Cin = Cin; c.K = K; c.relu = relu;
+  c.lds = lds; c.x = x; c.w = w; c.M = M; c.H = H; c.W = W; c.Cin = Cin; c.K = K; c.relu = relu; c.dhw = dhw; c.dw = dw;
   c.lane = tid & 63;
   c.wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   c.zsrc = g_zero_line + (c.lane & 7) * 16;
@@ -614,12 +677,13 @@ extern "C" __attribute__((visibility("hidden"))) int elfnet_conv3x3_native_f16(c
   const int nfull = width > 0 ? full_items(total, width) : (int)total;
   const int64_t ids = 2 * total - nfull;
   const dim3 grid((unsigned)(width > 0 && width < ids ? width : ids));
+  const Recip dhw = recip_of((uint32_t)(h * wd)), dw = recip_of((uint32_t)wd);   // h * wd <= m, below 2^31
   if (res)
     hipLaunchKernelGGL(k_conv3x3_f16<true>, grid, dim3(kThreads), 0, stream, (const char*)x, (const char*)w, (const _Float16*)bias,
-                       (const _Float16*)res, (_Float16*)y, (int)m, h, wd, c, k, relu, tiles, nfull, (int)ids);
+                       (const _Float16*)res, (_Float16*)y, (int)m, h, wd, c, k, relu, tiles, nfull, (int)ids, dhw, dw);
   else
     hipLaunchKernelGGL(k_conv3x3_f16<false>, grid, dim3(kThreads), 0, stream, (const char*)x, (const char*)w, (const _Float16*)bias,
-                       (const _Float16*)nullptr, (_Float16*)y, (int)m, h, wd, c, k, relu, tiles, nfull, (int)ids);
+                       (const _Float16*)nullptr, (_Float16*)y, (int)m, h, wd, c, k, relu, tiles, nfull, (int)ids, dhw, dw);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
@@ -638,6 +702,16 @@ extern "C" int64_t elfnet_conv3x3_f16_plan(int64_t tiles, int columns, int round
     if (half) *half = wi.half;
   }
   return groups;
+}
+
+// Host arithmetic only: the multiplier and the shift the kernel divides a position by `divisor` with (recip_of): for every
+// 0 <= n < 2^31, n / divisor == (((n + 1) * mul) >> 32) >> shift, the product in 64 bits.
+extern "C" int elfnet_conv3x3_f16_recip(int64_t divisor, uint32_t* mul, uint32_t* shift) {
+  if (divisor < 1 || divisor > ((int64_t)1 << 31) || !mul || !shift) return ELFGO_E_BADARG;
+  const Recip r = recip_of((uint32_t)divisor);
+  *mul = r.mul;
+  *shift = r.shift;
+  return 0;
 }
 
 // Host arithmetic only: the workgroups of that launch.  Workgroup g runs the work ids g, g + G, g + 2 G, ... of the plan.

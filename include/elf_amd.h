@@ -742,6 +742,10 @@ int64_t elfnet_conv3x3_f16_plan(int64_t tiles, int columns, int round_width, int
 /* Host arithmetic: the workgroups G of that launch, min(round_width, work ids), or ELFGO_E_BADARG for what _plan refuses.
  * Workgroup g runs the work ids g, g + G, g + 2 G, ... in ascending order; a half id is the last one of its workgroup. */
 int64_t elfnet_conv3x3_f16_grid(int64_t tiles, int columns, int round_width);
+/* Host arithmetic: the multiplier and shift algo 1's kernel divides a position by `divisor` with (its launch's H * W and W):
+ * for every 0 <= n < 2^31, n / divisor == (((n + 1) * mul) >> 32) >> shift, the product taken in 64 bits.  1 <= divisor <= 2^31,
+ * otherwise (or with a NULL out pointer) ELFGO_E_BADARG; 0 on success. */
+int elfnet_conv3x3_f16_recip(int64_t divisor, uint32_t* mul, uint32_t* shift);
 /* The same function as elfnet_conv3x3_f16 -- same tensors, same roundings, algo 0's accumulation order and therefore its output
  * bits -- on a third main loop, for calls of a few thousand positions (a single game's 16-row net call is 5 776): tiles of
  * 64 positions x 64 output channels, one plain launch of ceil(rows * h * wd / 64) x (k / 64) workgroups, so that such a call
