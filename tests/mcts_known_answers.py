@@ -293,6 +293,67 @@ ALL_CASES = [case_select_the_high_prior, case_backup_arithmetic_and_sign_white_r
              case_virtual_loss_keeps_a_dominant_prior, case_virtual_loss_unseats_a_narrow_lead]
 
 
+# ---- positional superko inside the tree (not in mcts_test.cc; go_state.h:117-124,194-203) ----------------------------------------
+def _superko_case(engine, t, pre=()):
+    """One search of 24 rollouts (one per batch) from pre + SUPERKO_GAME[:t] with superko_lines.line_net: the search walks down the
+    game, the node after move 76 repeats the position after move 73 and is terminal with value +1 (-1 with the colours swapped by a
+    leading pass), never sent to the net.  Expectation: superko_lines.expected_line_edge, a closed form derived there by hand.
+    Fails if the repetition is missed (the node goes to the net: one more row in net.seen, V = 0 instead of +-1 in the reward, and a
+    subtree grows below it), if it is scored by Tromp-Taylor or with the wrong sign, or if a live node of the line is taken for a
+    repetition (an early +-1 in the reward, fewer net rows)."""
+    import superko_lines as sl
+    G = sl.SUPERKO_GAME
+    last, R, sign = len(G) - 1, 24, -1 if len(pre) % 2 else 1
+    net = sl.line_net(N, list(pre), G, t)
+    log = engine(list(pre) + G[:t], config(R, 1), net)
+    c = G[t]
+    _only(log, {(c % (N + 2) - 1, c // (N + 2) - 1): sl.expected_line_edge(t, R, last, 0.125, sign)})
+    assert len(net.seen) == sl.line_rows(t, last) and all(v == np.float32(0.125) for v in net.seen), net.seen
+    assert log["best_action"] == c
+
+
+def case_superko_repeats_the_second_newest_game_record(engine):
+    """root after move 75: the repeated position (after move 73) is the game's second-newest record; the terminal is the root's child"""
+    _superko_case(engine, 75)
+
+
+def case_superko_repeats_the_newest_game_record(engine):
+    """root after move 74: the repeated position is the newest record that precedes the root -- the boundary of the records the
+    game contributes"""
+    _superko_case(engine, 74)
+
+
+def case_superko_repeats_the_root_itself(engine):
+    """root after move 73: the repeated position is the root node's own"""
+    _superko_case(engine, 73)
+
+
+def case_superko_repeats_an_interior_tree_node(engine):
+    """root after move 72: the repeated position is a tree node between the root and the terminal"""
+    _superko_case(engine, 72)
+
+
+def case_superko_repeats_a_deeper_interior_node(engine):
+    """root after move 68: terminal at depth 8, the repeated position five nodes below the root"""
+    _superko_case(engine, 68)
+
+
+def case_superko_colours_swapped_game_record(engine):
+    """a leading pass swaps the colours: Black makes the repetition, White is to move in it, value -1; root after move 75"""
+    _superko_case(engine, 75, pre=(0,))
+
+
+def case_superko_colours_swapped_interior_node(engine):
+    """colours swapped, root after move 72: value -1 backed up through White and Black nodes alike"""
+    _superko_case(engine, 72, pre=(0,))
+
+
+ALL_CASES += [case_superko_repeats_the_second_newest_game_record, case_superko_repeats_the_newest_game_record,
+              case_superko_repeats_the_root_itself, case_superko_repeats_an_interior_tree_node,
+              case_superko_repeats_a_deeper_interior_node, case_superko_colours_swapped_game_record,
+              case_superko_colours_swapped_interior_node]
+
+
 # ---- the two CPU engines -------------------------------------------------------------------------------------------------------
 def _first_search(r):
     assert len(r["search"]) == 1

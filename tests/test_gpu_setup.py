@@ -191,9 +191,7 @@ def test_planes_after_setup(elf):
 # ---- 8. super-ko after a setup -------------------------------------------------------------------------------------------------
 # A 9x9 game that ends on a positional repetition (a send-two-return-one cycle on the edge): the position after move 76 is the
 # position after move 73.  Reference Coords.
-SUPERKO_GAME = [41, 45, 96, 67, 83, 15, 24, 75, 101, 42, 26, 73, 37, 71, 31, 90, 16, 70, 91, 48, 86, 19, 36, 62, 81, 17, 25, 50, 58,
-                38, 84, 69, 47, 23, 12, 60, 57, 20, 89, 27, 18, 107, 52, 13, 108, 102, 14, 28, 85, 95, 104, 51, 106, 92, 103, 46, 78,
-                30, 102, 80, 105, 79, 82, 39, 68, 16, 72, 59, 107, 34, 93, 100, 64, 53, 31, 42]
+from superko_lines import SUPERKO_GAME  # noqa: E402  (the search's own tests walk the same game: tests/superko_lines.py)
 
 
 def test_superko_after_setup(elf):
