@@ -33,9 +33,11 @@
 //             a half tile's time.  Same kernel, same launch, same K chain per output element: the bits do not change.  The host
 //             entry decides (full_items below).
 //   items     a launch is G = min(round width, work ids) workgroups; workgroup g runs the ids g, g + G, ... in ascending order,
-//             statically, depending on no other workgroup.  Behind an item's last barrier it decodes the next item's rows, issues
-//             that item's whole prologue into the staging buffers and only then runs its own epilogue: the stores drain, and the
-//             next first K tile lands, at the same time (finish_item has the order and the counts).
+//             statically, depending on no other workgroup.  A full item with a full item behind it stages that item's first seven
+//             half-tiles from its own last two K tiles, in the slots that would stage nothing, so the staging stream does not
+//             stop between two main loops and only the wave-private epilogue lies between them (main_loop, `chained`).  The
+//             workgroup's last full item ends drained: behind its last barrier it decodes the half item's rows, if one follows,
+//             issues that item's whole prologue and only then runs its own epilogue (finish_item has the order and the counts).
 //
 // The operands are swapped in the MFMA (A = weights, B = activations) so that a lane's accumulator registers run along the
 // channels: four consecutive channels of one position per register group, one ds_write_b64 each.
@@ -236,8 +238,17 @@ __device__ __forceinline__ void issue_prologue(const Ctx& c, const Rows& rw, int
 // The main loop of one work item: 256 positions x kNT * 128 output channels (kNT = 2: the full tile, 1: the half tile) over all
 // of K, into acc.  Entered with the item's prologue issued, waited for and behind its barrier.  Comments are written for the full
 // tile; the half tile's differences stand at the `kNT == 1` branches.
-template <int kNT>
-__device__ __forceinline__ void main_loop(const Ctx& c, const Rows& rw, floatx16 (&acc)[4][kNT]) {
+// The full tile's loop also takes what the chain needs (the comment at `chained` below): par, the LDS buffer of the item's K tile
+// 0; stores, whether the item before it on this workgroup left 16 stores per lane behind its carried pieces; and, with kChain (a
+// full item follows this full item on the workgroup), that item's tile and first channel: it decodes that item's rows, stages its
+// first seven half-tiles and leaves its rows in rw.  The two kinds of full item are two copies of the loop, and the kernel runs
+// its chained items in a loop of their own: with both ends behind one steady loop this compiler allocates the accumulators twice
+// and spills some 400 registers.
+template <int kNT, bool kChain>
+__device__ __forceinline__ void main_loop(const Ctx& c, Rows& rw, floatx16 (&acc)[4][kNT], int par, bool stores, int ntile,
+                                          int nkbase) {
+  static_assert(kNT == 2 || !kChain, "only a full item is chained");
+  Rows rn;   // the next item's rows (kChain)
   char* const lds = c.lds;
   const int lane = c.lane, wv = c.wv;
   // ---- fragments: lane (fr = lane & 31, fh = lane >> 5) holds row fr of a 32-row MFMA tile and 8 of the 16 k of one MFMA
@@ -254,6 +265,9 @@ __device__ __forceinline__ void main_loop(const Ctx& c, const Rows& rw, floatx16
   auto ldx = [&](const char* b, int mt, int kk) { return *(const half8*)(b + xrow + mt * 4096 + cs[kk]); };
   auto ldw = [&](const char* b, int nt, int kk) { return *(const half8*)(b + wrow + nt * 4096 + cs[kk]); };
 
+  // The full tile's K tile 0 is a copy of its own in front of the loop, and there the compiler folds these zeros into the first MFMA
+  // of every accumulator as its C operand (C = 0: +0 plus the products, the same bits): no v_mov_b32 is left of them.  The half
+  // tile's stay 64 v_mov_b32.
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
@@ -342,16 +356,19 @@ __device__ __forceinline__ void main_loop(const Ctx& c, const Rows& rw, floatx16
     raw_barrier();
   };
 
-  // mode 0: a K tile with two more behind it; 1: the last but one; 2: the last
-  auto ktile = [&](auto mode, int t) {
-    constexpr int kMode = decltype(mode)::v;
-    const int cur = t & 1;
+  // One K tile.  kP1, kP2: the pieces M1 and M2 stage (2 or 0; 2 + 2 kNT or 0), from rw at (tap1, kc1) and (tap2, kc2); kW1, kW2:
+  // the counts of its two waits; first = 1: K tile 0 of a full item (the waits below, the next item's decode), 2: the last but one
+  // K tile of a chained item (the turn below).  tc is the tile's index in the workgroup's chain of K tiles: its buffer is tc & 1.
+  auto ktile = [&](auto p1, auto p2, auto w1, auto w2, auto first, int tc, int tap1, int kc1, int tap2, int kc2) {
+    constexpr int kP1 = decltype(p1)::v, kP2 = decltype(p2)::v, kW1 = decltype(w1)::v, kW2 = decltype(w2)::v;
+    constexpr bool kFirst = decltype(first)::v == 1, kTurn = decltype(first)::v == 2;
+    const int cur = tc & 1;
     const char* b = lds + cur * kBufBytes;
     // the pieces' wave-uniform offsets are made here, in a load segment, so that among the MFMAs a piece is a select, an add and
     // the load
     uint32_t dx1 = 0, dx2 = 0, dw2 = 0;
-    if constexpr (kMode <= 1) dx1 = x_delta(c, k.tap1, k.kc1);
-    if constexpr (kMode == 0) { dx2 = x_delta(c, k.tap2, k.kc2); dw2 = w_delta(c, k.tap2, k.kc2); }
+    if constexpr (kP1 != 0) dx1 = x_delta(c, tap1, kc1);
+    if constexpr (kP2 != 0) { dx2 = x_delta(c, tap2, kc2); dw2 = w_delta(c, tap2, kc2); }
     asm volatile("" : "+s"(dx1), "+s"(dx2), "+s"(dw2));
     // L1
 #pragma unroll
@@ -361,37 +378,99 @@ __device__ __forceinline__ void main_loop(const Ctx& c, const Rows& rw, floatx16
       xf[1][kk] = ldx(b, 1, kk);
       if constexpr (kNT == 2) wb[kk] = ldw(b, 1, kk);
     }
-    wait_staged<kMode == 2 ? 0 : kWaitL1, true>();
+    // K tile 0 behind a carried transition: the 16 stores of the item before are younger than the pieces this wait leaves in
+    // flight and older than nothing it waits for, so they are added to the count; a lane may have issued fewer where that item's
+    // tile had rows at or beyond M, and then the steady count, which is right for no store at all and stronger otherwise
+    if (kFirst && stores) wait_staged<kW1 + 8 * kNT, true>();
+    else wait_staged<kW1, true>();
     raw_barrier();
     // M1
-    mseg(Mode<0>{}, Mode<kMode <= 1 ? 2 : 0>{}, cur, k.tap1, dx1, 0);
+    mseg(Mode<0>{}, p1, cur, tap1, dx1, 0);
     // L2
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
       xf[0][kk] = ldx(b, 2, kk);
       xf[1][kk] = ldx(b, 3, kk);
     }
-    wait_staged<kMode == 2 ? 0 : kWaitL2, true>();
+    // the next item's rows, decoded here once per item, in the load segment with the longest wait at its barrier; nothing is
+    // staged from them before M2 of the item's last but one K tile
+    if constexpr (kFirst && kChain) decode_rows<2>(c, rn, ntile, nkbase);
+    // the turn: M1 of the item's last but one K tile was the last to stage from the item's own rows, and everything from this
+    // tile's M2 on is staged from the next item's, which become rw here
+    if constexpr (kTurn) rw = rn;
+    if (kFirst && stores) wait_staged<kW2 + 8 * kNT, true>();
+    else wait_staged<kW2, true>();
     raw_barrier();
     // M2
-    mseg(Mode<1>{}, Mode<kMode == 0 ? 2 + 2 * kNT : 0>{}, cur, k.tap2, dx2, dw2);
+    mseg(Mode<1>{}, p2, cur, tap2, dx2, dw2);
   };
+  auto next_k = [&]() {
+    k.tap1 = k.tap2; k.kc1 = k.kc2;
+    if (++k.kc2 == kchunks) { k.kc2 = 0; ++k.tap2; }
+  };
+  const Mode<2> kX{};                 // M1's pieces: Xb
+  const Mode<2 + 2 * kNT> kXW{};      // M2's: Xa, Wa, Wb (Xa, Wh)
+  const Mode<0> kNone{};
+  const Mode<kWaitL1> kL1{};
+  const Mode<kWaitL2> kL2{};
   const int late = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8);   // waves 4..7: the second wave of every SIMD
+  auto leave = [&]() {
+#if ELFNET_CONV3X3_PRIO == 2
+    __builtin_amdgcn_s_setprio(0);
+#endif
+    if (!late) raw_barrier();
+  };
   if (late) raw_barrier();
 #if ELFNET_CONV3X3_PRIO == 2
   if (late) __builtin_amdgcn_s_setprio(1);
 #endif
-  for (int t = 0; t < ktiles - 2; ++t) {
-    ktile(Mode<0>{}, t);
-    k.tap1 = k.tap2; k.kc1 = k.kc2;
-    if (++k.kc2 == kchunks) { k.kc2 = 0; ++k.tap2; }
+  if constexpr (kNT == 1) {
+    for (int t = 0; t < ktiles - 2; ++t) {
+      ktile(kX, kXW, kL1, kL2, kNone, t, k.tap1, k.kc1, k.tap2, k.kc2);
+      next_k();
+    }
+    ktile(kX, kNone, kL1, kL2, kNone, ktiles - 2, k.tap1, k.kc1, 0, 0);   // the last but one: waits as every tile before it
+    ktile(kNone, kNone, kNone, kNone, kNone, ktiles - 1, 0, 0, 0, 0);     // the last: for everything, in its L1
+  } else {
+    // chained: a full item follows this one on the workgroup.  The staging stream then runs on into it: with T = ktiles, K tile
+    // T + j of this item is K tile j of the next, staged from the next item's rows (rn, decoded in L2(0); they become rw in
+    // L2(T-2), behind the last piece of the item's own), and the slots that would stage nothing get their pieces back, in the
+    // prologue's issue order:
+    //   M2(T-2)  Xa Wa Wb of the next item's K tile 0      M1(T-1)  Xb of its K tile 0      M2(T-1)  Xa Wa Wb of its K tile 1
+    // So K tiles T - 2 and T - 1 are steady tiles: they wait with 6 and 2, and the queue is never empty between two main loops.
+    // The buffer of a K tile is the parity of its index in the chain (tc = par + t): with an odd T the next item starts in the
+    // other buffer, and the kernel carries par from item to item.
+    //   landed   the steady rule, continued: L2(T-1)'s wait is for Xa, Wa, Wb of tile T (the next item's 0), with Xb(T) of M1(T-1)
+    //            behind them: vmcnt(2), by every wave, in front of a barrier; they are read in the next item's L1(0), behind at
+    //            least three more barriers (M2(T-1)'s, the stagger's one, the transition's).  The next L1(0)'s wait is for Xb(T),
+    //            read in its L2(0): behind it Xa, Wa, Wb of T + 1 (6) and the epilogue's stores (16): vmcnt(22); its L2(0)'s is for
+    //            Xa, Wa, Wb of T + 1, read in L1(1): behind them the 16 stores and Xb(T+1) of M1(0): vmcnt(18).  From the next K
+    //            tile 1 on the stores are older than whatever is waited for and the steady counts hold.  (The epilogue's own wait
+    //            for its bias and skip registers is the compiler's vmcnt(0), which also retires the eight carried loads: these
+    //            counts do not rely on it.)
+    //   free     M2(T-2), M1(T-1) and M2(T-1) restage what the steady M2, M1, M2 of those tiles restage, read in L1(T-2), L2(T-2)
+    //            and L1(T-1): two barriers between the late half's read and the early half's restaging, as above.  The next item's
+    //            M1(0) and M2(0) restage Xb of tile T - 1's buffer (read in L2(T-1)) and Xa, Wa, Wb of tile T - 2's (last read
+    //            in L1(T-2); as tile T's, in its own L1(0)): the steady distances plus the transition's two barriers.  The
+    //            epilogue between them touches only the wave's own 4 KiB behind the K-tile buffers.
+    // A full item that is its workgroup's last, or has a half item behind it, ends drained as before: its last but one K tile
+    // stages Xb of the last in M1 and nothing in M2, its last nothing and waits with 0.
+    ktile(kX, kXW, kL1, kL2, Mode<1>{}, par, k.tap1, k.kc1, k.tap2, k.kc2);
+    next_k();
+    for (int t = 1; t < ktiles - 2; ++t) {
+      ktile(kX, kXW, kL1, kL2, kNone, par + t, k.tap1, k.kc1, k.tap2, k.kc2);
+      next_k();
+    }
+    if constexpr (kChain) {
+      const KPos kn = first_kpos(fresh_uniform(kchunks));
+      ktile(kX, kXW, kL1, kL2, Mode<2>{}, par + ktiles - 2, k.tap1, k.kc1, 0, 0);
+      ktile(kX, kXW, kL1, kL2, kNone, par + ktiles - 1, 0, 0, kn.tap1, kn.kc1);
+    } else {
+      ktile(kX, kNone, kL1, kL2, kNone, par + ktiles - 2, k.tap1, k.kc1, 0, 0);
+      ktile(kNone, kNone, kNone, kNone, kNone, par + ktiles - 1, 0, 0, 0, 0);
+    }
   }
-  ktile(Mode<1>{}, ktiles - 2);
-  ktile(Mode<2>{}, ktiles - 1);
-#if ELFNET_CONV3X3_PRIO == 2
-  __builtin_amdgcn_s_setprio(0);
-#endif
-  if (!late) raw_barrier();
+  leave();
   // Barriers of one item, per wave: the prologue's, 4 per K tile, and the stagger's one (in front of the loop for waves 4..7,
   // behind it for waves 0..3): 4 ktiles + 2 for every wave, so the items of a workgroup stay paired whatever their kind.  Behind
   // the last of them every wave is past its last fragment read: a wave 4..7 arrives there from its last M2, with the lgkmcnt(0) of
@@ -527,7 +606,8 @@ __device__ __forceinline__ void epilogue(const Ctx& c, const half4 (&hacc)[4][kN
   }
 }
 
-// The end of one item and the start of the next (kNext = 2: a full item follows, 1: a half item, 0: nothing).  Order:
+// The drained end of one item and the start of the next (kNext = 1: a half item follows, 0: nothing; 2, a full item, is written
+// out too but no longer used: a full item in front of a full item ends in finish_chained below).  Order:
 //   bias and skip loads of this item (1 + 16 plain loads with the skip, 1 without)
 //   the next item's rows decoded over this item's (dead since its last staging), its whole prologue issued (14 or 10 LDS-DMA loads)
 //   this item's epilogue: four passes, 4 stores each (the half tile: 2)
@@ -589,6 +669,50 @@ __device__ __forceinline__ void finish_item(Ctx& c, int lane, Rows& rw, const fl
   }
 }
 
+// The end of a full item whose staging stream has run on into the next full item (main_loop, `chained`): nothing of the next item
+// is left to do here, its rows are decoded and its first seven half-tiles are issued, eight loads of them still in flight.  Order:
+//   the 16 skip loads, directly behind the item's last barrier: the fragment registers are dead, and the skip's miss latency
+//   is what this path still exposes; then the bias load, and the conversions, which the loads return under
+//   the compiler's wait for the bias and skip registers, made to stand behind the conversions as finish_item does (left to their
+//   first uses inside the passes' branches, it comes back as a vmcnt(0) in the next item's first load segment, behind the stores):
+//   with LDS-DMA loads pending it is a vmcnt(0), which also retires the eight carried loads, all older than the skip loads
+//   the epilogue: four passes, 4 stores each, no wait on vmcnt
+//   the transition's barrier, with no wait in front of it: what the next L1(0) reads was waited for in L2 of this item's last K tile
+// Returns whether every lane issued all its 16 stores (the next item's first K tile counts them).
+template <bool kHasRes>
+__device__ __forceinline__ bool finish_chained(Ctx& c, int lane, const floatx16 (&acc)[4][2], const _Float16* __restrict__ bias,
+                                               const _Float16* __restrict__ res, _Float16* __restrict__ y, int tile, int kbase) {
+  Skip<kHasRes, 2> s;
+  c.lane = fresh(lane);
+  load_skip<kHasRes, 2>(c, s, res, tile, kbase);
+  __builtin_amdgcn_sched_barrier(0);
+  load_bias<kHasRes, 2>(c, s, bias, tile, kbase);
+  __builtin_amdgcn_sched_barrier(0);
+  half4 hacc[4][2][4];
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) hacc[mt][nt][g][i] = (_Float16)acc[mt][nt][g * 4 + i];
+        asm volatile("" : "+v"(hacc[mt][nt][g]));   // converted here, not where it is written out
+      }
+  c.lane = fresh(lane);
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("" ::"v"(s.bv));
+  if constexpr (kHasRes) {
+#pragma unroll
+    for (int it = 0; it < 16; ++it) asm volatile("" ::"v"(s.rv[it]));
+  }
+  const bool all = __builtin_amdgcn_readfirstlane((tile + 1) * kTileM <= c.M);
+  if (all) epilogue<kHasRes, 2, true>(c, hacc, s, y, tile, kbase);
+  else epilogue<kHasRes, 2, false>(c, hacc, s, y, tile, kbase);
+  raw_barrier();
+  return all;
+}
+
 // One workgroup runs the work ids g, g + G, g + 2 G, ... of the launch (G = gridDim.x), in ascending order.  The host entry makes
 // G = min(round width, ids), so where the last round is split the full ids are a multiple of G: a workgroup's first item is a
 // full one and a half item, if it has one, is its last (at most one: there are at most G half ids).
@@ -612,34 +736,42 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv3x3_f16(const char* __restr
   issue_prologue<2>(c, rw, Cin >> 6);
   wait_staged<8, false>();   // Xa, Wa, Wb of K tile 0; behind them Xb(0), Xa(1), Wa(1), Wb(1)
   raw_barrier();
-  // The three ends of a full item are uniform branches that do not meet again: each has its own epilogue, so the compiler's
-  // counts for the bias and skip registers are those of one path (joined, it would take the path without a prologue and wait
-  // for the other paths' prologues), and a return of its own.
+  // What follows an item is known before its main loop, and is the same for every wave.  While it is a full item the staging
+  // stream runs on into it and the item ends in finish_chained; the workgroup's last full item ends drained, in finish_item, with
+  // a half item or nothing behind it.  The three ends are uniform branches that do not meet again: each has its own epilogue, so
+  // the compiler's counts for the bias and skip registers are those of one path (joined, it would take the path without a
+  // prologue and wait for the other paths' prologues).
   const int lane = c.lane;
-  int hk = 0;
+  const int ktiles = 9 * (Cin >> 6);
+  int par = 0, nid;
+  bool stores = false;
+  WorkItem nwi = wi;
   for (;;) {
+    nid = id + G;
+    if (nid >= ids) break;
+    nwi = work_item(nid, tiles, nfull);
+    if (__builtin_amdgcn_readfirstlane(nwi.half) >= 0) break;
     floatx16 acc[4][2];
     c.lane = fresh(lane);
-    main_loop<2>(c, rw, acc);
-    const int nid = id + G;
-    if (nid >= ids) {
-      finish_item<kHasRes, 2, 0>(c, lane, rw, acc, bias, res, y, wi.tile, wi.col * kTileN, 0, 0);
-      return;
-    }
-    const WorkItem nwi = work_item(nid, tiles, nfull);
-    if (__builtin_amdgcn_readfirstlane(nwi.half) >= 0) {
-      const int nkbase = nwi.col * kTileN + nwi.half * (kTileN / 2);
-      finish_item<kHasRes, 2, 1>(c, lane, rw, acc, bias, res, y, wi.tile, wi.col * kTileN, nwi.tile, nkbase);
-      wi = nwi; hk = nkbase;
-      break;
-    }
-    finish_item<kHasRes, 2, 2>(c, lane, rw, acc, bias, res, y, wi.tile, wi.col * kTileN, nwi.tile, nwi.col * kTileN);
+    main_loop<2, true>(c, rw, acc, par, stores, nwi.tile, nwi.col * kTileN);
+    stores = finish_chained<kHasRes>(c, lane, acc, bias, res, y, wi.tile, wi.col * kTileN);
+    par = (par + ktiles) & 1;
     id = nid;
     wi = nwi;
   }
+  floatx16 acc[4][2];
+  c.lane = fresh(lane);
+  main_loop<2, false>(c, rw, acc, par, stores, 0, 0);
+  if (nid >= ids) {
+    finish_item<kHasRes, 2, 0>(c, lane, rw, acc, bias, res, y, wi.tile, wi.col * kTileN, 0, 0);
+    return;
+  }
+  const int hk = nwi.col * kTileN + __builtin_amdgcn_readfirstlane(nwi.half) * (kTileN / 2);
+  finish_item<kHasRes, 2, 1>(c, lane, rw, acc, bias, res, y, wi.tile, wi.col * kTileN, nwi.tile, hk);
+  wi = nwi;
   floatx16 acch[4][1];
   c.lane = fresh(lane);
-  main_loop<1>(c, rw, acch);
+  main_loop<1, false>(c, rw, acch, 0, false, 0, 0);
   finish_item<kHasRes, 1, 0>(c, lane, rw, acch, bias, res, y, wi.tile, hk, 0, 0);
 }
 
