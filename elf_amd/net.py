@@ -174,6 +174,16 @@ class FusedInferenceNet:
     fp16 channels_last MIOpen's fusion plan falls back to naive kernels, > 10x slower.)
     Same function as PolicyValueNet.forward (src_py/elfgames/go/df_model3.py:62-110,224-313) up to fp16 rounding: the conv result
     is rounded to fp16 once and the epilogue once, where the eager sequence rounds after every kernel.
+    That sequence (the exact sum -> fp16; + bias (+ skip) in fp32, max(., 0); -> fp16) is this library's kernels': on a calibrated
+    net every trunk convolution of every route is the documented epilogue of the fp64 sum rounded to fp16 or of an fp16 neighbour of
+    it, and differs from the former in 0.01 to 0.02 % of its elements (tests/test_gpu_net_trained_like.py, on an MI355X).  The two
+    ends are PyTorch's ops and promise less.  The input convolution is whatever solver MIOpen picks for the shape: measured there, its
+    fp16 result is still a neighbour of the rounded exact sum, but another one than it in 13 to 17 % of the elements, so its sum is
+    not an fp32 sum rounded once; the final trunk activation is 1.13 to 1.19 times as far from fp64 as the documented sequence's
+    (NativeInferenceNet's: 1.00).  And the heads need not return the same bits twice: at 19 x 19 x 256 and 8 rows MIOpen's 1 x 1 policy
+    head convolution returned other bits call after call for one activation of that net, in every run of the test (about 1600 of
+    5776 outputs; for a random-init net's activation it repeated), which moves pi by up to its distance from fp64 again.
+    NativeInferenceNet has neither property.
     Unlike the eager net, a NaN in front of a ReLU becomes 0 (the kernels' max is fmaxf, torch.relu keeps the NaN): a diverged
     activation does not show as NaN in pi or V."""
 
