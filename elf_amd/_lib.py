@@ -156,6 +156,11 @@ SIGNATURES = {
     "elfnet_conv3x3_f16_width": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "elfnet_conv3x3_f16_plan": (_i64, [_i64, _i, _i, _i64, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "elfnet_conv3x3_f16_grid": (_i64, [_i64, _i, _i]),
+    "elfnet_conv3x3_f16_boards": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp]),
+    "elfnet_conv3x3_f16_boards_plan": (_i64, [_i64, _i, _i, _i, _i, _i64, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "elfnet_conv3x3_f16_boards_deal": (_i64, [_i64, _i, _i, _i, _i, _i, _i]),
+    "elfnet_conv3x3_f16_boards_load": (_i64, [_i64, _i, _i, _i, _i, _i, _i]),
+    "elfnet_conv3x3_f16_order": (_i, [_i64, _i, _i, _i, _i, _i]),
     "elfnet_conv3x3_f16_recip": (_i, [_i64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "elfnet_conv3x3_small_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "elfnet_conv3x3_in_f16": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),

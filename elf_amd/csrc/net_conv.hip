@@ -12,8 +12,10 @@
 //         whose strides differ from E's, so a [K] bias would have to be expanded to a whole activation.  The ABD op builds the same
 //         gridwise GEMM (same K order y, x, c; same pipeline v1) and gives each D its own descriptor (G_K layout for the bias).
 // algo 1  not CK: the hand-written 256 x 256 x 64 LDS-DMA kernel of net_conv3x3.hip, an object of its own that this file only
-//         calls (elfnet_conv3x3_native_f16, hidden; that object exports only elfnet_conv3x3_f16_plan, host arithmetic).  Same K
-//         order and MFMA as algo 0.  elfnet_conv3x3_f16_width hands algo 1 the round width its split of the last round goes by.
+//         calls (elfnet_conv3x3_native_f16, hidden; that object exports only host arithmetic: the plans of its two row orders
+//         and the rule that chooses between them).  Same K order and MFMA as algo 0.  elfnet_conv3x3_f16_width hands algo 1 the
+//         round width its split of the last round goes by and keeps it on the linear order, elfnet_conv3x3_f16_boards forces
+//         board order, and the plain entry lets that object choose by shape.
 //
 // This translation unit is its own object (GNUmakefile): the CK templates take ~40 s each to compile and depend on none of the
 // project's .cuh files, which is also why it carries its own small device guard instead of including engine_host.h.
@@ -134,16 +136,14 @@ int run(const void* x, const void* w, const std::array<const void*, ND>& ds, voi
 // net_conv3x3.hip
 extern "C" __attribute__((visibility("hidden"))) int elfnet_conv3x3_native_f16(const void* x, const void* w, const void* bias,
                                                                                const void* res, void* y, int64_t rows, int h, int wd,
-                                                                               int c, int k, int relu, int round_width,
+                                                                               int c, int k, int relu, int round_width, int order,
                                                                                hipStream_t stream);
 
-extern "C" int elfnet_conv3x3_f16(const void* x, const void* w, const void* bias, const void* res, void* y, int64_t rows, int h, int wd,
-                                  int c, int k, int relu, int algo, void* stream) {
-  return elfnet_conv3x3_f16_width(x, w, bias, res, y, rows, h, wd, c, k, relu, algo, 0, stream);
-}
+namespace {
 
-extern "C" int elfnet_conv3x3_f16_width(const void* x, const void* w, const void* bias, const void* res, void* y, int64_t rows, int h,
-                                        int wd, int c, int k, int relu, int algo, int round_width, void* stream) {
+// order is algo 1's row order: 0 linear, 1 board, -1 the one net_conv3x3.hip chooses for the shape
+int conv3x3_f16(const void* x, const void* w, const void* bias, const void* res, void* y, int64_t rows, int h, int wd, int c, int k,
+                int relu, int algo, int round_width, int order, void* stream) {
   if (!x || !w || !bias || !y || rows < 0 || h <= 0 || wd <= 0 || c <= 0 || k <= 0) return ELFGO_E_BADARG;
   if ((c & 7) != 0 || (k & 7) != 0 || (algo != 0 && algo != 1) || round_width < 0) return ELFGO_E_BADARG;
   if ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)res | (uintptr_t)y) & 15) != 0) return ELFGO_E_BADARG;
@@ -157,8 +157,27 @@ extern "C" int elfnet_conv3x3_f16_width(const void* x, const void* w, const void
   DevGuard _dg(at.device);
   const Shape s{(int)rows, h, wd, c, k};
   hipStream_t st = (hipStream_t)stream;
-  if (algo == 1) return elfnet_conv3x3_native_f16(x, w, bias, res, y, rows, h, wd, c, k, relu, round_width, st);
+  if (algo == 1) return elfnet_conv3x3_native_f16(x, w, bias, res, y, rows, h, wd, c, k, relu, round_width, order, st);
   // one launch whatever the size: the device op splits N itself
   if (res) return run<ConvA<DsBiasRes, T2>, 2>(x, w, {bias, res}, y, s, relu, st, true);
   return run<ConvA<DsBias, T1>, 1>(x, w, {bias}, y, s, relu, st, true);
+}
+
+}  // namespace
+
+extern "C" int elfnet_conv3x3_f16(const void* x, const void* w, const void* bias, const void* res, void* y, int64_t rows, int h, int wd,
+                                  int c, int k, int relu, int algo, void* stream) {
+  return conv3x3_f16(x, w, bias, res, y, rows, h, wd, c, k, relu, algo, 0, -1, stream);
+}
+
+// a named round width keeps algo 1 on the linear order; 0 is the plain entry
+extern "C" int elfnet_conv3x3_f16_width(const void* x, const void* w, const void* bias, const void* res, void* y, int64_t rows, int h,
+                                        int wd, int c, int k, int relu, int algo, int round_width, void* stream) {
+  return conv3x3_f16(x, w, bias, res, y, rows, h, wd, c, k, relu, algo, round_width, round_width > 0 ? 0 : -1, stream);
+}
+
+// algo 1 in board order, whatever the shape and the width
+extern "C" int elfnet_conv3x3_f16_boards(const void* x, const void* w, const void* bias, const void* res, void* y, int64_t rows, int h,
+                                         int wd, int c, int k, int relu, int round_width, void* stream) {
+  return conv3x3_f16(x, w, bias, res, y, rows, h, wd, c, k, relu, 1, round_width, 1, stream);
 }

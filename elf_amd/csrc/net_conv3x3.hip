@@ -13,8 +13,8 @@
 //             once the last half-tile is on its way.  Every staged piece is a full aligned 128-B line: 8 lanes per row.
 //   halo      a staging lane decodes its four rows once (position -> n, h, w: two divisions by launch constants, each a multiply
 //             by a multiplier the host entry made and a shift) and keeps a 9-bit tap mask (a 3-bit row mask times a 3-bit column
-//             mask) and a byte offset; for an off-board tap, and for a row at or beyond M, its source address is a zero-filled
-//             line in global memory.  LDS is never zeroed by a second path.
+//             mask) and a byte offset; for an off-board tap, and for a row at or beyond its item's limit (M; in board order the
+//             last board), its source address is a zero-filled line in global memory.  LDS is never zeroed by a second path.
 //   LDS image lane-linear, as the DMA writes it; the 16-B slot s of row r holds the row's chunk s ^ ((r >> 1) & 7): the XOR is on
 //             the source address when staging and on the read address of the fragment ds_read_b128s, which are then conflict-free
 //             (rows r and r + 1 share a 256-B bank row, so the swizzle steps every second row; checked against the 16-lane groups
@@ -25,15 +25,30 @@
 //             consecutive channels per lane; bias and res are read in that shape, and the values are BiasResAct's of
 //             net_conv.hip: float(half(acc)) + bias (+ res), max(., 0), one rounding to fp16, computed as one v_fma_mix_f32 per
 //             addition (it converts its fp16 operands itself), the rounding, and the ReLU on the packed fp16 pair behind it under
-//             a uniform branch (max and a monotone rounding commute; NaN gives +0 either way).  Rows at or beyond M are not
+//             a uniform branch (max and a monotone rounding commute; NaN gives +0 either way).  Rows at or beyond the limit are not
 //             stored.  No workgroup barrier: a wave reads back what it wrote itself.
 //   tail      the work items of a launch (position tiles x channel columns of 256) run in rounds of one per CU.  Where the last
 //             round is at most half full, each of its items runs as two work ids of 256 positions x 128 channels (the half
 //             tile: the same waves at 128 x 32 each, three staged half-tiles per K tile instead of four), so that round takes
 //             a half tile's time.  Same kernel, same launch, same K chain per output element: the bits do not change.  The host
 //             entry decides (full_items below).
-//   items     a launch is G = min(round width, work ids) workgroups; workgroup g runs the ids g, g + G, ... in ascending order,
-//             statically, depending on no other workgroup.  A full item with a full item behind it stages that item's first seven
+//   orders    the 256 rows of a tile are, in linear order, 256 consecutive positions (n, h, w), about 13.5 rows of a 19 x 19
+//             board: every tile has positions on every edge, runs all nine taps and multiplies the zero line wherever a tap is
+//             off the board, 6.9 % of all K tiles on 19 x 19.  In board order they are one board position (h, w) of 256 consecutive
+//             boards, H W positions apart: every row has the same taps on the board, the item carries that 9-bit mask in a scalar
+//             and its K loop visits only the set taps, ascending (first_tap, next_tap; popcount x Cin / 64 K tiles: 4 taps in a
+//             corner, 6 on an edge, 9 inside; 3025 taps per block of boards on 19 x 19 instead of 3249).  One kernel body: row r of an
+//             item is position base + r stride, valid below limit (decode_rows, load_skip and the epilogue's stores share that one
+//             mapping), and linear order is the mask 0x1FF with the per-row masks below.  The comment at Deal has the ids and how
+//             they are dealt; the host entry chooses the order by shape (order_of).
+//   bits      for finite operands both orders give the same bits, algo 0's: every accumulator takes the same non-zero products in
+//             the same order; what linear order adds is MFMAs whose B operand is all zeros, that is products +-0 added to an
+//             accumulator that started at +0 and can never be -0 (an fp16 product is exact in fp32, and a sum that cancels exactly
+//             is +0 in round-to-nearest), and x + (+-0) = x.  What differs: a non-finite weight at a tap that is off the board for a
+//             position reaches that position in linear order (0 x Inf = NaN) and not in board order.
+//   items     a launch is G = min(round width, work ids) workgroups; workgroup g runs the ids g, g + G, ... in ascending order
+//             (board order: the last, partial round from workgroup G - 1 downwards), statically, depending on no other workgroup.
+//             A full item with a full item behind it stages that item's first seven
 //             half-tiles from its own last two K tiles, in the slots that would stage nothing, so the staging stream does not
 //             stop between two main loops and only the wave-private epilogue lies between them (main_loop, `chained`).  The
 //             workgroup's last full item ends drained: behind its last barrier it decodes the half item's rows, if one follows,
@@ -65,7 +80,7 @@ constexpr int kBufBytes = 2 * kOperandBytes;     // activations, then weights
 constexpr int kWaveCBytes = 4096;                // a wave's own piece of the epilogue: 32 positions x 64 channels fp16
 constexpr int kLdsBytes = 2 * kBufBytes + 8 * kWaveCBytes;   // two K tiles and the eight waves' epilogue pieces: 160 KiB, all a CU has
 
-// the line every off-board tap and every row beyond M is staged from
+// the line every off-board tap and every row at or beyond its item's limit is staged from
 __device__ __attribute__((aligned(128))) unsigned char g_zero_line[128] = {0};
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
@@ -140,6 +155,66 @@ inline Recip recip_of(uint32_t d) {   // 1 <= d <= 2^31
   return Recip{(uint32_t)((((uint64_t)1 << s) - 1) / d), (uint32_t)(s - 32)};
 }
 __device__ __forceinline__ uint32_t div_by(uint32_t n, Recip r) { return __umulhi(n + 1, r.mul) >> r.shift; }
+// the same quotient where the host plans with it too (the deal below); on the device n is wave-uniform there
+__host__ __device__ inline uint32_t udiv_by(uint32_t n, Recip r) { return (uint32_t)(((uint64_t)(n + 1) * r.mul) >> 32) >> r.shift; }
+
+// ---- the two row orders.  A work item is 256 rows x a channel column; row r of it is position base + r * stride, valid for
+// r < limit, and the item visits the taps of `mask` (bit 3 ky + kx), ascending, Cin / 64 K tiles each.
+//   linear  tile t is the positions 256 t .. 256 t + 255: base = 256 t, stride 1, limit = M - base, every tap (0x1FF); what is off
+//           the board is decided per row (decode_rows).  Ids, split last round and deal are work_item's and full_items' above.
+//   board   with B = ceil(rows / 256) blocks of 256 consecutive boards, an item is (block b, board position hw, column): row r is
+//           board 256 b + r at hw, base = 256 b H W + hw, stride H W, limit = rows - 256 b.  Every row has the same taps on the
+//           board, so the item visits only those: 4 for a corner, 6 for an edge, 9 inside.  No half tiles.
+//           id = (rank(hw) * columns + column) * B + b, the block fastest; rank lists the inner positions, then the edges, then
+//           the corners, each class row-major (a board with H or W below 3 has no such classes: rank = hw), so the long items
+//           come first.  With G workgroups and F = ids / G, workgroup g runs g, g + G, ... in the F full rounds and, in the last,
+//           partial round, id F G + (G - 1 - g) if there is one: the last round's items, the shortest, go to the workgroups that
+//           got the shorter items of the round where the classes change.  Static, no workgroup depends on another.
+struct Deal {
+  int board;                 // the row order: 0 linear, 1 board
+  int ids, fullids;          // work ids; board: F G, the ids of the full rounds (linear: never reached)
+  int tiles, nfull;          // linear: work_item's arguments
+  int nblk, per_rank, boards, stride;   // board: B, B * columns, rows, H W (linear: stride 1)
+  Recip dpr, dblk, din, dw;  // board: the divisions by per_rank, B, W - 2 and W
+};
+struct Item { int base, limit, kbase, mask, half; };
+__host__ __device__ inline int tap_mask(int hh, int ww, int H, int W) {
+  const int rowm = (hh > 0 ? 1 : 0) | 8 | (hh + 1 < H ? 64 : 0), colm = (ww > 0 ? 1 : 0) | 2 | (ww + 1 < W ? 4 : 0);
+  return rowm * colm;   // decode_rows has why this is the mask
+}
+// rank -> board position (h, w)
+__host__ __device__ inline void pos_of_rank(int k, int H, int W, Recip din, Recip dw, int& hh, int& ww) {
+  if (H < 3 || W < 3) { hh = (int)udiv_by((uint32_t)k, dw); ww = k - hh * W; return; }
+  const int a = W - 2, inner = (H - 2) * a, side = 2 * (H - 2);
+  if (k < inner) { hh = (int)udiv_by((uint32_t)k, din); ww = k - hh * a + 1; hh += 1; }
+  else if ((k -= inner) < a) { hh = 0; ww = k + 1; }
+  else if ((k -= a) < side) { hh = (k >> 1) + 1; ww = (k & 1) * (W - 1); }
+  else if ((k -= side) < a) { hh = H - 1; ww = k + 1; }
+  else { k -= a; hh = (k >> 1) * (H - 1); ww = (k & 1) * (W - 1); }
+}
+__host__ __device__ inline Item item_of(const Deal& d, int id, int M, int H, int W, int* block = nullptr, int* pos = nullptr) {
+  if (!d.board) {
+    const WorkItem wi = work_item(id, d.tiles, d.nfull);
+    return Item{wi.tile * kTileM, M - wi.tile * kTileM, wi.col * kTileN + (wi.half > 0 ? kTileN / 2 : 0), 0x1FF, wi.half};
+  }
+  const int rank = (int)udiv_by((uint32_t)id, d.dpr), rem = id - rank * d.per_rank;
+  const int col = (int)udiv_by((uint32_t)rem, d.dblk), b = rem - col * d.nblk;
+  int hh, ww;
+  pos_of_rank(rank, H, W, d.din, d.dw, hh, ww);
+  const int hw = hh * W + ww;
+  if (block) *block = b;
+  if (pos) *pos = hw;
+  return Item{b * kTileM * d.stride + hw, d.boards - b * kTileM, col * kTileN, tap_mask(hh, ww, H, W), -1};
+}
+// the id behind `id` on workgroup g of G; at or beyond d.ids: none
+__host__ __device__ inline int next_id(const Deal& d, int id, int g, int G) {
+  if (id >= d.fullids) return d.ids;
+  const int nid = id + G;
+  return nid >= d.fullids ? d.fullids + (G - 1 - g) : nid;
+}
+// the K-tile taps of a mask: the lowest, and the next above t (9 or more: none)
+__host__ __device__ inline int first_tap(int mask) { return __builtin_ctz((unsigned)mask | 0x200u); }
+__host__ __device__ inline int next_tap(int mask, int t) { return t + 1 + __builtin_ctz(((unsigned)mask >> (t + 1)) | 0x200u); }
 
 // What a wave knows about itself and the launch: everything the staging and the epilogue address by.
 struct Ctx {
@@ -147,6 +222,7 @@ struct Ctx {
   const char* x;
   const char* w;
   int M, H, W, Cin, K, relu;
+  int stride;                    // positions between two rows of an item: 1 (linear order) or H W (board order)
   Recip dhw, dw;                 // the decode's divisions by H W and by W
   int lane, wv;                  // wv through readfirstlane: what depends on the wave alone stays in scalar registers
   const unsigned char* zsrc;     // this lane's 16 B of the zero line
@@ -164,23 +240,23 @@ struct Rows { uint32_t xoff[4], woff[4], xmask[4]; };
 // The half tile (kNT == 1) has one weight half-tile per K tile, Wh: its 128 weight rows, LDS row = channel - kbase, wave (wm, wn)
 // reads rows wn * 32 + fr; piece i of wave wv is rows i * 64 + wv * 8 .. + 7 (woff[0..1]).
 template <int kNT>
-__device__ __forceinline__ void decode_rows(const Ctx& c, Rows& rw, int tile, int kbase) {
-  const int lane = c.lane, wv = c.wv;
+__device__ __forceinline__ void decode_rows(const Ctx& c, Rows& rw, const Item& it) {
+  const int lane = c.lane, wv = c.wv, kbase = it.kbase;
   const uint32_t hw = (uint32_t)(c.H * c.W), wd = (uint32_t)c.W;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int hf = j >> 1, i = j & 1;
     const int r = i * 128 + hf * 64 + wv * 8 + (lane >> 3);
-    const int p = tile * kTileM + r;
+    const int p = it.base + r * c.stride;   // the one mapping of (item, row) to a position; load_skip and epilogue have it too
     // tap 3 ky + kx is on the board iff row hh + ky - 1 and column ww + kx - 1 are: the rows' three bits stand at 0, 3 and 6, the
     // columns' at 0, 1 and 2, and their product has bit 3 ky + kx set iff both are (no carries: the column mask is below 8)
     const uint32_t rem = (uint32_t)p - div_by((uint32_t)p, c.dhw) * hw, hh = div_by(rem, c.dw), ww = rem - hh * wd;
     const uint32_t rowm = (hh > 0 ? 1u : 0u) | 8u | ((int)hh + 1 < c.H ? 64u : 0u);
     const uint32_t colm = (ww > 0 ? 1u : 0u) | 2u | ((int)ww + 1 < c.W ? 4u : 0u);
     uint32_t m = __umul24(rowm, colm);
-    asm("" : "+v"(m));   // made for every row and selected, with no branch around the arithmetic for the rows at or beyond M
-    rw.xmask[j] = p < c.M ? m : 0u;
-    rw.xoff[j] = (uint32_t)p * (uint32_t)(c.Cin * 2) + (((lane & 7) ^ ((r >> 1) & 7)) << 4);   // below 2^31 wherever it is used (p < M)
+    asm("" : "+v"(m));   // made for every row and selected, with no branch around the arithmetic for the rows at or beyond the limit
+    rw.xmask[j] = r < it.limit ? m : 0u;
+    rw.xoff[j] = (uint32_t)p * (uint32_t)(c.Cin * 2) + (((lane & 7) ^ ((r >> 1) & 7)) << 4);   // below 2^31 wherever it is used (a valid row)
     const int rwt = kNT == 2 ? (i * 2 + (wv >> 2)) * 64 + hf * 32 + (wv & 3) * 8 + (lane >> 3) : i * 64 + wv * 8 + (lane >> 3);
     rw.woff[j] = (uint32_t)(kbase + rwt) * (uint32_t)(9 * c.Cin * 2) + (((lane & 7) ^ ((rwt >> 1) & 7)) << 4);
   }
@@ -216,21 +292,22 @@ __device__ __forceinline__ void stage_w(const Ctx& c, const Rows& rw, int hf, in
   for (int i = 0; i < 2; ++i) stage_w_piece<kNT>(c, rw, hf, i, d, buf);
 }
 // K tiles t + 1 and t + 2 of a work item, carried in scalars through its loop
-struct KPos { int tap1, kc1, tap2, kc2; };
-__device__ __forceinline__ KPos first_kpos(int kchunks) {
-  KPos k{0, 1, 0, 2};
-  if (kchunks == 1) { k.tap1 = 1; k.kc1 = 0; k.tap2 = 2; k.kc2 = 0; }
-  else if (kchunks == 2) { k.tap2 = 1; k.kc2 = 0; }
+struct KPos { int tap0, tap1, kc1, tap2, kc2; };
+__device__ __forceinline__ KPos first_kpos(int kchunks, int mask) {
+  const int t0 = first_tap(mask);
+  KPos k{t0, t0, 1, t0, 2};
+  if (kchunks == 1) { k.tap1 = next_tap(mask, t0); k.kc1 = 0; k.tap2 = next_tap(mask, k.tap1); k.kc2 = 0; }
+  else if (kchunks == 2) { k.tap2 = next_tap(mask, t0); k.kc2 = 0; }
   return k;
 }
 // An item's prologue, issue only: Xa Wa Wb Xb of K tile 0 and Xa Wa Wb of K tile 1 (seven half-tiles, 14 loads per wave; the half
 // tile: Xa Wh Xb, Xa Wh, five and 10).  Its wait is wait_staged<kFly> (+ what was issued behind it) and a barrier.
 template <int kNT>
-__device__ __forceinline__ void issue_prologue(const Ctx& c, const Rows& rw, int kchunks) {
-  const KPos k = first_kpos(fresh_uniform(kchunks));   // K tile 1's tap and chunk are made here, per item, not kept
-  stage_x(c, rw, 0, 0, 0, 0); stage_w<kNT>(c, rw, 0, 0, 0, 0);
-  if constexpr (kNT == 2) stage_w<kNT>(c, rw, 1, 0, 0, 0);
-  stage_x(c, rw, 1, 0, 0, 0);
+__device__ __forceinline__ void issue_prologue(const Ctx& c, const Rows& rw, int kchunks, int mask) {
+  const KPos k = first_kpos(fresh_uniform(kchunks), mask);   // K tile 1's tap and chunk are made here, per item, not kept
+  stage_x(c, rw, 0, k.tap0, 0, 0); stage_w<kNT>(c, rw, 0, k.tap0, 0, 0);
+  if constexpr (kNT == 2) stage_w<kNT>(c, rw, 1, k.tap0, 0, 0);
+  stage_x(c, rw, 1, k.tap0, 0, 0);
   stage_x(c, rw, 0, k.tap1, k.kc1, 1); stage_w<kNT>(c, rw, 0, k.tap1, k.kc1, 1);
   if constexpr (kNT == 2) stage_w<kNT>(c, rw, 1, k.tap1, k.kc1, 1);
 }
@@ -245,8 +322,8 @@ __device__ __forceinline__ void issue_prologue(const Ctx& c, const Rows& rw, int
 // its chained items in a loop of their own: with both ends behind one steady loop this compiler allocates the accumulators twice
 // and spills some 400 registers.
 template <int kNT, bool kChain>
-__device__ __forceinline__ void main_loop(const Ctx& c, Rows& rw, floatx16 (&acc)[4][kNT], int par, bool stores, int ntile,
-                                          int nkbase) {
+__device__ __forceinline__ void main_loop(const Ctx& c, Rows& rw, floatx16 (&acc)[4][kNT], int par, bool stores, int mask,
+                                          const Item& nit) {
   static_assert(kNT == 2 || !kChain, "only a full item is chained");
   Rows rn;   // the next item's rows (kChain)
   char* const lds = c.lds;
@@ -317,9 +394,11 @@ __device__ __forceinline__ void main_loop(const Ctx& c, Rows& rw, floatx16 (&acc
   constexpr int kWaitL1 = 2 * (1 + kNT), kWaitL2 = 2;   // loads in flight behind the counted waits: 6 (4), and 2
   constexpr int kM1At[2] = {4 * kNT - 1, 6 * kNT - 1};                                        // 7, 11 (3, 5)
   constexpr int kM2At[6] = {2 * kNT - 1, 2 * kNT + 1, 2 * kNT + 3, kNT == 2 ? 9 : 6, 11, 13};   // 3, 5, 7, 9, 11, 13 (1, 3, 5, 6)
-  const int kchunks = c.Cin >> 6, ktiles = 9 * kchunks;   // at least 9
+  // the item's K tiles: its mask's taps, ascending, kchunks each; 9 kchunks in linear order, down to 2 in board order (the host
+  // entry refuses a shape with an item of one K tile)
+  const int kchunks = c.Cin >> 6, ktiles = __builtin_popcount((unsigned)mask) * kchunks;
   half8 xf[2][4], wa[4], wb[kNT == 2 ? 4 : 1];
-  KPos k = first_kpos(kchunks);
+  KPos k = first_kpos(kchunks, mask);
   auto wfrag = [&](int nt, int kk) -> half8 {
     if constexpr (kNT == 2) return nt ? wb[kk] : wa[kk];
     else return wa[kk];
@@ -361,7 +440,7 @@ __device__ __forceinline__ void main_loop(const Ctx& c, Rows& rw, floatx16 (&acc
   // K tile of a chained item (the turn below).  tc is the tile's index in the workgroup's chain of K tiles: its buffer is tc & 1.
   auto ktile = [&](auto p1, auto p2, auto w1, auto w2, auto first, int tc, int tap1, int kc1, int tap2, int kc2) {
     constexpr int kP1 = decltype(p1)::v, kP2 = decltype(p2)::v, kW1 = decltype(w1)::v, kW2 = decltype(w2)::v;
-    constexpr bool kFirst = decltype(first)::v == 1, kTurn = decltype(first)::v == 2;
+    constexpr bool kFirst = (decltype(first)::v & 1) != 0, kTurn = (decltype(first)::v & 2) != 0;
     const int cur = tc & 1;
     const char* b = lds + cur * kBufBytes;
     // the pieces' wave-uniform offsets are made here, in a load segment, so that among the MFMAs a piece is a select, an add and
@@ -394,7 +473,7 @@ __device__ __forceinline__ void main_loop(const Ctx& c, Rows& rw, floatx16 (&acc
     }
     // the next item's rows, decoded here once per item, in the load segment with the longest wait at its barrier; nothing is
     // staged from them before M2 of the item's last but one K tile
-    if constexpr (kFirst && kChain) decode_rows<2>(c, rn, ntile, nkbase);
+    if constexpr (kFirst && kChain) decode_rows<2>(c, rn, nit);
     // the turn: M1 of the item's last but one K tile was the last to stage from the item's own rows, and everything from this
     // tile's M2 on is staged from the next item's, which become rw here
     if constexpr (kTurn) rw = rn;
@@ -406,7 +485,7 @@ __device__ __forceinline__ void main_loop(const Ctx& c, Rows& rw, floatx16 (&acc
   };
   auto next_k = [&]() {
     k.tap1 = k.tap2; k.kc1 = k.kc2;
-    if (++k.kc2 == kchunks) { k.kc2 = 0; ++k.tap2; }
+    if (++k.kc2 == kchunks) { k.kc2 = 0; k.tap2 = next_tap(mask, k.tap2); }
   };
   const Mode<2> kX{};                 // M1's pieces: Xb
   const Mode<2 + 2 * kNT> kXW{};      // M2's: Xa, Wa, Wb (Xa, Wh)
@@ -455,19 +534,30 @@ __device__ __forceinline__ void main_loop(const Ctx& c, Rows& rw, floatx16 (&acc
     //            epilogue between them touches only the wave's own 4 KiB behind the K-tile buffers.
     // A full item that is its workgroup's last, or has a half item behind it, ends drained as before: its last but one K tile
     // stages Xb of the last in M1 and nothing in M2, its last nothing and waits with 0.
-    ktile(kX, kXW, kL1, kL2, Mode<1>{}, par, k.tap1, k.kc1, k.tap2, k.kc2);
-    next_k();
-    for (int t = 1; t < ktiles - 2; ++t) {
-      ktile(kX, kXW, kL1, kL2, kNone, par + t, k.tap1, k.kc1, k.tap2, k.kc2);
+    // An item of two K tiles (board order, an end of a board one position wide at 64 input channels) has its first K tile for
+    // its last but one: that tile is both, and decodes the next item's rows and turns to them in the same L2.
+    if (ktiles > 2) {
+      ktile(kX, kXW, kL1, kL2, Mode<1>{}, par, k.tap1, k.kc1, k.tap2, k.kc2);
       next_k();
-    }
-    if constexpr (kChain) {
-      const KPos kn = first_kpos(fresh_uniform(kchunks));
-      ktile(kX, kXW, kL1, kL2, Mode<2>{}, par + ktiles - 2, k.tap1, k.kc1, 0, 0);
-      ktile(kX, kXW, kL1, kL2, kNone, par + ktiles - 1, 0, 0, kn.tap1, kn.kc1);
+      for (int t = 1; t < ktiles - 2; ++t) {
+        ktile(kX, kXW, kL1, kL2, kNone, par + t, k.tap1, k.kc1, k.tap2, k.kc2);
+        next_k();
+      }
+      if constexpr (kChain) {
+        const KPos kn = first_kpos(fresh_uniform(kchunks), nit.mask);
+        ktile(kX, kXW, kL1, kL2, Mode<2>{}, par + ktiles - 2, k.tap1, k.kc1, kn.tap0, 0);
+        ktile(kX, kXW, kL1, kL2, kNone, par + ktiles - 1, kn.tap0, 0, kn.tap1, kn.kc1);
+      } else {
+        ktile(kX, kNone, kL1, kL2, kNone, par + ktiles - 2, k.tap1, k.kc1, 0, 0);
+        ktile(kNone, kNone, kNone, kNone, kNone, par + ktiles - 1, 0, 0, 0, 0);
+      }
+    } else if constexpr (kChain) {
+      const KPos kn = first_kpos(fresh_uniform(kchunks), nit.mask);
+      ktile(kX, kXW, kL1, kL2, Mode<3>{}, par, k.tap1, k.kc1, kn.tap0, 0);
+      ktile(kX, kXW, kL1, kL2, kNone, par + 1, kn.tap0, 0, kn.tap1, kn.kc1);
     } else {
-      ktile(kX, kNone, kL1, kL2, kNone, par + ktiles - 2, k.tap1, k.kc1, 0, 0);
-      ktile(kNone, kNone, kNone, kNone, kNone, par + ktiles - 1, 0, 0, 0, 0);
+      ktile(kX, kNone, kL1, kL2, Mode<1>{}, par, k.tap1, k.kc1, 0, 0);
+      ktile(kNone, kNone, kNone, kNone, kNone, par + 1, 0, 0, 0, 0);
     }
   }
   leave();
@@ -525,39 +615,38 @@ struct EpiLane {
   static constexpr int kPos = 64 / kC;         // positions per read-back instruction
   static constexpr int kR = 32 / kPos;         // read-backs per pass
   int pr, q, chan;                             // the lane's position in a read-back, its chunk, its first channel of the item
-  int row0;                                    // the wave's first position
-  __device__ __forceinline__ EpiLane(const Ctx& c, int tile, int kbase)
-      : pr(c.lane / kC), q(c.lane % kC), chan(kbase + (c.wv & 3) * 32 * kNT + (c.lane % kC) * 8),
-        row0(tile * kTileM + (c.wv >> 2) * 128) {}
+  int row0;                                    // the wave's first row of the item
+  __device__ __forceinline__ EpiLane(const Ctx& c, int kbase)
+      : pr(c.lane / kC), q(c.lane % kC), chan(kbase + (c.wv & 3) * 32 * kNT + (c.lane % kC) * 8), row0((c.wv >> 2) * 128) {}
   static __device__ __forceinline__ int swz(int p) { return kNT == 2 ? (p >> 1) & 7 : (p >> 2) & 3; }
 };
 
-// bias and the skip's 16 B per (position, chunk), in the shape the read-back has.  A row beyond M reads the last valid row instead
-// (no branch around a load) and is not stored.
+// bias and the skip's 16 B per (position, chunk), in the shape the read-back has.  A row at or beyond the item's limit reads the
+// tensor's last row instead (no branch around a load) and is not stored.
 template <bool kHasRes, int kNT>
-__device__ __forceinline__ void load_bias(const Ctx& c, Skip<kHasRes, kNT>& s, const _Float16* __restrict__ bias, int tile, int kbase) {
-  const EpiLane<kNT> e(c, tile, kbase);
+__device__ __forceinline__ void load_bias(const Ctx& c, Skip<kHasRes, kNT>& s, const _Float16* __restrict__ bias, const Item& it) {
+  const EpiLane<kNT> e(c, it.kbase);
   s.bv = *(const half8*)(bias + e.chan);
 }
 template <bool kHasRes, int kNT>
-__device__ __forceinline__ void load_skip(const Ctx& c, Skip<kHasRes, kNT>& s, const _Float16* __restrict__ res, int tile, int kbase) {
+__device__ __forceinline__ void load_skip(const Ctx& c, Skip<kHasRes, kNT>& s, const _Float16* __restrict__ res, const Item& it) {
   using E = EpiLane<kNT>;
-  const E e(c, tile, kbase);
+  const E e(c, it.kbase);
   if constexpr (kHasRes) {
 #pragma unroll
-    for (int it = 0; it < 4 * E::kR; ++it) {
-      const int p = e.row0 + (it / E::kR) * 32 + (it % E::kR) * E::kPos + e.pr;
-      s.rv[it] = *(const half8*)(res + (size_t)(p < c.M ? p : c.M - 1) * c.K + e.chan);
+    for (int i = 0; i < 4 * E::kR; ++i) {
+      const int r = e.row0 + (i / E::kR) * 32 + (i % E::kR) * E::kPos + e.pr;
+      s.rv[i] = *(const half8*)(res + (size_t)(r < it.limit ? it.base + r * c.stride : c.M - 1) * c.K + e.chan);
     }
   }
 }
 
-// kAll: every row of the tile is below M, and every lane issues all its 8 kNT stores (the count the next item's first wait uses).
+// kAll: every row of the item is valid, and every lane issues all its 8 kNT stores (the count the next item's first wait uses).
 template <bool kHasRes, int kNT, bool kAll>
 __device__ __forceinline__ void epilogue(const Ctx& c, const half4 (&hacc)[4][kNT][4], const Skip<kHasRes, kNT>& s,
-                                         _Float16* __restrict__ y, int tile, int kbase) {
+                                         _Float16* __restrict__ y, const Item& it) {
   using E = EpiLane<kNT>;
-  const E e(c, tile, kbase);
+  const E e(c, it.kbase);
   char* const cl = c.lds + 2 * kBufBytes + c.wv * kWaveCBytes;
   const int fr = c.lane & 31, fh = c.lane >> 5;
   constexpr int kRowB = 16 * E::kC;
@@ -599,8 +688,8 @@ __device__ __forceinline__ void epilogue(const Ctx& c, const half4 (&hacc)[4][kN
 #pragma unroll
         for (int i = 0; i < 4; ++i) ov[i] = relu_h2(ov[i]);
       }
-      const int p = e.row0 + mt * 32 + j * E::kPos + e.pr;
-      if (kAll || p < c.M) *(uint32x4*)(y + (size_t)p * c.K + e.chan) = ov;
+      const int r = e.row0 + mt * 32 + j * E::kPos + e.pr;
+      if (kAll || r < it.limit) *(uint32x4*)(y + (size_t)(it.base + r * c.stride) * c.K + e.chan) = ov;
     }
     __builtin_amdgcn_wave_barrier();   // the next pass's writes stay behind this pass's read-backs
   }
@@ -621,10 +710,10 @@ __device__ __forceinline__ void epilogue(const Ctx& c, const half4 (&hacc)[4][kN
 //   too high waits for too little: that tile waits with kFly alone, which is right for no store at all and stronger otherwise.
 template <bool kHasRes, int kNT, int kNext>
 __device__ __forceinline__ void finish_item(Ctx& c, int lane, Rows& rw, const floatx16 (&acc)[4][kNT], const _Float16* __restrict__ bias,
-                                            const _Float16* __restrict__ res, _Float16* __restrict__ y, int tile, int kbase,
-                                            int ntile, int nkbase) {
+                                            const _Float16* __restrict__ res, _Float16* __restrict__ y, const Item& it,
+                                            const Item& nit) {
   Skip<kHasRes, kNT> s;
-  load_bias<kHasRes, kNT>(c, s, bias, tile, kbase);
+  load_bias<kHasRes, kNT>(c, s, bias, it);
   __builtin_amdgcn_sched_barrier(0);
   // the accumulators' first rounding, at once: 64 registers instead of 128 under the skip's 64 and the prologue's addresses
   half4 hacc[4][kNT][4];
@@ -640,10 +729,10 @@ __device__ __forceinline__ void finish_item(Ctx& c, int lane, Rows& rw, const fl
       }
   c.lane = fresh(lane);   // behind the conversions: no address of what follows is made while all 192 registers are in use
   __builtin_amdgcn_sched_barrier(0);
-  load_skip<kHasRes, kNT>(c, s, res, tile, kbase);
+  load_skip<kHasRes, kNT>(c, s, res, it);
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (kNext != 0) {
-    decode_rows<kNext>(c, rw, ntile, nkbase);
+    decode_rows<kNext>(c, rw, nit);
     __builtin_amdgcn_sched_barrier(0);
   }
   // The compiler's wait for the bias and skip registers is made to stand here, in front of the prologue: once LDS-DMA loads are
@@ -652,15 +741,15 @@ __device__ __forceinline__ void finish_item(Ctx& c, int lane, Rows& rw, const fl
   asm volatile("" ::"v"(s.bv));
   if constexpr (kHasRes) {
 #pragma unroll
-    for (int it = 0; it < 8 * kNT; ++it) asm volatile("" ::"v"(s.rv[it]));
+    for (int i = 0; i < 8 * kNT; ++i) asm volatile("" ::"v"(s.rv[i]));
   }
   if constexpr (kNext != 0) {
-    issue_prologue<kNext>(c, rw, c.Cin >> 6);
+    issue_prologue<kNext>(c, rw, c.Cin >> 6, nit.mask);
     __builtin_amdgcn_sched_barrier(0);
   }
-  const bool all = __builtin_amdgcn_readfirstlane((tile + 1) * kTileM <= c.M);
-  if (all) epilogue<kHasRes, kNT, true>(c, hacc, s, y, tile, kbase);
-  else epilogue<kHasRes, kNT, false>(c, hacc, s, y, tile, kbase);
+  const bool all = __builtin_amdgcn_readfirstlane(it.limit >= kTileM);
+  if (all) epilogue<kHasRes, kNT, true>(c, hacc, s, y, it);
+  else epilogue<kHasRes, kNT, false>(c, hacc, s, y, it);
   if constexpr (kNext != 0) {
     constexpr int kFly = 2 * (2 + kNext);
     if (all) wait_staged<kFly + 8 * kNT, false>();
@@ -681,12 +770,12 @@ __device__ __forceinline__ void finish_item(Ctx& c, int lane, Rows& rw, const fl
 // Returns whether every lane issued all its 16 stores (the next item's first K tile counts them).
 template <bool kHasRes>
 __device__ __forceinline__ bool finish_chained(Ctx& c, int lane, const floatx16 (&acc)[4][2], const _Float16* __restrict__ bias,
-                                               const _Float16* __restrict__ res, _Float16* __restrict__ y, int tile, int kbase) {
+                                               const _Float16* __restrict__ res, _Float16* __restrict__ y, const Item& it) {
   Skip<kHasRes, 2> s;
   c.lane = fresh(lane);
-  load_skip<kHasRes, 2>(c, s, res, tile, kbase);
+  load_skip<kHasRes, 2>(c, s, res, it);
   __builtin_amdgcn_sched_barrier(0);
-  load_bias<kHasRes, 2>(c, s, bias, tile, kbase);
+  load_bias<kHasRes, 2>(c, s, bias, it);
   __builtin_amdgcn_sched_barrier(0);
   half4 hacc[4][2][4];
 #pragma unroll
@@ -704,36 +793,38 @@ __device__ __forceinline__ bool finish_chained(Ctx& c, int lane, const floatx16 
   asm volatile("" ::"v"(s.bv));
   if constexpr (kHasRes) {
 #pragma unroll
-    for (int it = 0; it < 16; ++it) asm volatile("" ::"v"(s.rv[it]));
+    for (int i = 0; i < 16; ++i) asm volatile("" ::"v"(s.rv[i]));
   }
-  const bool all = __builtin_amdgcn_readfirstlane((tile + 1) * kTileM <= c.M);
-  if (all) epilogue<kHasRes, 2, true>(c, hacc, s, y, tile, kbase);
-  else epilogue<kHasRes, 2, false>(c, hacc, s, y, tile, kbase);
+  const bool all = __builtin_amdgcn_readfirstlane(it.limit >= kTileM);
+  if (all) epilogue<kHasRes, 2, true>(c, hacc, s, y, it);
+  else epilogue<kHasRes, 2, false>(c, hacc, s, y, it);
   raw_barrier();
   return all;
 }
 
-// One workgroup runs the work ids g, g + G, g + 2 G, ... of the launch (G = gridDim.x), in ascending order.  The host entry makes
-// G = min(round width, ids), so where the last round is split the full ids are a multiple of G: a workgroup's first item is a
-// full one and a half item, if it has one, is its last (at most one: there are at most G half ids).
+// One workgroup runs its work ids of the launch one after the other (G = gridDim.x): g, g + G, g + 2 G, ... in ascending order and,
+// in board order, the last round from workgroup G - 1 downwards (next_id).  The host entry makes G = min(round width, ids), so
+// where the last round is split the full ids are a multiple of G: a workgroup's first item is a full one and a half item, if it
+// has one, is its last (at most one: there are at most G half ids; board order has none).
 template <bool kHasRes>
 __global__ __launch_bounds__(kThreads, 2) void k_conv3x3_f16(const char* __restrict__ x, const char* __restrict__ w,
                                                              const _Float16* __restrict__ bias, const _Float16* __restrict__ res,
                                                              _Float16* __restrict__ y, int M, int H, int W, int Cin, int K, int relu,
-                                                             int tiles, int nfull, int ids, Recip dhw, Recip dw) {
+                                                             Deal d, Recip dhw, Recip dw) {
   __shared__ __attribute__((aligned(128))) char lds[kLdsBytes];   // ALL of the kernel's LDS: one array
   const int tid = threadIdx.x;
   Ctx c;
   c.lds = lds; c.x = x; c.w = w; c.M = M; c.H = H; c.W = W; c.Cin = Cin; c.K = K; c.relu = relu; c.dhw = dhw; c.dw = dw;
+  c.stride = d.stride;
   c.lane = tid & 63;
   c.wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   c.zsrc = g_zero_line + (c.lane & 7) * 16;
-  const int G = (int)gridDim.x;
-  int id = (int)blockIdx.x;
-  WorkItem wi = work_item(id, tiles, nfull);   // a full item: see above
+  const int G = (int)gridDim.x, g = (int)blockIdx.x, kchunks = Cin >> 6;
+  int id = g;
+  Item it = item_of(d, id, M, H, W);   // a full item: see above
   Rows rw;
-  decode_rows<2>(c, rw, wi.tile, wi.col * kTileN);
-  issue_prologue<2>(c, rw, Cin >> 6);
+  decode_rows<2>(c, rw, it);
+  issue_prologue<2>(c, rw, kchunks, it.mask);
   wait_staged<8, false>();   // Xa, Wa, Wb of K tile 0; behind them Xb(0), Xa(1), Wa(1), Wb(1)
   raw_barrier();
   // What follows an item is known before its main loop, and is the same for every wave.  While it is a full item the staging
@@ -742,37 +833,34 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv3x3_f16(const char* __restr
   // the compiler's counts for the bias and skip registers are those of one path (joined, it would take the path without a
   // prologue and wait for the other paths' prologues).
   const int lane = c.lane;
-  const int ktiles = 9 * (Cin >> 6);
   int par = 0, nid;
   bool stores = false;
-  WorkItem nwi = wi;
+  Item nit = it;
   for (;;) {
-    nid = id + G;
-    if (nid >= ids) break;
-    nwi = work_item(nid, tiles, nfull);
-    if (__builtin_amdgcn_readfirstlane(nwi.half) >= 0) break;
+    nid = next_id(d, id, g, G);
+    if (nid >= d.ids) break;
+    nit = item_of(d, nid, M, H, W);
+    if (__builtin_amdgcn_readfirstlane(nit.half) >= 0) break;
     floatx16 acc[4][2];
     c.lane = fresh(lane);
-    main_loop<2, true>(c, rw, acc, par, stores, nwi.tile, nwi.col * kTileN);
-    stores = finish_chained<kHasRes>(c, lane, acc, bias, res, y, wi.tile, wi.col * kTileN);
-    par = (par + ktiles) & 1;
+    main_loop<2, true>(c, rw, acc, par, stores, it.mask, nit);
+    stores = finish_chained<kHasRes>(c, lane, acc, bias, res, y, it);
+    par = (par + __builtin_popcount((unsigned)it.mask) * kchunks) & 1;   // the item's own K tiles
     id = nid;
-    wi = nwi;
+    it = nit;
   }
   floatx16 acc[4][2];
   c.lane = fresh(lane);
-  main_loop<2, false>(c, rw, acc, par, stores, 0, 0);
-  if (nid >= ids) {
-    finish_item<kHasRes, 2, 0>(c, lane, rw, acc, bias, res, y, wi.tile, wi.col * kTileN, 0, 0);
+  main_loop<2, false>(c, rw, acc, par, stores, it.mask, it);
+  if (nid >= d.ids) {
+    finish_item<kHasRes, 2, 0>(c, lane, rw, acc, bias, res, y, it, it);
     return;
   }
-  const int hk = nwi.col * kTileN + __builtin_amdgcn_readfirstlane(nwi.half) * (kTileN / 2);
-  finish_item<kHasRes, 2, 1>(c, lane, rw, acc, bias, res, y, wi.tile, wi.col * kTileN, nwi.tile, hk);
-  wi = nwi;
+  finish_item<kHasRes, 2, 1>(c, lane, rw, acc, bias, res, y, it, nit);
   floatx16 acch[4][1];
   c.lane = fresh(lane);
-  main_loop<1, false>(c, rw, acch, 0, false, 0, 0);
-  finish_item<kHasRes, 1, 0>(c, lane, rw, acch, bias, res, y, wi.tile, hk, 0, 0);
+  main_loop<1, false>(c, rw, acch, 0, false, nit.mask, nit);
+  finish_item<kHasRes, 1, 0>(c, lane, rw, acch, bias, res, y, nit, nit);
 }
 
 // the CU count of the current device, asked for once per device
@@ -788,36 +876,159 @@ int round_width_of_device() {
   return n;
 }
 
+// ---- host: the two plans
+// the linear order's deal for `width` items at a time (0: one id per workgroup)
+Deal linear_deal(int64_t m, int k, int width, int* G) {
+  Deal d{};
+  d.tiles = (int)((m + kTileM - 1) / kTileM);
+  const int64_t total = (int64_t)d.tiles * (k / kTileN);       // below 2^31: m * k is below 2^30
+  d.nfull = width > 0 ? full_items(total, width) : (int)total;
+  d.ids = (int)(2 * total - d.nfull);
+  d.fullids = 1 << 30;
+  d.stride = 1;
+  *G = width > 0 && width < d.ids ? width : d.ids;
+  return d;
+}
+// Does board order take the shape?  Not an item of one K tile (a 1 x 1 board at 64 input channels: the loop's first K tile is at
+// the latest its last but one), and its ids stay below 2^30.
+bool board_takes(int64_t rows, int h, int wd, int c, int k) {
+  const int64_t nblk = (rows + kTileM - 1) / kTileM;
+  return rows > 0 && !((int64_t)h * wd == 1 && c < 128) && nblk * h * wd * (k / kTileN) < ((int64_t)1 << 30);
+}
+Deal board_deal(int64_t rows, int h, int wd, int k, int width, int* G) {
+  Deal d{};
+  d.board = 1;
+  d.nblk = (int)((rows + kTileM - 1) / kTileM);
+  d.per_rank = d.nblk * (k / kTileN);
+  d.boards = (int)rows;
+  d.stride = h * wd;
+  d.ids = d.per_rank * d.stride;
+  *G = width > 0 && width < d.ids ? width : d.ids;
+  d.fullids = d.ids / *G * *G;
+  d.nfull = d.ids;
+  d.dpr = recip_of((uint32_t)d.per_rank);
+  d.dblk = recip_of((uint32_t)d.nblk);
+  d.din = recip_of((uint32_t)(wd > 2 ? wd - 2 : 1));
+  d.dw = recip_of((uint32_t)wd);
+  return d;
+}
+// the K tiles of workgroup g of G, in chunks-per-tap units of `kchunks`: board order
+int64_t board_load(const Deal& d, int g, int G, int h, int wd, int kchunks) {
+  int64_t sum = 0;
+  for (int id = g; id < d.ids; id = next_id(d, id, g, G))
+    sum += (int64_t)__builtin_popcount((unsigned)item_of(d, id, 0, h, wd).mask) * kchunks;
+  return sum;
+}
+// The order the plain entry takes for a shape at `width` items a round: board order iff there are at least 256 rows and its most
+// loaded workgroup has strictly fewer K tiles than the linear order's, which is its full rounds x 9 kchunks plus a last round of
+// 9 kchunks, or of 3/4 of that where it is split (a half tile takes 0.75 of a tile's time: profiles/conv_tail_probe.json).
+// Compared in quarters of a K tile.  Host arithmetic, the same on every call of a shape; the last answer is kept per thread.
+int order_of(int64_t rows, int h, int wd, int c, int k, int width) {
+  if (rows < kTileM || width <= 0 || !board_takes(rows, h, wd, c, k)) return 0;
+  struct Key { int64_t rows; int h, wd, c, k, width, order; };
+  static thread_local Key last{-1, 0, 0, 0, 0, 0, 0};
+  if (last.rows == rows && last.h == h && last.wd == wd && last.c == c && last.k == k && last.width == width) return last.order;
+  const int kchunks = c >> 6;
+  int G = 0;
+  const Deal l = linear_deal(rows * h * wd, k, width, &G);
+  const int64_t total = (int64_t)l.tiles * (k / kTileN), r = total % width;
+  const int64_t lin4 = (total / width * 4 + (r == 0 ? 0 : l.nfull < total ? 3 : 4)) * 9 * kchunks;
+  const Deal b = board_deal(rows, h, wd, k, width, &G);
+  int64_t most = 0;
+  for (int g = 0; g < G && 4 * most < lin4; ++g) {
+    const int64_t v = board_load(b, g, G, h, wd, kchunks);
+    if (v > most) most = v;
+  }
+  last = Key{rows, h, wd, c, k, width, 4 * most < lin4 ? 1 : 0};
+  return last.order;
+}
+
 }  // namespace
 
-// The entry point behind elfnet_conv3x3_f16_width(algo = 1); net_conv.hip has checked pointers, alignment and the size limits (every
-// tensor below 2^31 bytes) and set the device.  One launch on `stream`: no allocation, no memset, no synchronisation, no copy.
-// Shapes the kernel does not take are refused with nothing launched.
-// round_width is how many work items run at a time, 0 for the device's CU count (one workgroup per CU).  With total = tiles x
-// columns and r = total % width, the last round is split iff total >= width and 0 < 2 r <= width: total + r work ids, the last r
-// items as two half tiles each (work_item); otherwise total ids.  The launch is a 1-D grid of min(width, ids) workgroups, each
-// running every width-th id (a width above the ids, or an unknown CU count: one id per workgroup).
+// The entry point behind elfnet_conv3x3_f16_width(algo = 1) and elfnet_conv3x3_f16_boards; net_conv.hip has checked pointers,
+// alignment and the size limits (every tensor below 2^31 bytes) and set the device.  One launch on `stream`: no allocation, no
+// memset, no synchronisation, no copy.  Shapes the kernel does not take are refused with nothing launched.
+// round_width is how many work items run at a time, 0 for the device's CU count (one workgroup per CU).
+// order: 0 the linear order, 1 board order, -1 whichever order_of names for the shape (the comment at Deal has both).
+// Linear: with total = tiles x columns and r = total % width, the last round is split iff total >= width and 0 < 2 r <= width:
+// total + r work ids, the last r items as two half tiles each (work_item); otherwise total ids.  The launch is a 1-D grid of
+// min(width, ids) workgroups, each running every width-th id (a width above the ids, or an unknown CU count: one id per workgroup).
+// Board: B x H W x columns ids, no half tiles, the same grid.
 extern "C" __attribute__((visibility("hidden"))) int elfnet_conv3x3_native_f16(const void* x, const void* w, const void* bias,
                                                                                const void* res, void* y, int64_t rows, int h, int wd,
-                                                                               int c, int k, int relu, int round_width,
+                                                                               int c, int k, int relu, int round_width, int order,
                                                                                hipStream_t stream) {
-  if ((c & 63) != 0 || (k & 255) != 0 || round_width < 0) return ELFGO_E_BADARG;
+  if ((c & 63) != 0 || (k & 255) != 0 || round_width < 0 || order < -1 || order > 1) return ELFGO_E_BADARG;
+  if (order == 1 && !board_takes(rows, h, wd, c, k)) return ELFGO_E_BADARG;
   const int64_t m = rows * h * wd;
-  const int tiles = (int)((m + kTileM - 1) / kTileM), cols = k / kTileN;
-  const int64_t total = (int64_t)tiles * cols;       // below 2^31: m * k is below 2^30
   const int width = round_width > 0 ? round_width : round_width_of_device();
-  const int nfull = width > 0 ? full_items(total, width) : (int)total;
-  const int64_t ids = 2 * total - nfull;
-  const dim3 grid((unsigned)(width > 0 && width < ids ? width : ids));
+  if (order < 0) order = order_of(rows, h, wd, c, k, width);
+  int G = 0;
+  const Deal d = order ? board_deal(rows, h, wd, k, width, &G) : linear_deal(m, k, width, &G);
+  const dim3 grid((unsigned)G);
   const Recip dhw = recip_of((uint32_t)(h * wd)), dw = recip_of((uint32_t)wd);   // h * wd <= m, below 2^31
   if (res)
     hipLaunchKernelGGL(k_conv3x3_f16<true>, grid, dim3(kThreads), 0, stream, (const char*)x, (const char*)w, (const _Float16*)bias,
-                       (const _Float16*)res, (_Float16*)y, (int)m, h, wd, c, k, relu, tiles, nfull, (int)ids, dhw, dw);
+                       (const _Float16*)res, (_Float16*)y, (int)m, h, wd, c, k, relu, d, dhw, dw);
   else
     hipLaunchKernelGGL(k_conv3x3_f16<false>, grid, dim3(kThreads), 0, stream, (const char*)x, (const char*)w, (const _Float16*)bias,
-                       (const _Float16*)nullptr, (_Float16*)y, (int)m, h, wd, c, k, relu, tiles, nfull, (int)ids, dhw, dw);
+                       (const _Float16*)nullptr, (_Float16*)y, (int)m, h, wd, c, k, relu, d, dhw, dw);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
+}
+
+// Host arithmetic only: the board-order launch of elfnet_conv3x3_f16_boards for a shape and round_width > 0.  Returns its work
+// ids; with id >= 0 also what that id computes: its block of 256 boards, its board position h * W + w, its channel column and its
+// 9-bit tap mask (bit 3 ky + kx: the tap is on the board).
+extern "C" int64_t elfnet_conv3x3_f16_boards_plan(int64_t rows, int h, int wd, int k, int round_width, int64_t id, int* block,
+                                                  int* position, int* column, int* mask) {
+  if (rows <= 0 || h <= 0 || wd <= 0 || k <= 0 || (k & 255) != 0 || round_width <= 0 || !board_takes(rows, h, wd, 128, k))
+    return ELFGO_E_BADARG;
+  int G = 0;
+  const Deal d = board_deal(rows, h, wd, k, round_width, &G);
+  if (id >= 0) {
+    if (id >= d.ids) return ELFGO_E_BADARG;
+    int b = 0, hw = 0;
+    const Item it = item_of(d, (int)id, 0, h, wd, &b, &hw);
+    if (block) *block = b;
+    if (position) *position = hw;
+    if (column) *column = it.kbase / kTileN;
+    if (mask) *mask = it.mask;
+  }
+  return d.ids;
+}
+
+// Host arithmetic only: the deal of that launch.  g < 0: the number of workgroups G.  Otherwise the work id that workgroup g runs
+// as its j-th item (j from 0), or -1 where it has fewer.
+extern "C" int64_t elfnet_conv3x3_f16_boards_deal(int64_t rows, int h, int wd, int k, int round_width, int g, int j) {
+  const int64_t ids = elfnet_conv3x3_f16_boards_plan(rows, h, wd, k, round_width, -1, nullptr, nullptr, nullptr, nullptr);
+  if (ids < 0) return ids;
+  int G = 0;
+  const Deal d = board_deal(rows, h, wd, k, round_width, &G);
+  if (g < 0) return G;
+  if (g >= G || j < 0) return ELFGO_E_BADARG;
+  int id = g;
+  for (; j > 0 && id < d.ids; --j) id = next_id(d, id, g, G);
+  return id < d.ids ? id : -1;
+}
+
+// Host arithmetic only: the K tiles (one tap x 64 input channels of one item) workgroup g of that launch runs through, at c input
+// channels: the sum of popcount(mask) * c / 64 over its items.
+extern "C" int64_t elfnet_conv3x3_f16_boards_load(int64_t rows, int h, int wd, int c, int k, int round_width, int g) {
+  const int64_t G = elfnet_conv3x3_f16_boards_deal(rows, h, wd, k, round_width, -1, 0);
+  if (G < 0) return G;
+  if (c <= 0 || (c & 63) != 0 || g < 0 || g >= G || !board_takes(rows, h, wd, c, k)) return ELFGO_E_BADARG;
+  int G2 = 0;
+  const Deal d = board_deal(rows, h, wd, k, round_width, &G2);
+  return board_load(d, g, G2, h, wd, c >> 6);
+}
+
+// The order elfnet_conv3x3_f16(algo 1) takes for a shape: 0 linear, 1 board (order_of).  round_width 0: at the current device's
+// CU count, as the plain entry (an unknown count: linear); above 0: host arithmetic only, at that width.
+extern "C" int elfnet_conv3x3_f16_order(int64_t rows, int h, int wd, int c, int k, int round_width) {
+  if (rows < 0 || h <= 0 || wd <= 0 || c <= 0 || k <= 0 || (c & 63) != 0 || (k & 255) != 0 || round_width < 0) return ELFGO_E_BADARG;
+  if (rows * h * wd * (int64_t)(c > k ? c : k) >= ((int64_t)1 << 30)) return ELFGO_E_BADARG;
+  return order_of(rows, h, wd, c, k, round_width > 0 ? round_width : round_width_of_device());
 }
 
 // Host arithmetic only: how elfnet_conv3x3_f16_width lays a launch of tiles x columns work items out for round_width > 0.

@@ -715,6 +715,14 @@ int elfnet_bias_act_bf16(void* x, const void* bias, const void* res, int64_t row
  *   MIOpen's tuned database picks for the 2048 x 19 x 19 x 256 trunk shape, 1 = the hand-written 256 x 256 x 64 LDS-DMA kernel, which
  *   takes c % 64 == 0 and k % 256 == 0 only, keeps algo 0's accumulation order (the same output bits) and is the faster one from
  *   about 33 000 positions (rows * H * W) on.
+ *   Algo 1 has two row orders with the same output bits for finite operands.  Linear: a work item is 256 consecutive positions
+ *   (n, h, w) and runs all nine taps, an off-board tap as a multiplication by zeros.  Board: a work item is one board position
+ *   (h, w) of 256 consecutive boards and runs only the taps that are on the board there (4 in a corner, 6 on an edge, 9 inside);
+ *   its items are dealt longest first, the last round to the least loaded workgroups.  This entry takes board order iff
+ *   rows >= 256 and board order's most loaded workgroup has strictly fewer K tiles (one tap x 64 input channels of one item) than
+ *   the linear order's at the device's CU count (elfnet_conv3x3_f16_order says which); otherwise linear.
+ *   The one difference: in linear order a non-finite weight at a tap that is off the board for a position still reaches that
+ *   position (0 x Inf = NaN, as in algo 0); in board order it does not, that tap is never multiplied.
  * Rounding: the fp32 accumulator is rounded to fp16 (as a convolution that stores y does), then bias, res and the ReLU are applied
  * in fp32 in elfnet_bias_act_f16's order and the result is rounded once more: conv + elfnet_bias_act_f16, without the round trip.
  * Both roundings saturate to Inf (an accumulator beyond 65 504 is Inf before the bias is added), and the ReLU is that pass's fmaxf:
@@ -734,6 +742,29 @@ int elfnet_conv3x3_f16(const void* x, const void* w, const void* bias, const voi
  * probes of the split and of the chains at sizes of a few tiles. */
 int elfnet_conv3x3_f16_width(const void* x, const void* w, const void* bias, const void* res, void* y,
                              int64_t rows, int h, int wd, int c, int k, int relu, int algo, int round_width, void* stream);
+/* Algo 1 in board order, at any rows and round width (elfnet_conv3x3_f16 chooses; a round_width above 0 through
+ * elfnet_conv3x3_f16_width is always the linear order).  With B = ceil(rows / 256) the launch has H W * B * (k / 256) work ids and
+ * min(round_width, ids) workgroups; round_width 0 = the device's CU count.  Refuses what algo 1 refuses, and a 1 x 1 board at
+ * c == 64 (an item of a single K tile).  For tests and probes. */
+int elfnet_conv3x3_f16_boards(const void* x, const void* w, const void* bias, const void* res, void* y,
+                              int64_t rows, int h, int wd, int c, int k, int relu, int round_width, void* stream);
+/* Host arithmetic: the work ids of that launch for round_width > 0, or ELFGO_E_BADARG.  With 0 <= id it also says what work id
+ * `id` computes (any of the pointers may be NULL): its block of 256 boards, its board position h * W + w, its channel column and
+ * its tap mask, bit 3 ky + kx set iff (h + ky - 1, w + kx - 1) is on the board.  id = (rank * columns + column) * B + block, where
+ * rank lists the inner positions, then the edges, then the corners, each row-major (H or W below 3: rank = position). */
+int64_t elfnet_conv3x3_f16_boards_plan(int64_t rows, int h, int wd, int k, int round_width, int64_t id,
+                                       int* block, int* position, int* column, int* mask);
+/* Host arithmetic: the deal of that launch.  g < 0: its workgroups G.  Otherwise the work id workgroup g runs as its j-th item
+ * (j from 0), or -1 where it has fewer: g + j G in the full rounds, and the last, partial round is dealt from workgroup G - 1
+ * downwards. */
+int64_t elfnet_conv3x3_f16_boards_deal(int64_t rows, int h, int wd, int k, int round_width, int g, int j);
+/* Host arithmetic: the K tiles workgroup g of that launch runs through at c input channels: popcount(mask) * c / 64, summed
+ * over its items. */
+int64_t elfnet_conv3x3_f16_boards_load(int64_t rows, int h, int wd, int c, int k, int round_width, int g);
+/* The row order elfnet_conv3x3_f16(algo 1) takes for a shape: 0 linear, 1 board (the rule above; the linear order's most loaded
+ * workgroup is its full rounds x 9 c / 64 K tiles plus 9 c / 64 for an unsplit last round or 3/4 of that for a split one).
+ * round_width 0: at the current device's CU count; above 0: host arithmetic at that width. */
+int elfnet_conv3x3_f16_order(int64_t rows, int h, int wd, int c, int k, int round_width);
 /* Host arithmetic: the work ids of the launch elfnet_conv3x3_f16_width(algo 1) makes for tiles x columns work items and
  * round_width > 0.  Returns the number of work ids (tiles * columns when the last round is not split, one more per split item),
  * or ELFGO_E_BADARG.  With any of tile / column / half non-NULL it also says what work id `id` computes: its tile, its column,

@@ -16,7 +16,10 @@ each running every W-th id one after the other with the next item's prologue iss
 the number of tiles) never splits and gives every work id a workgroup of its own, which is the A/B of the split and of the chains
 inside one build.  The rule needs one whole round in front of the split one, so at most a third of the
 tiles can be split: W = 2 * tiles / 3 gives one round of W full tiles and one of W half tiles.  FusedInferenceNet routes to algo 1 only where its mean is below algo 0's by more than the spread
-(max - min over the repeats) of either."""
+(max - min over the repeats) of either.
+--order linear|board pins algo 1's row order, which elfnet_conv3x3_f16 otherwise chooses by shape (elfnet_conv3x3_f16_order):
+linear is elfnet_conv3x3_f16_width at the device's CU count named as the round width (or at --round-width), board is
+elfnet_conv3x3_f16_boards; the same build, the same process: the A/B of the two orders."""
 import argparse
 import ctypes as C
 import json
@@ -39,6 +42,7 @@ def main():
     ap.add_argument("--algos", default="0,1", help="comma-separated: 0, 1 (elfnet_conv3x3_f16's algos) and small (elfnet_conv3x3_small_f16)")
     ap.add_argument("--round-width", type=int, default=None,
                     help="algo 1's round width (elfnet_conv3x3_f16_width): 0 = the CU count, -1 = never split the last round")
+    ap.add_argument("--order", choices=["linear", "board"], default=None, help="algo 1's row order; default: the library's own choice")
     ap.add_argument("--no-pair", action="store_true", help="leave F.conv2d + elfnet_bias_act_f16 out: only the fused variants run")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "conv_fused_probe.json"))
     a = ap.parse_args()
@@ -65,10 +69,15 @@ def main():
     p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
 
     width = None if a.round_width is None else (1 << 30) if a.round_width < 0 else a.round_width
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
 
     def fused(algo, res):
         if algo == "small":
             return lambda: L.elfnet_conv3x3_small_f16(p(x), p(w), p(b), p(res), p(y), rows, n, n, ch, ch, 1, st)
+        if algo == 1 and a.order == "board":
+            return lambda: L.elfnet_conv3x3_f16_boards(p(x), p(w), p(b), p(res), p(y), rows, n, n, ch, ch, 1, width or 0, st)
+        if algo == 1 and a.order == "linear":
+            return lambda: L.elfnet_conv3x3_f16_width(p(x), p(w), p(b), p(res), p(y), rows, n, n, ch, ch, 1, 1, width or cus, st)
         if width is not None:
             return lambda: L.elfnet_conv3x3_f16_width(p(x), p(w), p(b), p(res), p(y), rows, n, n, ch, ch, 1, algo, width, st)
         return lambda: L.elfnet_conv3x3_f16(p(x), p(w), p(b), p(res), p(y), rows, n, n, ch, ch, 1, algo, st)
@@ -98,7 +107,8 @@ def main():
         return dict(status=0, us=[round(u, 2) for u in us], mean_us=round(sum(us) / len(us), 2), min_us=round(min(us), 2),
                     max_us=round(max(us), 2))
 
-    res = dict(shape=dict(rows=rows, board_size=n, channels=ch), round_width=a.round_width, launches=a.launches, warmup=a.warmup, repeats=a.repeats,
+    res = dict(shape=dict(rows=rows, board_size=n, channels=ch), round_width=a.round_width, order=a.order,
+               order_chosen=int(L.elfnet_conv3x3_f16_order(rows, n, n, ch, ch, 0)), launches=a.launches, warmup=a.warmup, repeats=a.repeats,
                device=torch.cuda.get_device_name(0), method="HIP events around back-to-back launches, µs per convolution")
     with torch.no_grad():
         for skip, rr in (("noskip", None), ("skip", r)):
