@@ -1,13 +1,11 @@
 """GPU: elfgo_area_map and elfgo_own_run (k_area_map, k_playout_own) against the CPU oracle's playouts, and the GTP commands
 built on them.  Every comparison is integer equality."""
-import os
-
 import numpy as np
 import pytest
 
 import ownership_expected as oe
-from conftest import GOLDEN
-from pyoracle import Port, Ref, playout_seeds
+from ownership_expected import mixed_rows, oracle, play_all, states_of
+from pyoracle import playout_seeds
 
 pytestmark = pytest.mark.gpu
 
@@ -16,36 +14,6 @@ pytestmark = pytest.mark.gpu
 def elf(built):
     import elf_amd
     return elf_amd
-
-
-def oracle(n):
-    return Ref(n) if Ref.available(n) else Port(n)
-
-
-def play_all(eng, move_lists):
-    """slot i <- move_lists[i] from the empty board, one ply of every slot per launch"""
-    for t in range(max(len(m) for m in move_lists)):
-        live = [i for i, m in enumerate(move_lists) if t < len(m)]
-        ok = eng.forward(live, [int(move_lists[i][t]) for i in live]).cpu().numpy()
-        assert (ok == 1).all()
-
-
-def states_of(E, move_lists):
-    out = []
-    for mv in move_lists:
-        s = E.new()
-        for c in mv:
-            assert E.forward(s, int(c)) == 1
-        out.append(s)
-    return out
-
-
-def mixed_rows(E, n):
-    """empty board, mid game, late game, a live simple ko, a finished game"""
-    sd = playout_seeds(3, base=31)
-    early, late = (20, 60) if n == 9 else (60, 300)
-    lists = [[], oe.prefix(E, sd[0], early)[1], oe.prefix(E, sd[1], late)[1], oe.ko_moves(n), oe.prefix(E, sd[2], 100000)[1]]
-    return lists
 
 
 def check_area(eng, E, states, ids=None):
@@ -61,12 +29,7 @@ def check_area(eng, E, states, ids=None):
 @pytest.mark.parametrize("n,plies", [(9, (20, 40)), (19, (60, 200))])
 def test_area_map(elf, n, plies):
     E = oracle(n)
-    seeds = playout_seeds(4)
-    lists = [[]] + [oe.prefix(E, sd, pl)[1] for sd in seeds for pl in plies]
-    if n == 19:      # every 10th ply of one ladder-suite game
-        g = np.load(os.path.join(GOLDEN, "ladder_suite.npz"))
-        game = [int(c) for c in g["moves"][g["offsets"][0]:g["offsets"][1]]]
-        lists += [game[:t] for t in range(10, len(game) + 1, 10)]
+    lists = oe.area_test_lists(E, n, plies)
     eng = elf.GoEngine(n, len(lists), 0)
     play_all(eng, lists)
     states = states_of(E, lists)
