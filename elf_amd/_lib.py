@@ -162,6 +162,8 @@ SIGNATURES = {
     "elfnet_conv3x3_f16_boards_load": (_i64, [_i64, _i, _i, _i, _i, _i, _i]),
     "elfnet_conv3x3_f16_order": (_i, [_i64, _i, _i, _i, _i, _i]),
     "elfnet_conv3x3_f16_recip": (_i, [_i64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "elfnet_conv3x3_f16_bufstage": (_i, [_i64, _i, _i, _i, _i, _i, _i] + [C.POINTER(C.c_uint32)] * 6),
+    "elfnet_conv3x3_f16_bufstage_probe": (_i, [_vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
     "elfnet_conv3x3_small_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "elfnet_conv3x3_in_f16": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "elfnet_heads_workspace": (_sz, [_i64, _i, _i]),

@@ -6,7 +6,8 @@
 //   tile      256 positions x 256 output channels x BK 64 (one tap, 64 consecutive input channels); all of N in one tile, so an
 //             activation byte is staged once for every output channel.  512 threads, 8 waves as 2 (positions) x 4 (channels), each
 //             owning 128 positions x 64 channels = 4 x 2 MFMA tiles = 128 accumulator registers.  One workgroup per CU.
-//   staging   LDS-DMA (global_load_lds_dwordx4) straight into two 64-KiB LDS buffers (activation tile, weight tile: 256 rows of
+//   staging   LDS-DMA (buffer_load_dwordx4 ... offen lds through one raw buffer descriptor per operand: the row's offset in a vector
+//             register, the K tile's in a scalar; the comment at kSentinel) straight into two 64-KiB LDS buffers (activation tile, weight tile: 256 rows of
 //             128 B each), in half-tiles of 128 rows of one operand, two 8-row pieces per wave, issued one at a time between the
 //             MFMAs of the MFMA segments; three or four half-tiles stay in flight across the loop's barriers, which are bare
 //             s_barriers behind counted vmcnt waits (the comment at the main loop has the slots and the counts).  vmcnt(0) only
@@ -14,7 +15,8 @@
 //   halo      a staging lane decodes its four rows once (position -> n, h, w: two divisions by launch constants, each a multiply
 //             by a multiplier the host entry made and a shift) and keeps a 9-bit tap mask (a 3-bit row mask times a 3-bit column
 //             mask) and a byte offset; for an off-board tap, and for a row at or beyond its item's limit (M; in board order the
-//             last board), its source address is a zero-filled line in global memory.  LDS is never zeroed by a second path.
+//             last board), its offset is one the descriptor's range check refuses, and the load writes zeros to LDS without
+//             reading memory.  LDS is never zeroed by a second path.  Board order keeps no mask: its items visit on-board taps only.
 //   LDS image lane-linear, as the DMA writes it; the 16-B slot s of row r holds the row's chunk s ^ ((r >> 1) & 7): the XOR is on
 //             the source address when staging and on the read address of the fragment ds_read_b128s, which are then conflict-free
 //             (rows r and r + 1 share a 256-B bank row, so the swizzle steps every second row; checked against the 16-lane groups
@@ -33,7 +35,7 @@
 //             a half tile's time.  Same kernel, same launch, same K chain per output element: the bits do not change.  The host
 //             entry decides (full_items below).
 //   orders    the 256 rows of a tile are, in linear order, 256 consecutive positions (n, h, w), about 13.5 rows of a 19 x 19
-//             board: every tile has positions on every edge, runs all nine taps and multiplies the zero line wherever a tap is
+//             board: every tile has positions on every edge, runs all nine taps and multiplies staged zeros wherever a tap is
 //             off the board, 6.9 % of all K tiles on 19 x 19.  In board order they are one board position (h, w) of 256 consecutive
 //             boards, H W positions apart: every row has the same taps on the board, the item carries that 9-bit mask in a scalar
 //             and its K loop visits only the set taps, ascending (first_tap, next_tap; popcount x Cin / 64 K tiles: 4 taps in a
@@ -80,15 +82,38 @@ constexpr int kBufBytes = 2 * kOperandBytes;     // activations, then weights
 constexpr int kWaveCBytes = 4096;                // a wave's own piece of the epilogue: 32 positions x 64 channels fp16
 constexpr int kLdsBytes = 2 * kBufBytes + 8 * kWaveCBytes;   // two K tiles and the eight waves' epilogue pieces: 160 KiB, all a CU has
 
-// the line every off-board tap and every row at or beyond its item's limit is staged from
-__device__ __attribute__((aligned(128))) unsigned char g_zero_line[128] = {0};
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
+typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
-// 64 lanes x 16 B: lane l's 16 bytes land at lds_base + 16 * l (the destination is wave-uniform, the source per lane)
-__device__ __forceinline__ void stage16(const char* src, char* lds_base) {
-  __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)lds_base, 16, 0, 0);
+// ---- buffer-addressed staging.  x and w are read through one raw buffer descriptor each (stride 0, offen), made in scalar
+// registers at kernel entry; a staged piece is buffer_load_dwordx4 v, s[rsrc], s offen lds: the lane's 32-bit byte offset (made
+// once per item, decode_rows) in the vector register, everything wave-uniform about the piece (tap, channel chunk) in the scalar
+// offset.  The sum the instruction addresses by is unsigned, and a tap's offset from a row's own position is negative for ky = 0
+// and kx = 0, so x's descriptor starts bias = (W + 1) Cin 2 bytes in front of x and every scalar offset of x carries + bias.
+// Zeros come from the descriptor's range check: a lane whose vector offset is at or above num_records reads nothing and its
+// 16 bytes of LDS are written with zeros.  Such a lane carries kSentinel, whatever the tensor's size: 16-byte aligned, at or above
+// every num_records the entry accepts, and with every scalar offset still below 2^32.  The arithmetic, shared with the host entry
+// elfnet_conv3x3_f16_bufstage and its test:
+//   x  bytes < 2^31 (net_conv.hip), bias and every scalar offset (at most (2 W + 3) Cin 2) below 2^30 (the native entry refuses a
+//      wider board): num_records = bytes + bias < 2^31 + 2^30 = kSentinel; a valid row's offset + scalar offset < 2^31 + 2^30;
+//      kSentinel + scalar offset < 2^32: no sum wraps.  A tap that is on the board addresses bytes of x only: offset + scalar
+//      offset - bias is that neighbour's chunk.
+//   w  bytes < 2^31, the scalar offset stays inside a weight row: below the tensor's size.
+constexpr uint32_t kSentinel = 0xC0000000u;
+constexpr uint32_t kRsrcWord3 = 0x00020000u;   // a raw buffer of dwords on gfx9: DATA_FORMAT 32, no swizzle, no index
+__host__ __device__ inline uint32_t x_bias(int W, int Cin) { return (uint32_t)(W + 1) * (uint32_t)(Cin * 2); }
+// the scalar byte offset of K tile (tap, kc): from a row's own position in x (bias included), and from the start of a weight row
+__host__ __device__ inline uint32_t x_soffset(int W, int Cin, int tap, int kc) {
+  const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
+  return (uint32_t)((dy * W + dx) * Cin * 2 + kc * 128) + x_bias(W, Cin);
+}
+__host__ __device__ inline uint32_t w_soffset(int Cin, int tap, int kc) { return (uint32_t)(tap * Cin * 2 + kc * 128); }
+// does the buffer form take the shape?  (every scalar offset of x below 2^30)
+inline bool bufstage_takes(int wd, int c) { return (2 * (int64_t)wd + 3) * c * 2 < ((int64_t)1 << 30); }
+
+// 64 lanes x 16 B: lane l's 16 bytes land at lds_base + 16 * l (the destination is wave-uniform, the source offset per lane)
+__device__ __forceinline__ void stage16(rsrc_t r, uint32_t voff, uint32_t soff, char* lds_base) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lptr_t)lds_base, 16, (int)voff, (int)soff, 0, 0);
 }
 
 // the counted wait of the main loop: at most kN of this wave's LDS-DMA loads (two per staged half-tile, in issue order) are
@@ -219,16 +244,15 @@ __host__ __device__ inline int next_tap(int mask, int t) { return t + 1 + __buil
 // What a wave knows about itself and the launch: everything the staging and the epilogue address by.
 struct Ctx {
   char* lds;
-  const char* x;
-  const char* w;
+  rsrc_t xr, wr;                 // the raw buffer descriptors of x (starting bias bytes in front of it) and w
+  uint32_t bias;                 // x_bias(W, Cin)
   int M, H, W, Cin, K, relu;
   int stride;                    // positions between two rows of an item: 1 (linear order) or H W (board order)
   Recip dhw, dw;                 // the decode's divisions by H W and by W
   int lane, wv;                  // wv through readfirstlane: what depends on the wave alone stays in scalar registers
-  const unsigned char* zsrc;     // this lane's 16 B of the zero line
 };
-// The rows a staging lane feeds, decoded once per work item: byte offsets of its four activation rows and four weight rows, and
-// the 9-bit tap masks of the activation rows.
+// The rows a staging lane feeds, decoded once per work item: the vector offsets of its four activation rows (kSentinel for a row at
+// or beyond the item's limit) and four weight rows, and, in linear order, the 9-bit tap masks of the activation rows.
 struct Rows { uint32_t xoff[4], woff[4], xmask[4]; };
 
 // ---- staging.  A K tile is staged as four half-tiles of 128 rows, in the order the fragment reads need them:
@@ -239,7 +263,7 @@ struct Rows { uint32_t xoff[4], woff[4], xmask[4]; };
 // (lane & 7) of that row.  Index hf * 2 + i below.
 // The half tile (kNT == 1) has one weight half-tile per K tile, Wh: its 128 weight rows, LDS row = channel - kbase, wave (wm, wn)
 // reads rows wn * 32 + fr; piece i of wave wv is rows i * 64 + wv * 8 .. + 7 (woff[0..1]).
-template <int kNT>
+template <int kNT, bool kBoard>
 __device__ __forceinline__ void decode_rows(const Ctx& c, Rows& rw, const Item& it) {
   const int lane = c.lane, wv = c.wv, kbase = it.kbase;
   const uint32_t hw = (uint32_t)(c.H * c.W), wd = (uint32_t)c.W;
@@ -250,40 +274,51 @@ __device__ __forceinline__ void decode_rows(const Ctx& c, Rows& rw, const Item& 
     const int p = it.base + r * c.stride;   // the one mapping of (item, row) to a position; load_skip and epilogue have it too
     // tap 3 ky + kx is on the board iff row hh + ky - 1 and column ww + kx - 1 are: the rows' three bits stand at 0, 3 and 6, the
     // columns' at 0, 1 and 2, and their product has bit 3 ky + kx set iff both are (no carries: the column mask is below 8)
-    const uint32_t rem = (uint32_t)p - div_by((uint32_t)p, c.dhw) * hw, hh = div_by(rem, c.dw), ww = rem - hh * wd;
-    const uint32_t rowm = (hh > 0 ? 1u : 0u) | 8u | ((int)hh + 1 < c.H ? 64u : 0u);
-    const uint32_t colm = (ww > 0 ? 1u : 0u) | 2u | ((int)ww + 1 < c.W ? 4u : 0u);
-    uint32_t m = __umul24(rowm, colm);
-    asm("" : "+v"(m));   // made for every row and selected, with no branch around the arithmetic for the rows at or beyond the limit
-    rw.xmask[j] = r < it.limit ? m : 0u;
-    rw.xoff[j] = (uint32_t)p * (uint32_t)(c.Cin * 2) + (((lane & 7) ^ ((r >> 1) & 7)) << 4);   // below 2^31 wherever it is used (a valid row)
+    // (board order: every tap the item visits is on the board for all its rows, no mask)
+    if constexpr (!kBoard) {
+      const uint32_t rem = (uint32_t)p - div_by((uint32_t)p, c.dhw) * hw, hh = div_by(rem, c.dw), ww = rem - hh * wd;
+      const uint32_t rowm = (hh > 0 ? 1u : 0u) | 8u | ((int)hh + 1 < c.H ? 64u : 0u);
+      const uint32_t colm = (ww > 0 ? 1u : 0u) | 2u | ((int)ww + 1 < c.W ? 4u : 0u);
+      uint32_t m = __umul24(rowm, colm);
+      asm("" : "+v"(m));   // made for every row and selected, with no branch around the arithmetic for the rows at or beyond the limit
+      rw.xmask[j] = r < it.limit ? m : 0u;
+    } else {
+      rw.xmask[j] = 0u;
+    }
+    uint32_t off = (uint32_t)p * (uint32_t)(c.Cin * 2) + (((lane & 7) ^ ((r >> 1) & 7)) << 4);   // below 2^31 for a valid row
+    asm("" : "+v"(off));   // as the mask: made for every row, then selected
+    rw.xoff[j] = r < it.limit ? off : kSentinel;
     const int rwt = kNT == 2 ? (i * 2 + (wv >> 2)) * 64 + hf * 32 + (wv & 3) * 8 + (lane >> 3) : i * 64 + wv * 8 + (lane >> 3);
     rw.woff[j] = (uint32_t)(kbase + rwt) * (uint32_t)(9 * c.Cin * 2) + (((lane & 7) ^ ((rwt >> 1) & 7)) << 4);
   }
 }
-// the byte offset of K tile (tap, kc) from a row's own position in x, and from the start of a weight row: wave-uniform
+// the scalar offset of K tile (tap, kc) in x (bias included) and in w: wave-uniform
 __device__ __forceinline__ uint32_t x_delta(const Ctx& c, int tap, int kc) {
   const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
-  return (uint32_t)((dy * c.W + dx) * c.Cin * 2 + kc * 128);
+  return (uint32_t)((dy * c.W + dx) * c.Cin * 2 + kc * 128) + c.bias;   // x_soffset(c.W, c.Cin, tap, kc)
 }
-__device__ __forceinline__ uint32_t w_delta(const Ctx& c, int tap, int kc) { return (uint32_t)(tap * c.Cin * 2 + kc * 128); }
-// piece i of one half-tile of the K tile at tap `tap` and offset d (x_delta, w_delta) into buffer buf; the two pieces of a
-// half-tile are issued in the order i = 0, 1
+__device__ __forceinline__ uint32_t w_delta(const Ctx& c, int tap, int kc) { return w_soffset(c.Cin, tap, kc); }
+// piece i of one half-tile of the K tile at tap `tap` and scalar offset d (x_delta, w_delta) into buffer buf; the two pieces of a
+// half-tile are issued in the order i = 0, 1.  Board order: the row's offset as it is.  Linear order: the sentinel where the tap is
+// off the board for the row (one select).
+template <bool kBoard>
 __device__ __forceinline__ void stage_x_piece(const Ctx& c, const Rows& rw, int hf, int i, int tap, uint32_t d, int buf) {
-  stage16(((rw.xmask[hf * 2 + i] >> tap) & 1) ? c.x + (uint32_t)(rw.xoff[hf * 2 + i] + d) : (const char*)c.zsrc,
-          c.lds + buf * kBufBytes + (i * 128 + hf * 64 + c.wv * 8) * 128);
+  uint32_t v = rw.xoff[hf * 2 + i];
+  if constexpr (!kBoard) v = ((rw.xmask[hf * 2 + i] >> tap) & 1) ? v : kSentinel;
+  stage16(c.xr, v, d, c.lds + buf * kBufBytes + (i * 128 + hf * 64 + c.wv * 8) * 128);
 }
 template <int kNT>
 __device__ __forceinline__ void stage_w_piece(const Ctx& c, const Rows& rw, int hf, int i, uint32_t d, int buf) {
-  stage16(c.w + (uint32_t)(rw.woff[hf * 2 + i] + d),
+  stage16(c.wr, rw.woff[hf * 2 + i], d,
           c.lds + buf * kBufBytes + kOperandBytes +
               (kNT == 2 ? (i * 2 + (c.wv >> 2)) * 64 + hf * 32 + (c.wv & 3) * 8 : i * 64 + c.wv * 8) * 128);
 }
 // both pieces of a half-tile, back to back: the prologue's form
+template <bool kBoard>
 __device__ __forceinline__ void stage_x(const Ctx& c, const Rows& rw, int hf, int tap, int kc, int buf) {
   const uint32_t d = x_delta(c, tap, kc);
 #pragma unroll
-  for (int i = 0; i < 2; ++i) stage_x_piece(c, rw, hf, i, tap, d, buf);
+  for (int i = 0; i < 2; ++i) stage_x_piece<kBoard>(c, rw, hf, i, tap, d, buf);
 }
 template <int kNT>
 __device__ __forceinline__ void stage_w(const Ctx& c, const Rows& rw, int hf, int tap, int kc, int buf) {
@@ -302,13 +337,13 @@ __device__ __forceinline__ KPos first_kpos(int kchunks, int mask) {
 }
 // An item's prologue, issue only: Xa Wa Wb Xb of K tile 0 and Xa Wa Wb of K tile 1 (seven half-tiles, 14 loads per wave; the half
 // tile: Xa Wh Xb, Xa Wh, five and 10).  Its wait is wait_staged<kFly> (+ what was issued behind it) and a barrier.
-template <int kNT>
+template <int kNT, bool kBoard>
 __device__ __forceinline__ void issue_prologue(const Ctx& c, const Rows& rw, int kchunks, int mask) {
   const KPos k = first_kpos(fresh_uniform(kchunks), mask);   // K tile 1's tap and chunk are made here, per item, not kept
-  stage_x(c, rw, 0, k.tap0, 0, 0); stage_w<kNT>(c, rw, 0, k.tap0, 0, 0);
+  stage_x<kBoard>(c, rw, 0, k.tap0, 0, 0); stage_w<kNT>(c, rw, 0, k.tap0, 0, 0);
   if constexpr (kNT == 2) stage_w<kNT>(c, rw, 1, k.tap0, 0, 0);
-  stage_x(c, rw, 1, k.tap0, 0, 0);
-  stage_x(c, rw, 0, k.tap1, k.kc1, 1); stage_w<kNT>(c, rw, 0, k.tap1, k.kc1, 1);
+  stage_x<kBoard>(c, rw, 1, k.tap0, 0, 0);
+  stage_x<kBoard>(c, rw, 0, k.tap1, k.kc1, 1); stage_w<kNT>(c, rw, 0, k.tap1, k.kc1, 1);
   if constexpr (kNT == 2) stage_w<kNT>(c, rw, 1, k.tap1, k.kc1, 1);
 }
 
@@ -321,7 +356,7 @@ __device__ __forceinline__ void issue_prologue(const Ctx& c, const Rows& rw, int
 // first seven half-tiles and leaves its rows in rw.  The two kinds of full item are two copies of the loop, and the kernel runs
 // its chained items in a loop of their own: with both ends behind one steady loop this compiler allocates the accumulators twice
 // and spills some 400 registers.
-template <int kNT, bool kChain>
+template <int kNT, bool kChain, bool kBoard>
 __device__ __forceinline__ void main_loop(const Ctx& c, Rows& rw, floatx16 (&acc)[4][kNT], int par, bool stores, int mask,
                                           const Item& nit) {
   static_assert(kNT == 2 || !kChain, "only a full item is chained");
@@ -422,8 +457,8 @@ __device__ __forceinline__ void main_loop(const Ctx& c, Rows& rw, floatx16 (&acc
           for (int p = 0; p < kP; ++p)
             if (at == (kSeg == 0 ? kM1At[p] : kM2At[p])) {
               __builtin_amdgcn_sched_barrier(0);
-              if constexpr (kSeg == 0) stage_x_piece(c, rw, 1, p, tap, dx, cur ^ 1);
-              else if (p < 2) stage_x_piece(c, rw, 0, p, tap, dx, cur);
+              if constexpr (kSeg == 0) stage_x_piece<kBoard>(c, rw, 1, p, tap, dx, cur ^ 1);
+              else if (p < 2) stage_x_piece<kBoard>(c, rw, 0, p, tap, dx, cur);
               else stage_w_piece<kNT>(c, rw, (p - 2) >> 1, p & 1, dw, cur);
               __builtin_amdgcn_sched_barrier(0);
             }
@@ -443,8 +478,8 @@ __device__ __forceinline__ void main_loop(const Ctx& c, Rows& rw, floatx16 (&acc
     constexpr bool kFirst = (decltype(first)::v & 1) != 0, kTurn = (decltype(first)::v & 2) != 0;
     const int cur = tc & 1;
     const char* b = lds + cur * kBufBytes;
-    // the pieces' wave-uniform offsets are made here, in a load segment, so that among the MFMAs a piece is a select, an add and
-    // the load
+    // the pieces' scalar offsets are made here, in a load segment, so that among the MFMAs a piece is the m0 write and the load
+    // (linear order: and the select of the row's offset or the sentinel)
     uint32_t dx1 = 0, dx2 = 0, dw2 = 0;
     if constexpr (kP1 != 0) dx1 = x_delta(c, tap1, kc1);
     if constexpr (kP2 != 0) { dx2 = x_delta(c, tap2, kc2); dw2 = w_delta(c, tap2, kc2); }
@@ -457,6 +492,14 @@ __device__ __forceinline__ void main_loop(const Ctx& c, Rows& rw, floatx16 (&acc
       xf[1][kk] = ldx(b, 1, kk);
       if constexpr (kNT == 2) wb[kk] = ldw(b, 1, kk);
     }
+    // The fragment registers pass through an empty statement in front of the segment's wait.  A buffer load counts on vmcnt alone
+    // (the flat form it replaces counted on lgkmcnt too, out of order, and the compiler answered that with one lgkmcnt(0) per MFMA
+    // segment), so the compiler now counts the ds_reads exactly and would put a counted lgkmcnt wait in front of every MFMA that
+    // takes a new fragment, fourteen more per K tile, each satisfied long before by the wait below.  This way its one wait stands
+    // here, and the registers are the statement's results behind it.
+    asm volatile("" : "+v"(xf[0][0]), "+v"(xf[0][1]), "+v"(xf[0][2]), "+v"(xf[0][3]), "+v"(xf[1][0]), "+v"(xf[1][1]), "+v"(xf[1][2]),
+                      "+v"(xf[1][3]), "+v"(wa[0]), "+v"(wa[1]), "+v"(wa[2]), "+v"(wa[3]));
+    if constexpr (kNT == 2) asm volatile("" : "+v"(wb[0]), "+v"(wb[1]), "+v"(wb[2]), "+v"(wb[3]));
     // K tile 0 behind a carried transition: the 16 stores of the item before are younger than the pieces this wait leaves in
     // flight and older than nothing it waits for, so they are added to the count; a lane may have issued fewer where that item's
     // tile had rows at or beyond M, and then the steady count, which is right for no store at all and stronger otherwise
@@ -473,10 +516,12 @@ __device__ __forceinline__ void main_loop(const Ctx& c, Rows& rw, floatx16 (&acc
     }
     // the next item's rows, decoded here once per item, in the load segment with the longest wait at its barrier; nothing is
     // staged from them before M2 of the item's last but one K tile
-    if constexpr (kFirst && kChain) decode_rows<2>(c, rn, nit);
+    if constexpr (kFirst && kChain) decode_rows<2, kBoard>(c, rn, nit);
     // the turn: M1 of the item's last but one K tile was the last to stage from the item's own rows, and everything from this
     // tile's M2 on is staged from the next item's, which become rw here
     if constexpr (kTurn) rw = rn;
+    asm volatile("" : "+v"(xf[0][0]), "+v"(xf[0][1]), "+v"(xf[0][2]), "+v"(xf[0][3]), "+v"(xf[1][0]), "+v"(xf[1][1]), "+v"(xf[1][2]),
+                      "+v"(xf[1][3]));   // as in L1
     if (kFirst && stores) wait_staged<kW2 + 8 * kNT, true>();
     else wait_staged<kW2, true>();
     raw_barrier();
@@ -708,7 +753,7 @@ __device__ __forceinline__ void epilogue(const Ctx& c, const half4 (&hacc)[4][kN
 //   the first wait needs Xa, Wa, Wb of K tile 0: behind them kFly = 8 loads of the prologue (6 for a half item next) and this
 //   item's 16 stores: vmcnt(24) (22).  Where the tile has rows at or beyond M a lane may issue fewer stores, and a count that is
 //   too high waits for too little: that tile waits with kFly alone, which is right for no store at all and stronger otherwise.
-template <bool kHasRes, int kNT, int kNext>
+template <bool kHasRes, int kNT, int kNext, bool kBoard>
 __device__ __forceinline__ void finish_item(Ctx& c, int lane, Rows& rw, const floatx16 (&acc)[4][kNT], const _Float16* __restrict__ bias,
                                             const _Float16* __restrict__ res, _Float16* __restrict__ y, const Item& it,
                                             const Item& nit) {
@@ -732,19 +777,21 @@ __device__ __forceinline__ void finish_item(Ctx& c, int lane, Rows& rw, const fl
   load_skip<kHasRes, kNT>(c, s, res, it);
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (kNext != 0) {
-    decode_rows<kNext>(c, rw, nit);
+    decode_rows<kNext, kBoard>(c, rw, nit);
     __builtin_amdgcn_sched_barrier(0);
   }
   // The compiler's wait for the bias and skip registers is made to stand here, in front of the prologue: once LDS-DMA loads are
   // pending it counts nothing and waits with vmcnt(0) for any register a plain load returns, which behind the prologue would be
-  // a wait for the prologue.  The conversions and the decode above are what these loads have to return in.
+  // a wait for the prologue.  The conversions and the decode above are what these loads have to return in.  (Nothing is pending
+  // here, the item ended drained, so with buffer loads the compiler counts these registers down one by one, vmcnt(16) .. vmcnt(0)
+  // with the skip: the same last wait, in the same place.)
   asm volatile("" ::"v"(s.bv));
   if constexpr (kHasRes) {
 #pragma unroll
     for (int i = 0; i < 8 * kNT; ++i) asm volatile("" ::"v"(s.rv[i]));
   }
   if constexpr (kNext != 0) {
-    issue_prologue<kNext>(c, rw, c.Cin >> 6, nit.mask);
+    issue_prologue<kNext, kBoard>(c, rw, c.Cin >> 6, nit.mask);
     __builtin_amdgcn_sched_barrier(0);
   }
   const bool all = __builtin_amdgcn_readfirstlane(it.limit >= kTileM);
@@ -806,25 +853,28 @@ __device__ __forceinline__ bool finish_chained(Ctx& c, int lane, const floatx16 
 // in board order, the last round from workgroup G - 1 downwards (next_id).  The host entry makes G = min(round width, ids), so
 // where the last round is split the full ids are a multiple of G: a workgroup's first item is a full one and a half item, if it
 // has one, is its last (at most one: there are at most G half ids; board order has none).
-template <bool kHasRes>
-__global__ __launch_bounds__(kThreads, 2) void k_conv3x3_f16(const char* __restrict__ x, const char* __restrict__ w,
-                                                             const _Float16* __restrict__ bias, const _Float16* __restrict__ res,
-                                                             _Float16* __restrict__ y, int M, int H, int W, int Cin, int K, int relu,
-                                                             Deal d, Recip dhw, Recip dw) {
+template <bool kHasRes, bool kBoard>
+__device__ __forceinline__ void conv_body(const char* __restrict__ x, const char* __restrict__ w, const _Float16* __restrict__ bias,
+                                          const _Float16* __restrict__ res, _Float16* __restrict__ y, int M, int H, int W, int Cin,
+                                          int K, int relu, const Deal& d, Recip dhw, Recip dw) {
   __shared__ __attribute__((aligned(128))) char lds[kLdsBytes];   // ALL of the kernel's LDS: one array
   const int tid = threadIdx.x;
   Ctx c;
-  c.lds = lds; c.x = x; c.w = w; c.M = M; c.H = H; c.W = W; c.Cin = Cin; c.K = K; c.relu = relu; c.dhw = dhw; c.dw = dw;
+  c.lds = lds; c.M = M; c.H = H; c.W = W; c.Cin = Cin; c.K = K; c.relu = relu; c.dhw = dhw; c.dw = dw;
   c.stride = d.stride;
   c.lane = tid & 63;
   c.wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  c.zsrc = g_zero_line + (c.lane & 7) * 16;
+  // the two descriptors, from kernel arguments alone: scalar registers.  x's starts bias bytes in front of x and is bias bytes
+  // longer (the comment at kSentinel); both sizes are below 2^31 + 2^30
+  c.bias = x_bias(W, Cin);
+  c.xr = __builtin_amdgcn_make_buffer_rsrc((void*)(x - c.bias), 0, (int)((uint32_t)M * (uint32_t)(Cin * 2) + c.bias), (int)kRsrcWord3);
+  c.wr = __builtin_amdgcn_make_buffer_rsrc((void*)w, 0, (int)((uint32_t)K * (uint32_t)(9 * Cin * 2)), (int)kRsrcWord3);
   const int G = (int)gridDim.x, g = (int)blockIdx.x, kchunks = Cin >> 6;
   int id = g;
   Item it = item_of(d, id, M, H, W);   // a full item: see above
   Rows rw;
-  decode_rows<2>(c, rw, it);
-  issue_prologue<2>(c, rw, kchunks, it.mask);
+  decode_rows<2, kBoard>(c, rw, it);
+  issue_prologue<2, kBoard>(c, rw, kchunks, it.mask);
   wait_staged<8, false>();   // Xa, Wa, Wb of K tile 0; behind them Xb(0), Xa(1), Wa(1), Wb(1)
   raw_barrier();
   // What follows an item is known before its main loop, and is the same for every wave.  While it is a full item the staging
@@ -840,10 +890,12 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv3x3_f16(const char* __restr
     nid = next_id(d, id, g, G);
     if (nid >= d.ids) break;
     nit = item_of(d, nid, M, H, W);
-    if (__builtin_amdgcn_readfirstlane(nit.half) >= 0) break;
+    if constexpr (!kBoard) {   // board order has no half items
+      if (__builtin_amdgcn_readfirstlane(nit.half) >= 0) break;
+    }
     floatx16 acc[4][2];
     c.lane = fresh(lane);
-    main_loop<2, true>(c, rw, acc, par, stores, it.mask, nit);
+    main_loop<2, true, kBoard>(c, rw, acc, par, stores, it.mask, nit);
     stores = finish_chained<kHasRes>(c, lane, acc, bias, res, y, it);
     par = (par + __builtin_popcount((unsigned)it.mask) * kchunks) & 1;   // the item's own K tiles
     id = nid;
@@ -851,16 +903,50 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv3x3_f16(const char* __restr
   }
   floatx16 acc[4][2];
   c.lane = fresh(lane);
-  main_loop<2, false>(c, rw, acc, par, stores, it.mask, it);
-  if (nid >= d.ids) {
-    finish_item<kHasRes, 2, 0>(c, lane, rw, acc, bias, res, y, it, it);
+  main_loop<2, false, kBoard>(c, rw, acc, par, stores, it.mask, it);
+  if (kBoard || nid >= d.ids) {
+    finish_item<kHasRes, 2, 0, kBoard>(c, lane, rw, acc, bias, res, y, it, it);
     return;
   }
-  finish_item<kHasRes, 2, 1>(c, lane, rw, acc, bias, res, y, it, nit);
-  floatx16 acch[4][1];
-  c.lane = fresh(lane);
-  main_loop<1, false>(c, rw, acch, 0, false, nit.mask, nit);
-  finish_item<kHasRes, 1, 0>(c, lane, rw, acch, bias, res, y, nit, nit);
+  if constexpr (!kBoard) {
+    finish_item<kHasRes, 2, 1, kBoard>(c, lane, rw, acc, bias, res, y, it, nit);
+    floatx16 acch[4][1];
+    c.lane = fresh(lane);
+    main_loop<1, false, kBoard>(c, rw, acch, 0, false, nit.mask, nit);
+    finish_item<kHasRes, 1, 0, kBoard>(c, lane, rw, acch, bias, res, y, nit, nit);
+  }
+}
+// The two row orders are two kernels of the one body: board order stages every activation piece from its row's offset as it is,
+// linear order keeps the rows' tap masks and one select per piece, and only linear order has half items.
+template <bool kHasRes>
+__global__ __launch_bounds__(kThreads, 2) void k_conv3x3_f16(const char* __restrict__ x, const char* __restrict__ w,
+                                                             const _Float16* __restrict__ bias, const _Float16* __restrict__ res,
+                                                             _Float16* __restrict__ y, int M, int H, int W, int Cin, int K, int relu,
+                                                             Deal d, Recip dhw, Recip dw) {
+  conv_body<kHasRes, false>(x, w, bias, res, y, M, H, W, Cin, K, relu, d, dhw, dw);
+}
+template <bool kHasRes>
+__global__ __launch_bounds__(kThreads, 2) void k_conv3x3_f16_boards(const char* __restrict__ x, const char* __restrict__ w,
+                                                                    const _Float16* __restrict__ bias, const _Float16* __restrict__ res,
+                                                                    _Float16* __restrict__ y, int M, int H, int W, int Cin, int K,
+                                                                    int relu, Deal d, Recip dhw, Recip dw) {
+  conv_body<kHasRes, true>(x, w, bias, res, y, M, H, W, Cin, K, relu, d, dhw, dw);
+}
+
+// The zero-fill probe of elfnet_conv3x3_f16_bufstage_probe: one wave, one staged piece.  1 KiB of LDS at lds_off is filled with
+// 0xFF by ds_write, then lane l stages 16 B from voff[l] + soff through a descriptor of `records` bytes at src, and the KiB is
+// copied out.
+__global__ __launch_bounds__(64) void k_bufstage_probe(const char* __restrict__ src, uint32_t records, const uint32_t* __restrict__ voff,
+                                                       uint32_t soff, uint32_t lds_off, uint32x4* __restrict__ out) {
+  __shared__ __attribute__((aligned(128))) char lds[kLdsBytes];
+  const int lane = threadIdx.x;
+  char* const dst = lds + lds_off;   // the host entry keeps it a multiple of 1024 and the KiB inside the array
+  *(uint32x4*)(dst + lane * 16) = uint32x4{~0u, ~0u, ~0u, ~0u};
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  const rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, (int)records, (int)kRsrcWord3);
+  stage16(r, voff[lane], soff, dst);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  out[lane] = *(const uint32x4*)(dst + lane * 16);
 }
 
 // the CU count of the current device, asked for once per device
@@ -960,6 +1046,7 @@ extern "C" __attribute__((visibility("hidden"))) int elfnet_conv3x3_native_f16(c
                                                                                hipStream_t stream) {
   if ((c & 63) != 0 || (k & 255) != 0 || round_width < 0 || order < -1 || order > 1) return ELFGO_E_BADARG;
   if (order == 1 && !board_takes(rows, h, wd, c, k)) return ELFGO_E_BADARG;
+  if (!bufstage_takes(wd, c)) return ELFGO_E_BADARG;   // a board some 2^27 / c positions wide: the comment at kSentinel
   const int64_t m = rows * h * wd;
   const int width = round_width > 0 ? round_width : round_width_of_device();
   if (order < 0) order = order_of(rows, h, wd, c, k, width);
@@ -967,12 +1054,10 @@ extern "C" __attribute__((visibility("hidden"))) int elfnet_conv3x3_native_f16(c
   const Deal d = order ? board_deal(rows, h, wd, k, width, &G) : linear_deal(m, k, width, &G);
   const dim3 grid((unsigned)G);
   const Recip dhw = recip_of((uint32_t)(h * wd)), dw = recip_of((uint32_t)wd);   // h * wd <= m, below 2^31
-  if (res)
-    hipLaunchKernelGGL(k_conv3x3_f16<true>, grid, dim3(kThreads), 0, stream, (const char*)x, (const char*)w, (const _Float16*)bias,
-                       (const _Float16*)res, (_Float16*)y, (int)m, h, wd, c, k, relu, d, dhw, dw);
-  else
-    hipLaunchKernelGGL(k_conv3x3_f16<false>, grid, dim3(kThreads), 0, stream, (const char*)x, (const char*)w, (const _Float16*)bias,
-                       (const _Float16*)nullptr, (_Float16*)y, (int)m, h, wd, c, k, relu, d, dhw, dw);
+  const auto kern = order ? (res ? k_conv3x3_f16_boards<true> : k_conv3x3_f16_boards<false>)
+                          : (res ? k_conv3x3_f16<true> : k_conv3x3_f16<false>);
+  hipLaunchKernelGGL(kern, grid, dim3(kThreads), 0, stream, (const char*)x, (const char*)w, (const _Float16*)bias,
+                     (const _Float16*)res, (_Float16*)y, (int)m, h, wd, c, k, relu, d, dhw, dw);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
@@ -1055,6 +1140,44 @@ extern "C" int elfnet_conv3x3_f16_recip(int64_t divisor, uint32_t* mul, uint32_t
   *mul = r.mul;
   *shift = r.shift;
   return 0;
+}
+
+// Host arithmetic only: what the kernel's buffer-addressed staging addresses a shape by (the comment at kSentinel; the kernel calls
+// the same functions).  bias: how far x's descriptor starts in front of x; x_records, w_records: the two descriptors' num_records;
+// sentinel: the vector offset of a lane that stages zeros.  With 0 <= tap < 9 and 0 <= kc < c / 64 also the scalar offsets of K
+// tile (tap, kc); tap < 0: the shape's values alone.  The vector offset of position p's 16-byte chunk q is p * c * 2 + 16 q in x,
+// that of output channel n's is n * 9 * c * 2 + 16 q in w.  Refuses what the launch refuses.
+extern "C" int elfnet_conv3x3_f16_bufstage(int64_t rows, int h, int wd, int c, int k, int tap, int kc, uint32_t* bias,
+                                           uint32_t* x_records, uint32_t* w_records, uint32_t* sentinel, uint32_t* x_soff,
+                                           uint32_t* w_soff) {
+  if (rows <= 0 || h <= 0 || wd <= 0 || c <= 0 || k <= 0 || (c & 63) != 0 || (k & 255) != 0 || tap >= 9) return ELFGO_E_BADARG;
+  if (rows * h * wd * (int64_t)(c > k ? c : k) >= ((int64_t)1 << 30) || (int64_t)k * 9 * c >= ((int64_t)1 << 30)) return ELFGO_E_BADARG;
+  if (!bufstage_takes(wd, c) || (tap >= 0 && (kc < 0 || kc >= (c >> 6)))) return ELFGO_E_BADARG;
+  const uint32_t b = x_bias(wd, c);
+  if (bias) *bias = b;
+  if (x_records) *x_records = (uint32_t)(rows * h * wd) * (uint32_t)(c * 2) + b;
+  if (w_records) *w_records = (uint32_t)k * (uint32_t)(9 * c * 2);
+  if (sentinel) *sentinel = kSentinel;
+  if (tap >= 0) {
+    if (x_soff) *x_soff = x_soffset(wd, c, tap, kc);
+    if (w_soff) *w_soff = w_soffset(c, tap, kc);
+  }
+  return 0;
+}
+
+// One staged piece of one wave, for the test of what the hardware does with a lane that is out of range: 1 KiB of LDS at byte
+// lds_offset (a multiple of 1024, below 160 KiB) is filled with 0xFF, lane l stages 16 bytes from voffset[l] + soffset through a
+// raw buffer descriptor of `records` bytes at src with the kernel's own instruction, and the KiB is copied to out.  src, voffset
+// (64 x uint32) and out (1 KiB) are device memory; every voffset[l] + soffset + 16 that is at most `records` must lie inside src's
+// allocation.  One launch on `stream`, nothing else.
+extern "C" int elfnet_conv3x3_f16_bufstage_probe(const void* src, uint32_t records, const void* voffset, uint32_t soffset,
+                                                 uint32_t lds_offset, void* out, void* stream) {
+  if (!src || !voffset || !out || (lds_offset & 1023u) != 0 || lds_offset > (uint32_t)(kLdsBytes - 1024)) return ELFGO_E_BADARG;
+  if ((((uintptr_t)src | (uintptr_t)out) & 15) != 0 || ((uintptr_t)voffset & 3) != 0) return ELFGO_E_BADARG;
+  hipLaunchKernelGGL(k_bufstage_probe, dim3(1), dim3(64), 0, (hipStream_t)stream, (const char*)src, records,
+                     (const uint32_t*)voffset, soffset, lds_offset, (uint32x4*)out);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
 }
 
 // Host arithmetic only: the workgroups of that launch.  Workgroup g runs the work ids g, g + G, g + 2 G, ... of the plan.

@@ -713,7 +713,7 @@ int elfnet_bias_act_bf16(void* x, const void* bias, const void* res, int64_t row
  *   x [rows,H,W,C], w [K,3,3,C] (a channels_last torch weight as it lies in memory), bias [K], res/y [rows,H,W,K];
  *   res may be NULL; y must not alias x or res.  algo: 0 = Composable Kernel's implicit GEMM with the tile configuration
  *   MIOpen's tuned database picks for the 2048 x 19 x 19 x 256 trunk shape, 1 = the hand-written 256 x 256 x 64 LDS-DMA kernel, which
- *   takes c % 64 == 0 and k % 256 == 0 only, keeps algo 0's accumulation order (the same output bits) and is the faster one from
+ *   takes c % 64 == 0, k % 256 == 0 and (2 W + 3) * c * 2 < 2^30 only (elfnet_conv3x3_f16_bufstage), keeps algo 0's accumulation order (the same output bits) and is the faster one from
  *   about 33 000 positions (rows * H * W) on.
  *   Algo 1 has two row orders with the same output bits for finite operands.  Linear: a work item is 256 consecutive positions
  *   (n, h, w) and runs all nine taps, an off-board tap as a multiplication by zeros.  Board: a work item is one board position
@@ -777,6 +777,28 @@ int64_t elfnet_conv3x3_f16_grid(int64_t tiles, int columns, int round_width);
  * for every 0 <= n < 2^31, n / divisor == (((n + 1) * mul) >> 32) >> shift, the product taken in 64 bits.  1 <= divisor <= 2^31,
  * otherwise (or with a NULL out pointer) ELFGO_E_BADARG; 0 on success. */
 int elfnet_conv3x3_f16_recip(int64_t divisor, uint32_t* mul, uint32_t* shift);
+/* Host arithmetic: what algo 1's kernel addresses x and w by when it stages a K tile.  It reads both through raw buffer descriptors
+ * (stride 0): a lane's 32-bit byte offset in a vector register plus a wave-uniform scalar offset, both unsigned.  x's descriptor
+ * starts *bias = (wd + 1) * c * 2 bytes in front of x, so that the scalar offset of a tap above or left of a position is not
+ * negative.  *x_records and *w_records are the descriptors' sizes in bytes (x's: the tensor plus bias), *sentinel is the vector
+ * offset of a lane that stages zeros (a row at or beyond its item's limit, an off-board tap in linear order): it is at or above
+ * both sizes for every shape the launch takes, a multiple of 16 and the same for every shape.  With 0 <= tap < 9 (3 ky + kx) and
+ * 0 <= kc < c / 64, *x_soff and *w_soff are the scalar offsets of that tap's channels 64 kc .. 64 kc + 63; tap < 0: the shape's
+ * four values alone.  The vector offset of chunk q (16 bytes, 8 channels) of position p is p * c * 2 + 16 q, and
+ * that + *x_soff - *bias is the byte offset in x of the same chunk of the tap's neighbour; a weight row n starts at n * 9 * c * 2.
+ * No sum of a vector offset (the sentinel included) and a scalar offset reaches 2^32.  Any out pointer may be NULL.
+ * ELFGO_E_BADARG for what the launch refuses: rows, h, wd, c, k not positive, c no multiple of 64, k none of 256, a tensor of 2^30
+ * elements or more, and a board so wide that (2 wd + 3) * c * 2 >= 2^30 (which this kernel refuses too); tap >= 9 or kc out of
+ * range. */
+int elfnet_conv3x3_f16_bufstage(int64_t rows, int h, int wd, int c, int k, int tap, int kc, uint32_t* bias, uint32_t* x_records,
+                                uint32_t* w_records, uint32_t* sentinel, uint32_t* x_soff, uint32_t* w_soff);
+/* One staged piece of one wave of that kernel, for the test of what the hardware does with a lane that is out of range: 1 KiB of
+ * LDS at byte lds_offset (a multiple of 1024, at most 159 KiB) is filled with 0xFF, lane l of 64 stages 16 bytes from
+ * voffset[l] + soffset through a raw buffer descriptor of `records` bytes at src, and the KiB is copied to out.  src (16-byte
+ * aligned), voffset (64 x uint32_t) and out (1 KiB) are device memory on the current device; every 16 bytes at
+ * voffset[l] + soffset that end at or below `records` must lie inside src's allocation.  One launch on `stream`. */
+int elfnet_conv3x3_f16_bufstage_probe(const void* src, uint32_t records, const void* voffset, uint32_t soffset, uint32_t lds_offset,
+                                      void* out, void* stream);
 /* The same function as elfnet_conv3x3_f16 -- same tensors, same roundings, algo 0's accumulation order and therefore its output
  * bits -- on a third main loop, for calls of a few thousand positions (a single game's 16-row net call is 5 776): tiles of
  * 64 positions x 64 output channels, one plain launch of ceil(rows * h * wd / 64) x (k / 64) workgroups, so that such a call
