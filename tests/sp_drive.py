@@ -37,10 +37,45 @@ def sp_from_fixture_cfg(elf_amd, n, cfg, **over):
     return sp
 
 
-def drive_stub(sp, n, cfg, done, on_step=None, black_ver=None):
+def per_game(rec, coord, visits, prior, reward, games):
+    """a search log -> {game: [one tuple per search, in the game's own order]}; the floats as their bytes, so tuples compare bit for bit"""
+    out = {g: [] for g in range(games)}
+    for i, r in enumerate(rec):
+        ne = r.n_edges
+        out[r.game].append((ne, r.move_played, r.best_action, r.total_visits, np.float32(r.root_value).tobytes(),
+                            coord[i, :ne].tobytes(), visits[i, :ne].tobytes(), prior[i, :ne].tobytes(), reward[i, :ne].tobytes()))
+    return out
+
+
+_ORACLE_LOGS = {}
+
+
+def oracle_per_game(n, cfg, G, searches, preload=()):
+    """{g: [search tuples]} of G games played one at a time by the CPU restatement (oracle/mcts_oracle.cc), game g seeded
+    seed + g: the per-game seed rule of a G-game context (include/elf_amd.h).  preload: moves forwarded before the first search
+    (GameOptions.preload_sgf with preload_sgf_move_to = len(preload)).  Computed once per configuration and shared; read only."""
+    from pyoracle import PortSelfPlay
+    key = (n, G, searches, tuple(preload), tuple(sorted(cfg.items())))
+    if key not in _ORACLE_LOGS:
+        port = PortSelfPlay(n)
+        port.set_preload(list(preload), len(preload))
+        try:
+            want = {}
+            for g in range(G):
+                r = port.run(**dict(cfg, num_games=1, seed=int(cfg["seed"]) + g, max_searches=searches))
+                want[g] = per_game(r["search"], r["coord"], r["visits"], r["prior"], r["reward"], 1)[0]
+        finally:
+            port.set_preload([], -1)
+        _ORACLE_LOGS[key] = want
+    return _ORACLE_LOGS[key]
+
+
+def drive_stub(sp, n, cfg, done, on_step=None, black_ver=None, wait_rows=True):
     """serve batches with the stub nets of the fixture until done(sp); two-AI games through begin_step2 / end_step2 with the
     "actor_white" rows evaluated by the second stub net and every reply carrying its model's version in rv (black_ver: a callable
-    giving the (black, white) versions the models have now, for runs in which a later request changes them)"""
+    giving the (black, white) versions the models have now, for runs in which a later request changes them).  wait_rows=False
+    (one AI per game only): the row count stays on the device, every row of sp.s is evaluated and nothing is added to the
+    returned row totals"""
     import torch
     salt, ties = int(cfg["net_salt"]), int(cfg["net_tie_levels"])
     two = int(cfg.get("white_ver", -1)) >= 0 or int(cfg.get("req2_white_ver", -1)) >= 0
@@ -60,8 +95,11 @@ def drive_stub(sp, n, cfg, done, on_step=None, black_ver=None):
                 rows_total[a] += rows
             sp.end_step2(rep)
         else:
-            rows = sp.begin_step()
-            rows_total[0] += rows
+            rows = sp.begin_step(wait_rows=wait_rows)
+            if wait_rows:
+                rows_total[0] += rows
+            else:
+                rows = sp.max_rows          # without the wait every row is evaluated; stale ones are ignored
             if rows:
                 pi, v = stub_net(n, sp.s[:rows].cpu().numpy(), salt, ties)
                 sp.end_step(torch.from_numpy(pi).to(sp.device), torch.from_numpy(v).to(sp.device),

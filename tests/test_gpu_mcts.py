@@ -9,7 +9,7 @@ import pytest
 
 from conftest import GOLDEN
 from pyoracle import stub_net
-from sp_drive import drive_stub, sp_from_fixture_cfg
+from sp_drive import drive_stub, per_game as _per_game, sp_from_fixture_cfg
 
 pytestmark = pytest.mark.gpu
 
@@ -355,15 +355,6 @@ def _drive_stub(sp, n, cfg, searches, wait_rows=True):
             sp.end_step(torch.from_numpy(pi).to(sp.device), torch.from_numpy(v).to(sp.device))
         else:
             sp.end_step(None, None)
-
-
-def _per_game(rec, coord, visits, prior, reward, games):
-    out = {g: [] for g in range(games)}
-    for i, r in enumerate(rec):
-        ne = r.n_edges
-        out[r.game].append((ne, r.move_played, r.best_action, r.total_visits, np.float32(r.root_value).tobytes(),
-                            coord[i, :ne].tobytes(), visits[i, :ne].tobytes(), prior[i, :ne].tobytes(), reward[i, :ne].tobytes()))
-    return out
 
 
 @pytest.mark.parametrize("n,G,roll,per_game", [(19, 8, 64, 4), (9, 16, 48, 10)])
