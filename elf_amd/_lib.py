@@ -49,6 +49,9 @@ SIGNATURES = {
     "elfgo_own_destroy": (_i, [_vp]),
     "elfgo_own_scratch_bytes": (_sz, [_vp]),
     "elfgo_own_run": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "elfgo_candidates": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "elfgo_playout_cand": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "elfgo_own_run_cand": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "elfmcts_create": (_i, [_vp, _i, _i, _i, _vp, C.POINTER(_vp)]),
     "elfmcts_destroy": (_i, [_vp]),
     "elfmcts_set_options": (_i, [_vp, _vp]),

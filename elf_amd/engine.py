@@ -238,10 +238,12 @@ class GoEngine:
         check(self.L.elfgo_export_board(self._h, p, k, C.c_void_p(col.data_ptr()), C.c_void_p(lib.data_ptr()), self._stream()))
         return col, lib
 
-    def playout(self, seeds, ids=None, max_steps=1 << 20, out=None):
+    def playout(self, seeds, ids=None, max_steps=1 << 20, out=None, self_atari_thres=None):
         """config-2 protocol: random legal non-true-eye play to game end, whole games in one launch.
         seeds: uint64 per board (numpy or int64-viewed tensor). Returns uint32-as-int64 tensor [k,4] =
-        hash_lo, hash_hi, ply, steps."""
+        hash_lo, hash_hi, ply, steps.
+        self_atari_thres=t plays from the reference's FindAllCandidateMoves(board, player, t) instead (elfgo_playout_cand): the
+        same list minus the self-ataris of t stones or more; None is elfgo_playout itself."""
         if isinstance(seeds, torch.Tensor):
             sd = seeds.to(self.device).contiguous()
         else:
@@ -251,7 +253,11 @@ class GoEngine:
         assert k2 == k
         if out is None:
             out = torch.empty((k, 4), dtype=torch.int32, device=self.device)
-        check(self.L.elfgo_playout(self._h, p, C.c_void_p(sd.data_ptr()), k, int(max_steps), C.c_void_p(out.data_ptr()), self._stream()))
+        if self_atari_thres is None:
+            check(self.L.elfgo_playout(self._h, p, C.c_void_p(sd.data_ptr()), k, int(max_steps), C.c_void_p(out.data_ptr()), self._stream()))
+        else:
+            check(self.L.elfgo_playout_cand(self._h, p, C.c_void_p(sd.data_ptr()), k, int(max_steps), int(self_atari_thres),
+                                            C.c_void_p(out.data_ptr()), self._stream()))
         return out
 
     # ---- per-point answers
@@ -274,14 +280,28 @@ class GoEngine:
                                       self._stream()))
         return (depth, calls) if with_calls else depth
 
-    def ownership(self, seeds, ids=None, playouts=256, komi=7.5, max_steps=1 << 20, max_lanes=0):
+    def candidates(self, ids=None, n=None, self_atari_thres=1):
+        """Self-atari reading for the side to move (isSelfAtari, base/board.cc:254-297, and FindAllCandidateMoves, :850-890)
+        -> (mask uint8 [k, N*N], stones int16 [k, N*N]), index a = x*N + y: mask is 1 on the legal points that are neither
+        the mover's own true eye nor a self-atari of self_atari_thres stones or more; stones is the size of the group a move
+        there would leave with exactly one liberty, 0 where it is no self-atari (or illegal).  A row whose slot id lies
+        outside the pool gets mask 0 and stones -1."""
+        t, p, k = self._ids(ids, n)
+        mask = torch.empty((k, self.n * self.n), dtype=torch.uint8, device=self.device)
+        stones = torch.empty((k, self.n * self.n), dtype=torch.int16, device=self.device)
+        check(self.L.elfgo_candidates(self._h, p, k, int(self_atari_thres), C.c_void_p(mask.data_ptr()), C.c_void_p(stones.data_ptr()),
+                                      self._stream()))
+        return mask, stones
+
+    def ownership(self, seeds, ids=None, playouts=256, komi=7.5, max_steps=1 << 20, max_lanes=0, self_atari_thres=None):
         """Monte-Carlo ownership: `playouts` config-2 playouts from a private copy of each listed slot (the slots themselves are
         only read), playout k of row i with seed seeds[i] + k * 0x9E3779B97F4A7C15 (mod 2^64).  Returns a dict:
         counts int32 [k, 2, N*N] (playouts in which the point ended as black / white area) and stats int64 [k, 4] (sum of
         black - white area, black wins after komi, super-ko endings, steps played) straight from the device, and derived from
         them own = (black - white) / playouts float32 [k, N*N], score_mean = mean area difference - komi, black_win_rate.
         The scratch handle is made on first use and lives until close(); max_lanes bounds the playouts in flight (0 = a default
-        from the CU count)."""
+        from the CU count).  self_atari_thres=t plays the candidate policy of playout(self_atari_thres=t)
+        (elfgo_own_run_cand); None is elfgo_own_run itself."""
         if isinstance(seeds, torch.Tensor):
             sd = seeds.to(self.device).contiguous()
         else:
@@ -300,8 +320,13 @@ class GoEngine:
             self._own = own = (int(max_lanes), h)
         counts = torch.empty((k, 2, self.n * self.n), dtype=torch.int32, device=self.device)
         stats = torch.empty((k, 4), dtype=torch.int64, device=self.device)
-        check(self.L.elfgo_own_run(own[1], p, C.c_void_p(sd.data_ptr()), k, int(playouts), int(max_steps), float(komi),
-                                   C.c_void_p(counts.data_ptr()), C.c_void_p(stats.data_ptr()), self._stream()))
+        if self_atari_thres is None:
+            check(self.L.elfgo_own_run(own[1], p, C.c_void_p(sd.data_ptr()), k, int(playouts), int(max_steps), float(komi),
+                                       C.c_void_p(counts.data_ptr()), C.c_void_p(stats.data_ptr()), self._stream()))
+        else:
+            check(self.L.elfgo_own_run_cand(own[1], p, C.c_void_p(sd.data_ptr()), k, int(playouts), int(max_steps), float(komi),
+                                            int(self_atari_thres), C.c_void_p(counts.data_ptr()), C.c_void_p(stats.data_ptr()),
+                                            self._stream()))
         return dict(counts=counts, stats=stats,
                     own=(counts[:, 0] - counts[:, 1]).to(torch.float32) / playouts,
                     score_mean=stats[:, 0].to(torch.float64) / playouts - komi,

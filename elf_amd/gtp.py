@@ -7,7 +7,7 @@ same replies ("= ..." / "? ..."), same coordinate letters (no 'I'): protocol_ver
 clear_board, play, genmove, showboard, final_score, list_commands, quit/exit.  On top of the reference's set (whose `u` / `h`
 commands are commented out, console_lib.py:196-204): undo, fixed_handicap, place_free_handicap, set_free_handicap, loadsgf,
 known_command -- what every GTP front-end sends -- over SelfPlay.setup / SelfPlay.undo; final_status_list and the private
-elf-ownership, elf-score_estimate and elf-ladders over the per-point answers of the board engine; lz-genmove_analyze (Leela Zero's
+elf-ownership, elf-score_estimate, elf-ladders and elf-candidates over the per-point answers of the board engine; lz-genmove_analyze (Leela Zero's
 analysing genmove, what Sabaki and Lizzie send) and elf-analysis over the search's candidates and lines (SelfPlay.analyze).
 
     eng = GtpEngine(actor, board_size=19, mcts_rollout_per_thread=1600)     # actor(batch) -> dict(pi=..., V=...)
@@ -73,7 +73,8 @@ HANDICAP_VERTICES = {2: ("D4", "Q16"), 3: ("D4", "Q16", "Q4"), 4: _H4, 5: _H4 + 
 
 
 class GtpEngine:
-    def __init__(self, actor, board_size=19, komi=7.5, device=0, status_playouts=256, status_seed=1, **selfplay_options):
+    def __init__(self, actor, board_size=19, komi=7.5, device=0, status_playouts=256, status_seed=1, status_self_atari_thres=None,
+                 **selfplay_options):
         opts = dict(mcts_rollout_per_thread=1600, mcts_rollout_per_batch=8, mcts_puct=1.5, mcts_virtual_loss=1,
                     mcts_persistent_tree=True, policy_distri_cutoff=0, resign_thres=0.0, seed=1)
         opts.update(selfplay_options)
@@ -85,11 +86,15 @@ class GtpEngine:
         self.exit = False
         self.status_playouts = int(status_playouts)
         self.status_seed = int(status_seed)
+        # None: the status playouts fill everything but the mover's own true eyes, and no seki is reported.  A threshold t: they
+        # play the reference's candidate moves (no self-atari of t stones or more), and final_status_list reports seki
+        self.status_self_atari_thres = None if status_self_atari_thres is None else int(status_self_atari_thres)
         self.commands = {k[3:]: f for k, f in inspect.getmembers(self, predicate=inspect.ismethod) if k.startswith("on_")}
         # private extensions carry the "elf-" prefix (GTP 2, section 2.13); a method name cannot hold the hyphen
         self.commands["elf-ownership"] = self.commands.pop("elf_ownership")
         self.commands["elf-score_estimate"] = self.commands.pop("elf_score_estimate")
         self.commands["elf-ladders"] = self.commands.pop("elf_ladders")
+        self.commands["elf-candidates"] = self.commands.pop("elf_candidates")
         self.commands["elf-analysis"] = self.commands.pop("elf_analysis")
         self.commands["lz-genmove_analyze"] = self.commands.pop("lz_genmove_analyze")
         # every finished search leaves its candidates and lines behind (elf-analysis): one small launch per move of one game
@@ -349,19 +354,55 @@ class GtpEngine:
     def _status_counts(self):
         """-> (stone colour per point, playouts that ended with the point black, ... white), numpy [N*N] in action order"""
         import numpy as np
-        own = self.boards.ownership(np.array([self.status_seed], np.uint64), ids=[0], playouts=self.status_playouts, komi=self.komi)
+        own = self.boards.ownership(np.array([self.status_seed], np.uint64), ids=[0], playouts=self.status_playouts, komi=self.komi,
+                                    self_atari_thres=self.status_self_atari_thres)
         counts = own["counts"].cpu().numpy()[0]
         col = self.boards.export_board(n=1)[0].cpu().numpy()[0]
         return col, counts[0], counts[1]
 
+    def _seki(self, col, cb, cw, dead):
+        """Stones that are not dead and whose group touches an empty point that ended as neither colour's area in more than half
+        of the playouts: with self-ataris kept out of the playouts, the shared liberties of a seki stay open to the end."""
+        import numpy as np
+        n = self.n
+        g = col.reshape(n, n)
+        open_pt = ((col == 0) & (2 * (self.status_playouts - cb - cw) > self.status_playouts)).reshape(n, n)
+        seki = np.zeros((n, n), bool)
+        seen = np.zeros((n, n), bool)
+        for x0, y0 in zip(*np.nonzero(g)):
+            if seen[x0, y0]:
+                continue
+            group, stack, touches = [], [(int(x0), int(y0))], False
+            seen[x0, y0] = True
+            while stack:
+                x, y = stack.pop()
+                group.append((x, y))
+                for qx, qy in ((x - 1, y), (x + 1, y), (x, y - 1), (x, y + 1)):
+                    if not (0 <= qx < n and 0 <= qy < n):
+                        continue
+                    if open_pt[qx, qy]:
+                        touches = True
+                    elif g[qx, qy] == g[x0, y0] and not seen[qx, qy]:
+                        seen[qx, qy] = True
+                        stack.append((qx, qy))
+            if touches:
+                for x, y in group:
+                    seki[x, y] = True
+        return seki.reshape(-1) & ~dead
+
     def on_final_status_list(self, items):
         """A stone is dead iff its point ends as the opponent's area in more of the playouts than as its own colour's, else
-        alive.  Seki is not detected: `seki` is always the empty list (stones in seki are reported alive)."""
+        alive.  By default seki is not detected: `seki` is the empty list and stones in seki are reported alive (or, where the
+        playouts fill their shared liberties, dead).  With status_self_atari_thres set, the playouts keep off self-ataris of that
+        size, and `seki` lists the stones that are not dead and whose group touches an empty point that ended as neither colour's
+        area in more than half of the playouts; `alive` then leaves them out.  A Monte-Carlo heuristic, not a proof: a dame that
+        both sides happen to leave open reads the same way."""
         if len(items) < 2 or items[1] not in ("dead", "alive", "seki"):
             return False, "invalid status"
         col, cb, cw = self._status_counts()
         dead = ((col == 1) & (cw > cb)) | ((col == 2) & (cb > cw))
-        pick = dead if items[1] == "dead" else ((col != 0) & ~dead) if items[1] == "alive" else (col < 0)
+        seki = self._seki(col, cb, cw, dead) if self.status_self_atari_thres is not None else (col < 0)
+        pick = dead if items[1] == "dead" else ((col != 0) & ~dead & ~seki) if items[1] == "alive" else seki
         return True, " ".join(xy2move(a // self.n, a % self.n) for a in range(self.n * self.n) if pick[a])
 
     def on_elf_ownership(self, items):
@@ -379,6 +420,16 @@ class GtpEngine:
         (GoEngine.ladder_map on game 0's current position), as VERTEX:depth pairs in board order (a = x*N + y); empty if none."""
         depth = self.boards.ladder_map(ids=[0]).cpu().numpy()[0]
         return True, " ".join("%s:%d" % (xy2move(a // self.n, a % self.n), int(depth[a])) for a in range(self.n * self.n) if depth[a])
+
+    def on_elf_candidates(self, items):
+        """elf-candidates [thres]: the reference's candidate moves of the side to move (GoEngine.candidates on game 0's current
+        position; thres defaults to 1: no self-atari at all) in board order (a = x*N + y), like elf-ladders: VERTEX for a plain
+        candidate, VERTEX:stones for one that is a self-atari of fewer than thres stones (stones = the size of the group the move
+        would leave with one liberty); empty if there is none."""
+        thres = int(items[1]) if len(items) > 1 else 1
+        mask, stones = [t.cpu().numpy()[0] for t in self.boards.candidates(ids=[0], self_atari_thres=thres)]
+        return True, " ".join(xy2move(a // self.n, a % self.n) + (":%d" % int(stones[a]) if stones[a] > 0 else "")
+                              for a in range(self.n * self.n) if mask[a])
 
     def on_list_commands(self, items):
         return True, "\n".join(self.commands.keys())

@@ -143,6 +143,29 @@ size_t elfgo_own_scratch_bytes(const ElfGoOwnership* o);
 int elfgo_own_run(ElfGoOwnership* o, const int32_t* ids, const uint64_t* seeds, int n, int playouts, int max_steps,
                   float komi, int32_t* counts, int64_t* stats, void* stream);
 
+/* Self-atari reading and the reference's candidate moves for the side to move (isSelfAtari, base/board.cc:254-297;
+ * FindAllCandidateMoves, board.cc:850-890):
+ *     mask[i][a]   = 1 iff point a = x*N + y is in FindAllCandidateMoves(board, next_player, self_atari_thres): legal by
+ *                    TryPlay, not the mover's own true eye, and not a self-atari of self_atari_thres stones or more
+ *     stones[i][a] = the num_stones that isSelfAtari(board, NULL, a, next_player, &num_stones) writes where it returns true
+ *                    (the group on a after the move has exactly one liberty; num_stones is its size), else 0
+ * stones is 0 at illegal points; a mover's own true eye can carry a value although its mask byte is 0.  The threshold has the
+ * reference's meaning (board.cc:883: the move is dropped when num_stones >= self_atari_thres), so a value <= 1 drops every
+ * self-atari and one above N*N drops none; stones does not depend on it.  uint8 / int16 [n][N*N], device pointers, row stride
+ * N*N; either may be NULL, not both.  ids NULL = slots [0, n).  A row whose slot id lies outside the pool gets mask 0 and
+ * stones -1.  The slots are only read; a slot may be named several times.  ELFGO_E_BADARG for a null engine, n <= 0 or both
+ * outputs NULL: nothing is launched. */
+int elfgo_candidates(ElfGoEngine* e, const int32_t* ids, int n, int self_atari_thres, uint8_t* mask, int16_t* stones,
+                     void* stream);
+/* elfgo_playout with the move list of FindAllCandidateMoves(board, next_player, self_atari_thres) (board.cc:850-890) in place
+ * of "legal and not the mover's own true eye": the same RNG, the same (rand % count)-th candidate in x-major order, pass when
+ * there is none, the same termination and the same out words.  With a threshold above N*N it plays elfgo_playout's games. */
+int elfgo_playout_cand(ElfGoEngine* e, const int32_t* ids, const uint64_t* seeds, int n, int max_steps, int self_atari_thres,
+                       uint32_t* out, void* stream);
+/* elfgo_own_run whose playouts are elfgo_playout_cand's (board.cc:850-890): the same seed rule, counts and stats. */
+int elfgo_own_run_cand(ElfGoOwnership* o, const int32_t* ids, const uint64_t* seeds, int n, int playouts, int max_steps,
+                       float komi, int self_atari_thres, int32_t* counts, int64_t* stats, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Device-resident MCTS (one tree per game) -- replaces, behind the same seams, the reference's
  *   elf/ai/tree_search/tree_search.h        TreeSearchT / TreeSearchSingleThreadT::batch_rollouts (:200-262)
