@@ -1,7 +1,8 @@
 // Self-atari reading and the reference's candidate-move policy: isSelfAtari (base/board.cc:254-297) for every point of a position
 // at once, FindAllCandidateMoves (board.cc:850-890) on top of it (k_candidates), and the playout kernels that pick from that list
-// instead of "legal minus own true eyes" (k_playout_cand, k_playout_own_cand).  One wave64 = one board, as everywhere else;
-// Board<N> is used through its public members only, and the slot's labels and liberties are only read.
+// instead of "legal minus own true eyes": CandPolicy, the policy of k_playout_cand here and of k_playout_own<N, CandPolicy>
+// (ownership.cuh).  One wave64 = one board, as everywhere else; Board<N> is used through its public members only, and the slot's
+// labels and liberties are only read.
 //   self-atari: the group that stands on the point after the move has exactly one liberty; num_stones is its size.
 //   prefilter:  isSelfAtari's two early exits, for all points at once on bitboards: two or more empty neighbours, or an own
 //               neighbour whose group has more than two liberties, and the move cannot end with one liberty (both are implied
@@ -19,10 +20,9 @@
 #pragma once
 #include "go_board.cuh"
 #include "engine_host.h"
-#include "ownership.cuh"
+#include "playout.cuh"
 
-#define CAND_WAVE 64
-#define CAND_WAVES 4   // boards per workgroup of the playout kernels: k_playout's PLAYOUT_WAVES
+#define CAND_WAVE 64   // k_candidates: one board per workgroup
 
 // The self-atari points among `test` (lane-distributed, a subset of the legal points of the side to move) whose group would
 // have at least `thres` stones: what FindAllCandidateMoves drops (board.cc:880-885).  bd.at_cache must be the atari set of the
@@ -184,55 +184,29 @@ __global__ __launch_bounds__(CAND_WAVE) void k_candidates(Pool<N> pool, int capa
   }
 }
 
-// k_playout's pick: the (x % total)-th set bit of the lane-distributed candidate bitboard in x-major order, -1 when there is none.
-// Inclusive prefix sum of the word counts over the lanes of row 0 on the DPP network, the word, the rank inside it; mlds[d] =
-// floor(2^32 / d) (the estimate of x / total is at most one too small).
-template <int N>
-__device__ __forceinline__ int cand_pick(u64 cand, u32 x, const u32* mlds) {
-  using G = Geo<N>;
-  const int cnt = __popcll(cand);
-  int inc = cnt;
-  inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, true);
-  inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, true);
-  if (G::R > 4) inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, true);
-  const int total = rl(inc, G::R - 1);
-  if (total <= 0) return -1;
-  const u32 qd = __umulhi(x, (u32)rfl((int)mlds[total]));
-  u32 rr = x - qd * (u32)total;
-  if (rr >= (u32)total) rr -= (u32)total;
-  const int kw = __popc((u32)bal_le((u32)inc, rr) & ((1u << G::R) - 1u));
-  const int base = rl(inc - cnt, kw);
-  const u64 wk = rl64(cand, kw);
-  const u32 rank = __builtin_amdgcn_mbcnt_hi((u32)(wk >> 32), __builtin_amdgcn_mbcnt_lo((u32)wk, 0));
-  const u64 sel = bal_eq(rank, rr - (u32)base) & wk;
-  return kw * 64 + (int)__builtin_ctzll(sel);
-}
-
-// One playout step with the candidate policy; returns 0 when forward refused (the game is over).  A threshold above N*N drops
-// nothing (no group is that large): the self-atari reading is skipped and the step is k_playout's.
-template <int N>
-__device__ __forceinline__ int cand_step(Board<N>& bd, const GameSK<N>& sk, u32 key, int thres, const u32* mlds) {
-  const u32 x = playout_rng_k(key, (u32)bd.ply);
-  u64 legal, cand;
-  bd.template legal_moves<true, true>(legal, cand);
-  if (thres <= Geo<N>::NP && bal_ne64(cand, 0ull)) cand &= ~self_atari_drop<N, false>(bd, cand, thres, nullptr);
-  const int pick_a = cand_pick<N>(cand, x, mlds);
-  return pick_a >= 0 ? bd.forward_legal_action(pick_a, sk) : bd.forward(M_PASS, sk);
-}
+// The candidate policy of the playouts: FindAllCandidateMoves' cut of the self-atari points of at least `thres` stones.  A
+// threshold above N*N drops nothing (no group is that large): the self-atari reading is skipped and the step is k_playout's.
+struct CandPolicy {
+  int thres;
+  template <int N>
+  __device__ __forceinline__ u64 keep(const Board<N>& bd, u64 cand) const {
+    if (thres <= Geo<N>::NP && bal_ne64(cand, 0ull)) cand &= ~self_atari_drop<N, false>(bd, cand, thres, nullptr);
+    return cand;
+  }
+};
 
 // k_playout (elf_amd.hip) with the candidate policy: the same RNG, x-major pick, termination and `out` words.
 template <int N>
-__global__ __launch_bounds__(CAND_WAVE * CAND_WAVES) void k_playout_cand(Pool<N> pool, const int32_t* ids, const u64* seeds, int n,
-                                                                          int max_steps, int thres, uint32_t* out) {
+__global__ __launch_bounds__(PLAYOUT_WAVE * PLAYOUT_WAVES) void k_playout_cand(Pool<N> pool, const int32_t* ids, const u64* seeds, int n,
+                                                                                int max_steps, int thres, uint32_t* out) {
   using G = Geo<N>;
-  __shared__ Slot<N> lds_all[CAND_WAVES];
+  __shared__ Slot<N> lds_all[PLAYOUT_WAVES];
   __shared__ u64 zlds[G::P];
-  __shared__ u32 mlds[G::NP + 2];   // floor(2^32 / d) for the pick's rng % candidates
-  for (int j = threadIdx.x; j < G::P; j += CAND_WAVE * CAND_WAVES) zlds[j] = pool.zob[j];
-  for (int j = threadIdx.x; j < G::NP + 2; j += CAND_WAVE * CAND_WAVES) mlds[j] = (u32)pool.zob[G::ZOBW + 4 * G::R + j];
+  __shared__ u32 mlds[G::NP + 2];
+  playout_tables<N, PLAYOUT_WAVE * PLAYOUT_WAVES>(pool.zob, zlds, mlds);
   __syncthreads();
   const int wv = rfl((int)(threadIdx.x >> 6));   // wave-uniform by construction
-  const int game = blockIdx.x * CAND_WAVES + wv;
+  const int game = blockIdx.x * PLAYOUT_WAVES + wv;
   if (game >= n) return;
   Slot<N>& lds = lds_all[wv];
   const int b = rfl(ids ? ids[game] : game);
@@ -242,88 +216,11 @@ __global__ __launch_bounds__(CAND_WAVE * CAND_WAVES) void k_playout_cand(Pool<N>
   const GameSK<N> sk{pool.skr(b)};
   const u32 key = playout_key(seeds[game]);
   bd.playout_begin(zlds);
-  int steps = 0;
-  while (steps < max_steps && !bd.terminated()) {
-    if (!cand_step<N>(bd, sk, key, thres, mlds)) break;
-    ++steps;
-  }
+  const int steps = playout_run<N>(bd, sk, key, max_steps, CandPolicy{thres}, mlds);
   bd.store(&pool.slots[b]);
   if (bd.lane == 0) {
     const u64 h = bd.hash;
     uint32_t* o = out + (size_t)game * 4;
     o[0] = (u32)h; o[1] = (u32)(h >> 32); o[2] = (u32)bd.ply; o[3] = (u32)steps;
   }
-}
-
-// k_playout_own (ownership.cuh) with the candidate policy: the same seed rule, work split, record areas and integer sums.
-template <int N>
-__global__ __launch_bounds__(CAND_WAVE * CAND_WAVES) void k_playout_own_cand(Pool<N> pool, u64* scratch, const int32_t* ids, const u64* seeds,
-                                                                              int n, int K, int max_steps, float komi, int thres,
-                                                                              int32_t* counts, unsigned long long* stats) {
-  using G = Geo<N>;
-  static_assert(CAND_WAVES == OWN_WAVES && CAND_WAVE == OWN_WAVE, "the ownership handle's record areas are sized for OWN_WAVES waves per workgroup");
-  __shared__ Slot<N> lds_all[CAND_WAVES];
-  __shared__ u64 zlds[G::P];
-  __shared__ u32 mlds[G::NP + 2];
-  __shared__ int acc[2 * G::NP];
-  for (int j = threadIdx.x; j < G::P; j += CAND_WAVE * CAND_WAVES) zlds[j] = pool.zob[j];
-  for (int j = threadIdx.x; j < G::NP + 2; j += CAND_WAVE * CAND_WAVES) mlds[j] = (u32)pool.zob[G::ZOBW + 4 * G::R + j];
-  for (int j = threadIdx.x; j < 2 * G::NP; j += CAND_WAVE * CAND_WAVES) acc[j] = 0;
-  __syncthreads();
-  const int wv = rfl((int)(threadIdx.x >> 6));
-  u64* const rec = scratch + (size_t)(blockIdx.x * CAND_WAVES + wv) * (G::MAXMOVE + 2) * G::SKW;
-  Slot<N>& lds = lds_all[wv];
-  Board<N> bd;
-  bd.init(&lds, pool.zob, rec);
-  const GameSK<N> sk{rec};
-  const int pairs = n * K, groups = (pairs + CAND_WAVES - 1) / CAND_WAVES;   // n * K < 2^31 - CAND_WAVES: checked by the host
-  const int q0 = (int)((long long)groups * blockIdx.x / gridDim.x), q1 = (int)((long long)groups * (blockIdx.x + 1) / gridDim.x);
-  int have = -1;     // the slot whose record prefix `rec` holds
-  int wg_row = -1;   // the row `acc` counts for
-  auto flush = [&]() {
-    int* g = counts + (size_t)wg_row * 2 * G::NP;
-    for (int j = threadIdx.x; j < 2 * G::NP; j += CAND_WAVE * CAND_WAVES) {
-      const int v = acc[j];
-      if (v) { atomicAdd(&g[j], v); acc[j] = 0; }
-    }
-  };
-  for (int q = q0; q < q1; ++q) {
-    const int row0 = q * CAND_WAVES / K;
-    if (row0 != wg_row) {   // the same decision in every wave of the workgroup
-      if (wg_row >= 0) { flush(); __syncthreads(); }
-      wg_row = row0;
-    }
-    const int p = q * CAND_WAVES + wv;
-    if (p < pairs) {
-      const int row = p / K, k = p - row * K;
-      const int b = rfl(ids ? ids[row] : row);
-      bd.load(&pool.slots[b]);
-      if (b != have) {
-        const u64* src = pool.skr(b);
-        for (int j = bd.lane; j < bd.sk_len * G::SKW; j += CAND_WAVE) rec[j] = src[j];
-        have = b;
-      }
-      const u32 key = playout_key(own_seed(seeds[row], k));
-      bd.playout_begin(zlds);
-      int steps = 0;
-      while (steps < max_steps && !bd.terminated()) {
-        if (!cand_step<N>(bd, sk, key, thres, mlds)) break;
-        ++steps;
-      }
-      u32 ab, aw;
-      area_rows<N>(bd, ab, aw);
-      const int diff = area_diff(ab, aw);
-      if (row == wg_row) own_add_rows<N>(acc, ab, aw, bd.lane);
-      else own_add_rows<N>(counts + (size_t)row * 2 * G::NP, ab, aw, bd.lane);
-      if (bd.lane == 0) {
-        unsigned long long* st = stats + (size_t)row * 4;
-        atomicAdd(&st[0], (unsigned long long)(long long)diff);
-        if ((float)diff - komi > 0.0f) atomicAdd(&st[1], 1ull);
-        if (bd.superko) atomicAdd(&st[2], 1ull);
-        atomicAdd(&st[3], (unsigned long long)steps);
-      }
-    }
-    __syncthreads();   // this group's LDS adds are in before a flush reads them
-  }
-  if (wg_row >= 0) flush();
 }

@@ -3,14 +3,14 @@
 // members only.
 //   area:    simple_flood_fill per colour + the black && !white / white && !black rule of simple_tt_scoring
 //            (base/go_state.h:32-93) -- Board::tt_area()'s fill, restated here because it must keep the rows it popcounts
-//   policy:  k_playout's (elf_amd.hip), restated move for move: uniform over the legal, non-true-eye points in x-major
-//            order, rng % count with playout_rng_k(key, ply), pass when there is none
+//   playout: the shared loop of playout.cuh under the kernel's Policy argument; with EyePolicy it is k_playout's game
 #pragma once
 #include "go_board.cuh"
 #include "engine_host.h"
+#include "playout.cuh"
 
-#define OWN_WAVE 64
-#define OWN_WAVES 4   // boards per workgroup of k_playout_own: k_playout's PLAYOUT_WAVES
+#define OWN_WAVE PLAYOUT_WAVE
+#define OWN_WAVES PLAYOUT_WAVES   // boards per workgroup of k_playout_own; the handle's record areas are sized by it
 
 // seed(i, k) = seeds[i] + k * 0x9E3779B97F4A7C15 (mod 2^64): playout 0 of a row is what k_playout plays with seeds[i]
 __device__ __forceinline__ u64 own_seed(u64 row_seed, int k) { return row_seed + (u64)k * 0x9E3779B97F4A7C15ull; }
@@ -109,17 +109,17 @@ __device__ __forceinline__ void own_add_rows(int* dst, u32 ab, u32 aw, int lane)
 //  * Counters are accumulated in LDS for the row the workgroup is on (the row of a group's first pair) and flushed with
 //    atomicAdd when that row changes and at the end; a wave whose pair already belongs to the next row (a group may straddle
 //    two rows) adds to the global counters directly.
-template <int N>
+//  * `pol` is the playout policy (playout.cuh), last so that the arguments before it are elfgo_own_run's in order.
+template <int N, class Policy>
 __global__ __launch_bounds__(OWN_WAVE * OWN_WAVES) void k_playout_own(Pool<N> pool, u64* scratch, const int32_t* ids, const u64* seeds,
                                                                        int n, int K, int max_steps, float komi, int32_t* counts,
-                                                                       unsigned long long* stats) {
+                                                                       unsigned long long* stats, Policy pol) {
   using G = Geo<N>;
   __shared__ Slot<N> lds_all[OWN_WAVES];
   __shared__ u64 zlds[G::P];
-  __shared__ u32 mlds[G::NP + 2];   // floor(2^32 / d) for the pick's rng % candidates
+  __shared__ u32 mlds[G::NP + 2];
   __shared__ int acc[2 * G::NP];
-  for (int j = threadIdx.x; j < G::P; j += OWN_WAVE * OWN_WAVES) zlds[j] = pool.zob[j];
-  for (int j = threadIdx.x; j < G::NP + 2; j += OWN_WAVE * OWN_WAVES) mlds[j] = (u32)pool.zob[G::ZOBW + 4 * G::R + j];
+  playout_tables<N, OWN_WAVE * OWN_WAVES>(pool.zob, zlds, mlds);
   for (int j = threadIdx.x; j < 2 * G::NP; j += OWN_WAVE * OWN_WAVES) acc[j] = 0;
   __syncthreads();
   const int wv = rfl((int)(threadIdx.x >> 6));   // wave-uniform by construction
@@ -157,34 +157,7 @@ __global__ __launch_bounds__(OWN_WAVE * OWN_WAVES) void k_playout_own(Pool<N> po
       }
       const u32 key = playout_key(own_seed(seeds[row], k));
       bd.playout_begin(zlds);
-      int steps = 0;
-      while (steps < max_steps && !bd.terminated()) {
-        const u32 x = playout_rng_k(key, (u32)bd.ply);
-        u64 legal, cand;
-        bd.template legal_moves<true, true>(legal, cand);
-        // the (x % total)-th set bit of the lane-distributed candidate bitboard: inclusive prefix sum of the word counts over
-        // the lanes of row 0 on the DPP network, the word, the rank inside it
-        const int cnt = __popcll(cand);
-        int inc = cnt;
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, true);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, true);
-        if (G::R > 4) inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, true);
-        const int total = rl(inc, G::R - 1);
-        int pick_a = -1;   // action id of the chosen candidate, -1 = pass
-        if (total > 0) {
-          const u32 qd = __umulhi(x, (u32)rfl((int)mlds[total]));   // floor(2^32 / total) estimate of x / total, at most one too small
-          u32 rr = x - qd * (u32)total;
-          if (rr >= (u32)total) rr -= (u32)total;
-          const int kw = __popc((u32)bal_le((u32)inc, rr) & ((1u << G::R) - 1u));
-          const int base = rl(inc - cnt, kw);
-          const u64 wk = rl64(cand, kw);
-          const u32 rank = __builtin_amdgcn_mbcnt_hi((u32)(wk >> 32), __builtin_amdgcn_mbcnt_lo((u32)wk, 0));
-          const u64 sel = bal_eq(rank, rr - (u32)base) & wk;
-          pick_a = kw * 64 + (int)__builtin_ctzll(sel);
-        }
-        if (!(pick_a >= 0 ? bd.forward_legal_action(pick_a, sk) : bd.forward(M_PASS, sk))) break;
-        ++steps;
-      }
+      const int steps = playout_run<N>(bd, sk, key, max_steps, pol, mlds);
       u32 ab, aw;
       area_rows<N>(bd, ab, aw);
       const int diff = area_diff(ab, aw);

@@ -1312,8 +1312,9 @@ int elfsp_search_log(const ElfSelfPlay* sp, int first, int n, ElfSpSearch* rec, 
 #include "setup_host.h"
 // Ladder reading (elfgo_ladder_map): device code in ladder.cuh, entry point in ladder_host.h, here for the same reason.
 #include "ladder_host.h"
-// Self-atari reading and candidate-move playouts (elfgo_candidates, elfgo_playout_cand, elfgo_own_run_cand): device code in
-// candidates.cuh, entry points in candidates_host.h, here for the same reason.
+// Self-atari reading and candidate-move playouts (elfgo_candidates, elfgo_playout_cand, elfgo_own_run_cand): the policy and
+// k_playout_cand in candidates.cuh over the shared playout of playout.cuh, entry points in candidates_host.h (the ownership one
+// is ownership_host.h's own_run under CandPolicy), here for the same reason.
 #include "candidates_host.h"
 // Search analysis of the self-play context (elfsp_analyze, elfsp_set_analysis, elfsp_last_analysis): entry points in
 // analysis_host.h over elfmcts_analyze; here because they read this file's ElfSelfPlay.

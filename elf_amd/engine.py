@@ -238,12 +238,8 @@ class GoEngine:
         check(self.L.elfgo_export_board(self._h, p, k, C.c_void_p(col.data_ptr()), C.c_void_p(lib.data_ptr()), self._stream()))
         return col, lib
 
-    def playout(self, seeds, ids=None, max_steps=1 << 20, out=None, self_atari_thres=None):
-        """config-2 protocol: random legal non-true-eye play to game end, whole games in one launch.
-        seeds: uint64 per board (numpy or int64-viewed tensor). Returns uint32-as-int64 tensor [k,4] =
-        hash_lo, hash_hi, ply, steps.
-        self_atari_thres=t plays from the reference's FindAllCandidateMoves(board, player, t) instead (elfgo_playout_cand): the
-        same list minus the self-ataris of t stones or more; None is elfgo_playout itself."""
+    def _seeds(self, seeds, ids):
+        """One uint64 seed per listed slot (numpy or int64-viewed tensor) -> (device tensor, ids tensor, ids pointer, rows)."""
         if isinstance(seeds, torch.Tensor):
             sd = seeds.to(self.device).contiguous()
         else:
@@ -251,6 +247,15 @@ class GoEngine:
         k = sd.numel()
         t, p, k2 = self._ids(ids, k)
         assert k2 == k
+        return sd, t, p, k
+
+    def playout(self, seeds, ids=None, max_steps=1 << 20, out=None, self_atari_thres=None):
+        """config-2 protocol: random legal non-true-eye play to game end, whole games in one launch.
+        seeds: uint64 per board (numpy or int64-viewed tensor). Returns uint32-as-int64 tensor [k,4] =
+        hash_lo, hash_hi, ply, steps.
+        self_atari_thres=t plays from the reference's FindAllCandidateMoves(board, player, t) instead (elfgo_playout_cand): the
+        same list minus the self-ataris of t stones or more; None is elfgo_playout itself."""
+        sd, t, p, k = self._seeds(seeds, ids)
         if out is None:
             out = torch.empty((k, 4), dtype=torch.int32, device=self.device)
         if self_atari_thres is None:
@@ -302,13 +307,7 @@ class GoEngine:
         The scratch handle is made on first use and lives until close(); max_lanes bounds the playouts in flight (0 = a default
         from the CU count).  self_atari_thres=t plays the candidate policy of playout(self_atari_thres=t)
         (elfgo_own_run_cand); None is elfgo_own_run itself."""
-        if isinstance(seeds, torch.Tensor):
-            sd = seeds.to(self.device).contiguous()
-        else:
-            sd = torch.from_numpy(np.ascontiguousarray(seeds, dtype=np.uint64).view(np.int64)).to(self.device)
-        k = sd.numel()
-        t, p, k2 = self._ids(ids, k)
-        assert k2 == k
+        sd, t, p, k = self._seeds(seeds, ids)
         own = getattr(self, "_own", None)
         if own is None or own[0] != int(max_lanes):
             if own is not None:

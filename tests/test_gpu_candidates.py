@@ -1,5 +1,5 @@
-"""GPU: elfgo_candidates (k_candidates), elfgo_playout_cand (k_playout_cand) and elfgo_own_run_cand (k_playout_own_cand) against
-the reference's own FindAllCandidateMoves / isSelfAtari (candidates_expected, proven by tests/test_candidates_cpu.py).  Every
+"""GPU: elfgo_candidates (k_candidates), elfgo_playout_cand (k_playout_cand) and elfgo_own_run_cand (k_playout_own<N, CandPolicy>)
+against the reference's own FindAllCandidateMoves / isSelfAtari (candidates_expected, proven by tests/test_candidates_cpu.py).  Every
 comparison is integer equality; every expected number is computed by the reference at test time, once per process."""
 import ctypes as C
 import os

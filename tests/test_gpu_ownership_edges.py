@@ -171,6 +171,22 @@ def test_slot_switching_on_one_workgroup(six, ids, K):
     assert same(before, snapshot(eng))
 
 
+def test_both_policies_run_one_harness(six):
+    """self_atari_thres = 82 is above 9 * 9, so the candidate policy drops nothing: k_playout_own<N, CandPolicy> must return the
+    counts and stats of k_playout_own<N, EyePolicy>, and the oracle's, bit for bit -- where groups straddle two rows (the
+    geometry rows at K = 3 under every deal) and where every wave changes slot between playouts (the twelve rows on one workgroup)"""
+    eng, E, states = six
+    switching = [LATE, EMPTY, MID, DONE, KO, STEP, EMPTY, MID, LATE, DONE, STEP, MID]
+    cases = [(oe.GEOMETRY_IDS, oe.geometry_seeds(), 3, lanes) for lanes in oe.GEOMETRY_LANES]
+    cases.append((switching, playout_seeds(len(switching), base=3100), 1, 1))
+    for ids, seeds, K, lanes in cases:
+        wc, ws = expected_rows(E, states, ids, seeds, K)
+        eye = run(eng, seeds, ids=ids, playouts=K, max_lanes=lanes)
+        cand = run(eng, seeds, ids=ids, playouts=K, max_lanes=lanes, self_atari_thres=82)
+        for got in (eye, cand):
+            assert np.array_equal(got[0], wc) and np.array_equal(got[1], ws), (K, lanes)
+
+
 def test_record_prefix_decides_the_playout(elf):
     """Sources whose records matter at once: the super-ko game one move short of its end, where about every other playout opens
     with the move that repeats a position of the game's own history (an ending by super-ko after one step -- found only in the

@@ -3,8 +3,8 @@
 (a) 4096 19x19 and 65 536 9x9 playouts from the empty board with playout_seeds: eng.playout (k_playout) and
     eng.playout(self_atari_thres=1 / 5) (k_playout_cand) on the same slots and seeds, alternating: board steps per second and
     mean steps per game of each;
-(b) eng.ownership at 16 ply-120 19x19 positions x 256 playouts, with no threshold (k_playout_own) and with thres 1 / 5
-    (k_playout_own_cand);
+(b) eng.ownership at 16 ply-120 19x19 positions x 256 playouts, with no threshold (k_playout_own<N, EyePolicy>) and with
+    thres 1 / 5 (k_playout_own<N, CandPolicy>);
 (c) eng.candidates beside eng.legal_mask on 4096 19x19 boards at ply 150.
 Times are device events around each call, after a warm-up.  Writes profiles/candidates_bench.json (or the path given as the
 first argument) and prints the same JSON."""
