@@ -5,13 +5,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from conv_cases import elf  # noqa: F401  (the fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def elf(built):
-    import elf_amd
-    return elf_amd
 
 
 @pytest.mark.parametrize("rows,ch", [(1, 8), (361, 256), (5000, 64), (19 * 19 * 37, 256)])

@@ -4,33 +4,20 @@ import ctypes as C
 
 import pytest
 
+import conv_cases as cc
+from conv_cases import elf  # noqa: F401  (the fixture)
+
 pytestmark = pytest.mark.gpu
 
 CH = 256
 ROWS = 2048
-
-
-@pytest.fixture(scope="module")
-def elf(built):
-    import elf_amd
-    return elf_amd
-
+HOW = {0: "algo0", 1: "plain"}     # conv_cases.launch's name of elfnet_conv3x3_f16 with that algo
 
 _cases = {}
 
 
-def _conv_fp32(x, w):
-    """conv2d(x, w, padding=1) in fp32 for NHWC x [rows,n,n,C] and w [K,3,3,C], written out as its nine taps: one fp32 GEMM per tap
-    over the zero-padded input, summed in fp32.  (F.conv2d itself would either search MIOpen's solvers for an fp32 shape nothing
-    else uses or, with MIOpen off, unfold row by row: 45 s for 2048 rows.  _case checks this against it on two rows.)"""
-    import torch
-    rows, n = x.shape[0], x.shape[1]
-    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))
-    out = torch.zeros((rows, n, n, w.shape[0]), device=x.device, dtype=torch.float32)
-    for ky in range(3):
-        for kx in range(3):
-            out += xp[:, ky:ky + n, kx:kx + n, :] @ w[:, ky, kx, :].t()
-    return out
+def _seed(rows, h, wd, c, k):
+    return 1000 + h
 
 
 def _case(n):
@@ -41,14 +28,10 @@ def _case(n):
     The smaller row counts are the first rows of the 2048: a convolution does not mix rows."""
     import torch
     if n not in _cases:
-        g = torch.Generator(device="cuda").manual_seed(1000 + n)
-        x = torch.randn((ROWS, n, n, CH), device="cuda", generator=g).half()                    # NHWC
-        w = (torch.randn((CH, 3, 3, CH), device="cuda", generator=g) * (9 * CH) ** -0.5).half()  # [K,3,3,C]: conv output is O(1)
-        b = torch.randn((CH,), device="cuda", generator=g).half()
-        r = torch.randn((ROWS, n, n, CH), device="cuda", generator=g).half()
+        x, w, b, r = cc.rand_case(_seed(ROWS, n, n, CH, CH), ROWS, n, n, CH, CH)
         with torch.no_grad():
-            pre = _conv_fp32(x.float(), w.float())
-            s0 = _conv_fp32(x.float().abs(), w.float().abs())
+            pre = cc.conv_fp32(x.float(), w.float())
+            s0 = cc.conv_fp32(x.float().abs(), w.float().abs())
             with torch.backends.cudnn.flags(enabled=False):
                 lit = torch.nn.functional.conv2d(x[:2].float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), padding=1)
         # the nine-tap form IS conv2d: against torch's own on two rows, to fp32 accumulation error (2^-24 per product, S0 their sum)
@@ -57,13 +40,6 @@ def _case(n):
         s0 += b.float().abs()
         _cases[n] = dict(x=x, w=w, b=b, r=r, pre=pre, s0=s0)
     return _cases[n]
-
-
-def _run(L, x, w, b, r, y, rows, n, relu, algo, c=CH, k=CH):
-    import torch
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    return L.elfnet_conv3x3_f16(p(x), p(w), p(b), p(r), p(y), rows, n, n, c, k, int(relu), algo,
-                                C.c_void_p(torch.cuda.current_stream().cuda_stream))
 
 
 @pytest.mark.parametrize("algo", [0, 1])
@@ -84,7 +60,7 @@ def test_conv3x3_against_fp32(elf, rows, n, use_res, relu, algo):
     if relu:
         ref = torch.relu(ref)
     y = torch.full((rows, n, n, CH), float("nan"), device="cuda", dtype=torch.float16)
-    rc = _run(elf.lib(), d["x"], d["w"], d["b"], d["r"] if use_res else None, y, rows, n, relu, algo)
+    rc = cc.launch(elf.lib(), HOW[algo], d["x"], d["w"], d["b"], d["r"] if use_res else None, y, relu, shape=(rows, n, n, CH, CH))
     assert rc == 0
     torch.cuda.synchronize()
     err = (y.float() - ref).abs()
@@ -138,7 +114,7 @@ def test_conv3x3_against_the_two_kernel_path(elf):
     bound = 2.0 ** -10 * ref.abs() + 2304 * 2.0 ** -24 * (d["s0"] + r.float().abs())
     for algo in (0, 1):
         y = torch.empty((ROWS, 19, 19, CH), device="cuda", dtype=torch.float16)
-        assert _run(L, x, w, b, r, y, ROWS, 19, 1, algo) == 0
+        assert cc.launch(L, HOW[algo], x, w, b, r, y, 1) == 0
         torch.cuda.synchronize()
         diff = (y.float() - old.float()).abs()
         print("algo %d: %d of %d elements differ from conv2d + elfnet_bias_act_f16, max |diff| %.3e"

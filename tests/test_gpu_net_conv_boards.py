@@ -21,10 +21,11 @@ import ctypes as C
 
 import pytest
 
+import conv_cases as cc
+from conv_cases import ALONE, RES_RELU, elf  # noqa: F401  (elf: the fixture)
+
 pytestmark = pytest.mark.gpu
 
-ALONE = 1 << 30
-RES_RELU = [(False, 0), (False, 1), (True, 0), (True, 1)]
 # (rows, h, w, c, k)
 SHAPES = [(256, 19, 19, 64, 256), (257, 19, 19, 128, 256),
           (256, 9, 9, 192, 256), (300, 9, 9, 64, 512), (513, 9, 9, 128, 256),
@@ -36,55 +37,13 @@ SHAPES = [(256, 19, 19, 64, 256), (257, 19, 19, 128, 256),
 WIDTHS = [1, 2, 3, ALONE]
 
 
-@pytest.fixture(scope="module")
-def elf(built):
-    import elf_amd
-    return elf_amd
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _guarded(rows, h, wd, k):
-    import torch
-    buf = torch.full((rows * h * wd + 1, k), float("nan"), device="cuda", dtype=torch.float16)
-    return buf, buf[:rows * h * wd].view(rows, h, wd, k)
-
-
-def _bits(t):
-    import torch
-    return t.contiguous().view(torch.int16)
+def _seed(rows, h, wd, c, k):
+    return 8191 + rows + 31 * h + 977 * wd + c + 7 * k
 
 
 def _launch(elf, t, use_res, relu, how, width=0):
-    """one launch into a fresh NaN-filled, guarded y.  how: 'board' (forced board order at `width`), 'linear' (algo 1 through
-    elfnet_conv3x3_f16_width), 'algo0', 'plain' (elfnet_conv3x3_f16 with algo 1)"""
-    import torch
-    L = elf.lib()
-    x, w, b = t["x"], t["w"], t["b"]
-    r = t["r"] if use_res else None
-    rows, h, wd, c = x.shape
-    k = w.shape[0]
-    buf, y = _guarded(rows, h, wd, k)
-    a = (_ptr(x), _ptr(w), _ptr(b), _ptr(r), _ptr(y), rows, h, wd, c, k, int(relu))
-    if how == "board":
-        rc = L.elfnet_conv3x3_f16_boards(*a, width, _stream())
-    elif how == "linear":
-        rc = L.elfnet_conv3x3_f16_width(*a, 1, width, _stream())
-    elif how == "algo0":
-        rc = L.elfnet_conv3x3_f16(*a, 0, _stream())
-    else:
-        rc = L.elfnet_conv3x3_f16(*a, 1, _stream())
-    assert rc == 0
-    torch.cuda.synchronize()
-    assert bool(torch.isnan(buf[-1]).all()), "the guard row behind y was written"
-    return y
+    """one launch into a fresh NaN-filled, guarded y (cc.run_guarded; how: cc.launch's)"""
+    return cc.run_guarded(elf.lib(), how, t["x"], t["w"], t["b"], t["r"] if use_res else None, relu, width)
 
 
 _cases = {}
@@ -96,17 +55,13 @@ def _case(elf, rows, h, wd, c, k):
     import torch
     key = (rows, h, wd, c, k)
     if key not in _cases:
-        g = torch.Generator(device="cuda").manual_seed(8191 + rows + 31 * h + 977 * wd + c + 7 * k)
-        t = {"x": torch.randn((rows, h, wd, c), device="cuda", generator=g).half(),
-             "w": (torch.randn((k, 3, 3, c), device="cuda", generator=g) * (9 * c) ** -0.5).half(),
-             "b": torch.randn((k,), device="cuda", generator=g).half(),
-             "r": torch.randn((rows, h, wd, k), device="cuda", generator=g).half(),
-             "ref": {}}
+        x, w, b, r = cc.rand_case(_seed(*key), *key)
+        t = {"x": x, "w": w, "b": b, "r": r, "ref": {}}
         for use_res, relu in RES_RELU:
-            y0 = _launch(elf, t, use_res, relu, "algo0")
+            y0 = cc.algo0_ref(elf.lib(), _seed(*key), key, use_res, relu)
             ya = _launch(elf, t, use_res, relu, "linear", ALONE)
             assert not bool(torch.isnan(y0).any())
-            assert torch.equal(_bits(ya), _bits(y0)), "linear algo 1 with one item per workgroup differs from algo 0"
+            assert torch.equal(cc.bits(ya), cc.bits(y0)), "linear algo 1 with one item per workgroup differs from algo 0"
             t["ref"][(use_res, relu)] = y0
         _cases[key] = t
     return _cases[key]
@@ -153,8 +108,8 @@ def test_board_order_equals_algo0(elf, shape, width, use_res, relu):
     y0 = t["ref"][(use_res, relu)]
     y = _launch(elf, t, use_res, relu, "board", width)
     print("%s width %d res %d relu %d: %d of %d elements differ from algo 0"
-          % (shape, width, use_res, relu, int((_bits(y) != _bits(y0)).sum().item()), y.numel()))
-    assert torch.equal(_bits(y), _bits(y0))
+          % (shape, width, use_res, relu, int((cc.bits(y) != cc.bits(y0)).sum().item()), y.numel()))
+    assert torch.equal(cc.bits(y), cc.bits(y0))
 
 
 # ------------------------------------------------------------------------------------------------ B. the chains of those launches
@@ -204,7 +159,7 @@ def test_every_output_is_the_mask_of_its_position(elf, rows, h, wd, c, width):
     bad = int((y.float() != want).sum().item())
     print("%s c %d width %d: %d of %d differ from the mask integers" % ((rows, h, wd), c, width, bad, y.numel()))
     assert bad == 0
-    assert torch.equal(_bits(y), _bits(_launch(elf, t, False, 0, "algo0")))
+    assert torch.equal(cc.bits(y), cc.bits(_launch(elf, t, False, 0, "algo0")))
 
 
 # ------------------------------------------------------------------------------------------------ D. NaNs stay where they belong
@@ -226,7 +181,7 @@ def test_a_nan_in_x_reaches_its_neighbourhood_on_its_board(elf, shape, board, hh
     isn = torch.isnan(y)
     assert torch.equal(isn.all(dim=3), want) and torch.equal(isn.any(dim=3), want)
     clean = t["ref"][(True, 0)]
-    assert torch.equal(_bits(y[~want]), _bits(clean[~want]))
+    assert torch.equal(cc.bits(y[~want]), cc.bits(clean[~want]))
 
 
 @pytest.mark.parametrize("shape,p", [((257, 5, 7, 64, 256), 0), ((257, 5, 7, 64, 256), 256 * 35 + 34), ((513, 9, 9, 128, 256), 255 * 81 + 80),
@@ -244,7 +199,7 @@ def test_a_nan_row_of_res_stays_in_its_row(elf, shape, p):
     keep = torch.ones(y.shape[0], dtype=torch.bool, device="cuda")
     keep[p] = False
     assert not bool(torch.isnan(y[keep]).any())
-    assert torch.equal(_bits(y[keep]), _bits(clean[keep]))
+    assert torch.equal(cc.bits(y[keep]), cc.bits(clean[keep]))
 
 
 # ------------------------------------------------------------------------------------------------ E. launch against launch
@@ -256,7 +211,7 @@ def test_twenty_launches_are_bit_equal(elf, shape, width):
     y0 = t["ref"][(True, 1)]
     for i in range(20):
         y = _launch(elf, t, True, 1, "board", width)
-        assert torch.equal(_bits(y), _bits(y0)), "launch %d differs from algo 0" % i
+        assert torch.equal(cc.bits(y), cc.bits(y0)), "launch %d differs from algo 0" % i
 
 
 # ------------------------------------------------------------------------------------------------ F. the plain entry
@@ -277,6 +232,6 @@ def test_the_plain_entry_takes_the_order_the_rule_names(elf, shape):
     t = _case(elf, *shape)
     for use_res, relu in RES_RELU:
         y = _launch(elf, t, use_res, relu, "plain")
-        assert torch.equal(_bits(y), _bits(t["ref"][(use_res, relu)]))
+        assert torch.equal(cc.bits(y), cc.bits(t["ref"][(use_res, relu)]))
         yb = _launch(elf, t, use_res, relu, "board", 0)
-        assert torch.equal(_bits(yb), _bits(y))
+        assert torch.equal(cc.bits(yb), cc.bits(y))

@@ -22,35 +22,22 @@ import ctypes as C
 
 import pytest
 
+import conv_cases as cc
+from conv_cases import ALONE, RES_RELU, elf  # noqa: F401  (elf: the fixture)
+
 pytestmark = pytest.mark.gpu
 
-ALONE = 1 << 30
-RES_RELU = [(False, 0), (False, 1), (True, 0), (True, 1)]
 PAD = 16384          # elements of NaN on either side of a cut-out tensor: more than any bias, a multiple of 8 (16-byte alignment)
 
 
-@pytest.fixture(scope="module")
-def elf(built):
-    import elf_amd
-    return elf_amd
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _bits(t):
-    import torch
-    return t.contiguous().view(torch.int16)
+def _seed(rows, h, wd, c, k):
+    return 4099 + rows + 31 * h + 977 * wd + c + 7 * k
 
 
 def _cut(t):
-    """a copy of t in the middle of a NaN-filled allocation; (allocation, view)"""
+    """a copy of t in the middle of a NaN-filled allocation; (allocation, view).  Not cc.carve: that one moves the view to an
+    address that is 16 modulo 32 and allocates `mod` elements more, and here the view starts exactly PAD elements in, at the
+    allocation's own alignment, with exactly PAD behind it."""
     import torch
     buf = torch.full((t.numel() + 2 * PAD,), float("nan"), device="cuda", dtype=torch.float16)
     v = buf[PAD:PAD + t.numel()].view(t.shape)
@@ -58,25 +45,17 @@ def _cut(t):
     return buf, v
 
 
-def _run(elf, x, w, b, r, relu, how, width=0, guard=True):
-    """one launch into a NaN-prefilled y cut out of a NaN-filled allocation; how: 'board', 'linear', 'algo0', 'plain'"""
+def _cut_run(elf, x, w, b, r, relu, how, width=0, guard=True):
+    """one launch (cc.launch's `how`) into a NaN-prefilled y cut out of a NaN-filled allocation, PAD elements on either side (none
+    with guard=False, for the shapes that fill the memory): cc.run_guarded's one guard row behind y is not this"""
     import torch
-    L = elf.lib()
     rows, h, wd, c = x.shape
     k = w.shape[0]
     n = rows * h * wd * k
     pad = PAD if guard else 0
     buf = torch.full((n + 2 * pad,), float("nan"), device="cuda", dtype=torch.float16)
     y = buf[pad:pad + n].view(rows, h, wd, k)
-    a = (_ptr(x), _ptr(w), _ptr(b), _ptr(r), _ptr(y), rows, h, wd, c, k, int(relu))
-    if how == "board":
-        rc = L.elfnet_conv3x3_f16_boards(*a, width, _stream())
-    elif how == "linear":
-        rc = L.elfnet_conv3x3_f16_width(*a, 1, width, _stream())
-    elif how == "algo0":
-        rc = L.elfnet_conv3x3_f16(*a, 0, _stream())
-    else:
-        rc = L.elfnet_conv3x3_f16(*a, 1, _stream())
+    rc = cc.launch(elf.lib(), how, x, w, b, r, y, relu, width)
     assert rc == 0
     torch.cuda.synchronize()
     if guard:
@@ -88,15 +67,12 @@ _cases = {}
 
 
 def _case(elf, rows, h, wd, c, k):
-    """random operands of one shape, cut out of NaN, and algo 0's outputs on plain copies of them: made once, not changed"""
+    """random operands of one shape, cut out of NaN, and algo 0's outputs on plain copies of them: made once, not changed.  (Not
+    cc.algo0_ref: the reference launch keeps its guard regions on both sides of y.)"""
     import torch
     key = (rows, h, wd, c, k)
     if key not in _cases:
-        g = torch.Generator(device="cuda").manual_seed(4099 + rows + 31 * h + 977 * wd + c + 7 * k)
-        x = torch.randn((rows, h, wd, c), device="cuda", generator=g).half()
-        w = (torch.randn((k, 3, 3, c), device="cuda", generator=g) * (9 * c) ** -0.5).half()
-        b = torch.randn((k,), device="cuda", generator=g).half()
-        r = torch.randn((rows, h, wd, k), device="cuda", generator=g).half()
+        x, w, b, r = cc.rand_case(_seed(*key), *key)
         t = {"keep": [], "ref": {}}
         for name, v in (("x", x), ("w", w), ("r", r)):
             buf, cut = _cut(v)
@@ -104,7 +80,7 @@ def _case(elf, rows, h, wd, c, k):
             t[name] = cut
         t["b"] = b
         for use_res, relu in RES_RELU:
-            y0 = _run(elf, x, w, b, r if use_res else None, relu, "algo0")
+            y0 = _cut_run(elf, x, w, b, r if use_res else None, relu, "algo0")
             assert not bool(torch.isnan(y0).any())
             t["ref"][(use_res, relu)] = y0
         _cases[key] = t
@@ -133,7 +109,7 @@ def test_an_out_of_range_lane_writes_zeros_to_lds(elf, lds_offset):
     voff[62] = records - 16 - soff     # the last 16 bytes in range under either reading
     vo = torch.tensor([v - (1 << 32) if v >= 1 << 31 else v for v in voff], dtype=torch.int32, device="cuda")   # the same 32 bits
     out = torch.full((1024,), 0x55, dtype=torch.uint8, device="cuda")
-    assert L.elfnet_conv3x3_f16_bufstage_probe(_ptr(src), records, _ptr(vo), soff, lds_offset, _ptr(out), _stream()) == 0
+    assert L.elfnet_conv3x3_f16_bufstage_probe(cc.ptr(src), records, cc.ptr(vo), soff, lds_offset, cc.ptr(out), cc.stream()) == 0
     torch.cuda.synchronize()
     out = out.cpu().view(64, 16)
     srcc = src.cpu()
@@ -165,11 +141,11 @@ BOARD = [(256, 5, 7, 64, 256), (257, 5, 7, 64, 256), (513, 5, 7, 128, 256), (256
 def test_linear_order_reads_nothing_outside_its_tensors(elf, shape, width, use_res, relu):
     import torch
     t = _case(elf, *shape)
-    y = _run(elf, t["x"], t["w"], t["b"], t["r"] if use_res else None, relu, "linear", width)
+    y = _cut_run(elf, t["x"], t["w"], t["b"], t["r"] if use_res else None, relu, "linear", width)
     y0 = t["ref"][(use_res, relu)]
     print("%s width %d: %d NaN, %d of %d differ from algo 0" % (shape, width, int(torch.isnan(y).sum().item()),
-                                                               int((_bits(y) != _bits(y0)).sum().item()), y.numel()))
-    assert torch.equal(_bits(y), _bits(y0))
+                                                               int((cc.bits(y) != cc.bits(y0)).sum().item()), y.numel()))
+    assert torch.equal(cc.bits(y), cc.bits(y0))
 
 
 @pytest.mark.parametrize("use_res,relu", RES_RELU)
@@ -178,11 +154,11 @@ def test_linear_order_reads_nothing_outside_its_tensors(elf, shape, width, use_r
 def test_board_order_reads_nothing_outside_its_tensors(elf, shape, width, use_res, relu):
     import torch
     t = _case(elf, *shape)
-    y = _run(elf, t["x"], t["w"], t["b"], t["r"] if use_res else None, relu, "board", width)
+    y = _cut_run(elf, t["x"], t["w"], t["b"], t["r"] if use_res else None, relu, "board", width)
     y0 = t["ref"][(use_res, relu)]
     print("%s width %d: %d NaN, %d of %d differ from algo 0" % (shape, width, int(torch.isnan(y).sum().item()),
-                                                               int((_bits(y) != _bits(y0)).sum().item()), y.numel()))
-    assert torch.equal(_bits(y), _bits(y0))
+                                                               int((cc.bits(y) != cc.bits(y0)).sum().item()), y.numel()))
+    assert torch.equal(cc.bits(y), cc.bits(y0))
 
 
 # ------------------------------------------------------------------------------------------------ C. exact integers
@@ -201,11 +177,11 @@ def test_all_ones_give_the_count_of_taps_on_the_board(elf, rows, h, wd, c, how, 
         for ww in range(wd):
             want[hh, ww] = sum(1 for ky in range(3) for kx in range(3) if 0 <= hh + ky - 1 < h and 0 <= ww + kx - 1 < wd)
     want = want.cuda()[None, :, :, None].expand(rows, h, wd, k)
-    y = _run(elf, x, w, b, None, 0, how, width)
+    y = _cut_run(elf, x, w, b, None, 0, how, width)
     bad = int((y.float() != want).sum().item())
     print("%s c %d %s width %d: %d of %d differ from the tap counts" % ((rows, h, wd), c, how, width, bad, y.numel()))
     assert bad == 0
-    assert torch.equal(_bits(y), _bits(_run(elf, x, w, b, None, 0, "algo0")))
+    assert torch.equal(cc.bits(y), cc.bits(_cut_run(elf, x, w, b, None, 0, "algo0")))
 
 
 # ------------------------------------------------------------------------------------------------ D. chains
@@ -224,8 +200,8 @@ def test_a_chain_of_items_on_one_workgroup(elf, c, k, width, how, use_res, relu)
         tiles = (rows * h * wd + 255) // 256
         assert L.elfnet_conv3x3_f16_plan(tiles, k // 256, width, 0, None, None, None) >= 5 * L.elfnet_conv3x3_f16_grid(tiles, k // 256, width)
     t = _case(elf, rows, h, wd, c, k)
-    y = _run(elf, t["x"], t["w"], t["b"], t["r"] if use_res else None, relu, how, width)
-    assert torch.equal(_bits(y), _bits(t["ref"][(use_res, relu)]))
+    y = _cut_run(elf, t["x"], t["w"], t["b"], t["r"] if use_res else None, relu, how, width)
+    assert torch.equal(cc.bits(y), cc.bits(t["ref"][(use_res, relu)]))
 
 
 # ------------------------------------------------------------------------------------------------ E. offsets up to 2^31
@@ -242,13 +218,13 @@ def test_the_largest_shape_the_entry_accepts(elf):
     x = torch.empty((rows, h, wd, c), device="cuda", dtype=torch.float16).normal_(generator=g)
     w = (torch.randn((k, 3, 3, c), device="cuda", generator=g) * (9 * c) ** -0.5).half()
     b = torch.randn((k,), device="cuda", generator=g).half()
-    y0 = _run(elf, x, w, b, None, 1, "algo0", guard=False)
+    y0 = _cut_run(elf, x, w, b, None, 1, "algo0", guard=False)
     assert not bool(torch.isnan(y0[-1]).any()) and bool((y0[-1] != 0).any())
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     assert cus > 0
     for how, width in (("linear", cus), ("linear", ALONE), ("board", 0), ("plain", 0)):
-        y = _run(elf, x, w, b, None, 1, how, width, guard=False)
-        same = torch.equal(_bits(y), _bits(y0))
+        y = _cut_run(elf, x, w, b, None, 1, how, width, guard=False)
+        same = torch.equal(cc.bits(y), cc.bits(y0))
         print("%s width %d: equal to algo 0: %s" % (how, width, same))
         assert same, (how, width)
         del y
@@ -266,8 +242,8 @@ def test_twenty_launches_of_the_headline_shape(elf):
     w = (torch.randn((k, 3, 3, c), device="cuda", generator=g) * (9 * c) ** -0.5).half()
     b = torch.randn((k,), device="cuda", generator=g).half()
     r = torch.empty((rows, h, wd, k), device="cuda", dtype=torch.float16).normal_(generator=g)
-    y0 = _run(elf, x, w, b, r, 1, "algo0", guard=False)
+    y0 = _cut_run(elf, x, w, b, r, 1, "algo0", guard=False)
     for i in range(20):
-        y = _run(elf, x, w, b, r, 1, "plain", guard=False)
-        assert torch.equal(_bits(y), _bits(y0)), "launch %d differs from algo 0" % i
+        y = _cut_run(elf, x, w, b, r, 1, "plain", guard=False)
+        assert torch.equal(cc.bits(y), cc.bits(y0)), "launch %d differs from algo 0" % i
     torch.cuda.empty_cache()

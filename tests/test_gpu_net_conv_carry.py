@@ -21,47 +21,19 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import conv_cases as cc
+from conv_cases import ALONE, RES_RELU, elf  # noqa: F401  (elf: the fixture)
+
 pytestmark = pytest.mark.gpu
 
-ALONE = 1 << 30                      # round width: every item has a workgroup of its own
-RES_RELU = [(False, 0), (False, 1), (True, 0), (True, 1)]
+
+def _seed(rows, h, wd, c, k):
+    return 4099 + rows + 31 * h + 977 * wd + c + 7 * k
 
 
-@pytest.fixture(scope="module")
-def elf(built):
-    import elf_amd
-    return elf_amd
-
-
-def _run(L, x, w, b, r, y, rows, h, wd, c, k, relu, algo, width):
-    import torch
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    return L.elfnet_conv3x3_f16_width(p(x), p(w), p(b), p(r), p(y), rows, h, wd, c, k, int(relu), algo, width, st)
-
-
-def _guarded(rows, h, wd, k):
-    import torch
-    buf = torch.full((rows * h * wd + 1, k), float("nan"), device="cuda", dtype=torch.float16)
-    return buf, buf[:rows * h * wd].view(rows, h, wd, k)
-
-
-def _bits(t):
-    import torch
-    return t.contiguous().view(torch.int16)
-
-
-def _launch(elf, t, use_res, relu, algo, width):
-    """one launch into a fresh NaN-filled, guarded y"""
-    import torch
-    x, w, b, r = t["x"], t["w"], t["b"], t["r"]
-    rows, h, wd, c = x.shape
-    k = w.shape[0]
-    buf, y = _guarded(rows, h, wd, k)
-    assert _run(elf.lib(), x, w, b, r if use_res else None, y, rows, h, wd, c, k, relu, algo, width) == 0
-    torch.cuda.synchronize()
-    assert bool(torch.isnan(buf[-1]).all()), "the guard row behind y was written"
-    return y
+def _launch(elf, t, use_res, relu, how, width=0):
+    """one launch into a fresh NaN-filled, guarded y (cc.run_guarded; how: 'algo0', or 'linear' at `width`)"""
+    return cc.run_guarded(elf.lib(), how, t["x"], t["w"], t["b"], t["r"] if use_res else None, relu, width)
 
 
 _cases = {}
@@ -72,17 +44,13 @@ def _case(elf, rows, h, wd, c, k):
     import torch
     key = (rows, h, wd, c, k)
     if key not in _cases:
-        g = torch.Generator(device="cuda").manual_seed(4099 + rows + 31 * h + 977 * wd + c + 7 * k)
-        t = {"x": torch.randn((rows, h, wd, c), device="cuda", generator=g).half(),
-             "w": (torch.randn((k, 3, 3, c), device="cuda", generator=g) * (9 * c) ** -0.5).half(),
-             "b": torch.randn((k,), device="cuda", generator=g).half(),
-             "r": torch.randn((rows, h, wd, k), device="cuda", generator=g).half(),
-             "ref": {}}
+        x, w, b, r = cc.rand_case(_seed(*key), *key)
+        t = {"x": x, "w": w, "b": b, "r": r, "ref": {}}
         for use_res, relu in RES_RELU:
-            y0 = _launch(elf, t, use_res, relu, 0, 0)
-            ya = _launch(elf, t, use_res, relu, 1, ALONE)
+            y0 = cc.algo0_ref(elf.lib(), _seed(*key), key, use_res, relu)
+            ya = cc.cached_ref(elf.lib(), "linear", _seed(*key), key, use_res, relu, ALONE)
             assert not bool(torch.isnan(y0).any())
-            assert torch.equal(_bits(ya), _bits(y0)), "algo 1 with one item per workgroup differs from algo 0"
+            assert torch.equal(cc.bits(ya), cc.bits(y0)), "algo 1 with one item per workgroup differs from algo 0"
             t["ref"][(use_res, relu)] = (y0, ya)
         _cases[key] = t
     return _cases[key]
@@ -92,12 +60,12 @@ def _check(elf, shape, width, use_res, relu):
     import torch
     t = _case(elf, *shape)
     y0, ya = t["ref"][(use_res, relu)]
-    y = _launch(elf, t, use_res, relu, 1, width)
+    y = _launch(elf, t, use_res, relu, "linear", width)
     print("%s width %d res %d relu %d: %d of %d elements differ from algo 0, %d from one item per workgroup"
-          % (shape, width, use_res, relu, int((_bits(y) != _bits(y0)).sum().item()), y.numel(),
-             int((_bits(y) != _bits(ya)).sum().item())))
-    assert torch.equal(_bits(y), _bits(y0))
-    assert torch.equal(_bits(y), _bits(ya))
+          % (shape, width, use_res, relu, int((cc.bits(y) != cc.bits(y0)).sum().item()), y.numel(),
+             int((cc.bits(y) != cc.bits(ya)).sum().item())))
+    assert torch.equal(cc.bits(y), cc.bits(y0))
+    assert torch.equal(cc.bits(y), cc.bits(ya))
 
 
 # ------------------------------------------------------------------------------------------------ A. chains and K-tile parity
@@ -166,16 +134,16 @@ def test_a_nan_in_x_stays_in_its_item(elf, c, item, first, use_res, relu):
     else:
         xf[256 * item + 255, c - 1] = float("nan")
     t["x"] = x
-    y = _launch(elf, t, use_res, relu, 1, 1).view(5, 256, 256)
-    y0 = _launch(elf, t, use_res, relu, 0, 0).view(5, 256, 256)
+    y = _launch(elf, t, use_res, relu, "linear", 1).view(5, 256, 256)
+    y0 = _launch(elf, t, use_res, relu, "algo0").view(5, 256, 256)
     nan_tiles = [bool(torch.isnan(y[i]).any()) for i in range(5)]
     print("c %d item %d first %d res %d: tiles with a NaN %s" % (c, item, first, use_res, nan_tiles))
     assert nan_tiles == [i == item for i in range(5)]
-    assert torch.equal(_bits(y), _bits(y0))
+    assert torch.equal(cc.bits(y), cc.bits(y0))
     clean = t["ref"][(use_res, relu)][0].view(5, 256, 256)
     for i in range(5):
         if i != item:
-            assert torch.equal(_bits(y[i]), _bits(clean[i])), "tile %d changed" % i
+            assert torch.equal(cc.bits(y[i]), cc.bits(clean[i])), "tile %d changed" % i
 
 
 @pytest.mark.parametrize("c", [64, 128])
@@ -186,13 +154,13 @@ def test_a_nan_row_of_res_stays_in_its_row(elf, c, p):
     r = t["r"].clone()
     r.view(1280, 256)[p, :] = float("nan")
     t["r"] = r
-    y = _launch(elf, t, True, 0, 1, 1).view(1280, 256)
+    y = _launch(elf, t, True, 0, "linear", 1).view(1280, 256)
     clean = t["ref"][(True, 0)][0].view(1280, 256)
     assert bool(torch.isnan(y[p]).all())
     keep = torch.ones(1280, dtype=torch.bool, device="cuda")
     keep[p] = False
     assert not bool(torch.isnan(y[keep]).any())
-    assert torch.equal(_bits(y[keep]), _bits(clean[keep]))
+    assert torch.equal(cc.bits(y[keep]), cc.bits(clean[keep]))
 
 
 @pytest.mark.parametrize("c", [64, 192])
@@ -207,12 +175,12 @@ def test_all_ones_count_the_taps_of_their_own_item(elf, rows, h, wd, c):
     rowc = np.array([(i > 0) + 1 + (i < h - 1) for i in range(h)])
     colc = np.array([(j > 0) + 1 + (j < wd - 1) for j in range(wd)])
     taps = torch.from_numpy((c * rowc[:, None] * colc[None, :]).astype(np.float32)).cuda()[None, :, :, None].expand(rows, h, wd, k)
-    y = _launch(elf, t, False, 0, 1, 1)
-    y0 = _launch(elf, t, False, 0, 0, 0)
+    y = _launch(elf, t, False, 0, "linear", 1)
+    y0 = _launch(elf, t, False, 0, "algo0")
     bad = int((y.float() != taps).sum().item())
     print("%s c %d: %d of %d differ from the nine-tap integers" % ((rows, h, wd), c, bad, y.numel()))
     assert bad == 0
-    assert torch.equal(_bits(y), _bits(y0))
+    assert torch.equal(cc.bits(y), cc.bits(y0))
 
 
 # ------------------------------------------------------------------------------------------------ E. launch against launch
@@ -223,5 +191,5 @@ def test_twenty_launches_are_bit_equal(elf, shape, width):
     t = _case(elf, *shape)
     y0 = t["ref"][(True, 1)][0]
     for i in range(20):
-        y = _launch(elf, t, True, 1, 1, width)
-        assert torch.equal(_bits(y), _bits(y0)), "launch %d differs from algo 0" % i
+        y = _launch(elf, t, True, 1, "linear", width)
+        assert torch.equal(cc.bits(y), cc.bits(y0)), "launch %d differs from algo 0" % i

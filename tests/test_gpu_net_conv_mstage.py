@@ -10,32 +10,23 @@ import ctypes as C
 
 import pytest
 
+import conv_cases as cc
+from conv_cases import elf  # noqa: F401  (the fixture)
+
 pytestmark = pytest.mark.gpu
 
 F, H0, H1 = -1, 0, 1
 
 
-@pytest.fixture(scope="module")
-def elf(built):
-    import elf_amd
-    return elf_amd
+def _seed(rows, h, wd, c, k):
+    return 6262 + rows + 31 * h + 977 * wd + c + 7 * k
 
 
-def _run(L, x, w, b, r, y, rows, h, wd, c, k, relu, algo, width=None):
-    """width None: elfnet_conv3x3_f16 (the device's own round width); otherwise elfnet_conv3x3_f16_width"""
-    import torch
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def _launch(L, x, w, b, r, y, relu, width=None):
+    """algo 1; width None: elfnet_conv3x3_f16 (the device's own round width); otherwise elfnet_conv3x3_f16_width"""
     if width is None:
-        return L.elfnet_conv3x3_f16(p(x), p(w), p(b), p(r), p(y), rows, h, wd, c, k, int(relu), algo, st)
-    return L.elfnet_conv3x3_f16_width(p(x), p(w), p(b), p(r), p(y), rows, h, wd, c, k, int(relu), algo, width, st)
-
-
-def _guarded(rows, h, wd, k):
-    """y prefilled with NaN, and one guard row of NaN behind its last row"""
-    import torch
-    buf = torch.full((rows * h * wd + 1, k), float("nan"), device="cuda", dtype=torch.float16)
-    return buf, buf[:rows * h * wd].view(rows, h, wd, k)
+        return cc.launch(L, "plain", x, w, b, r, y, relu)
+    return cc.launch(L, "linear", x, w, b, r, y, relu, width)
 
 
 def _kinds(L, rows, h, wd, k, width):
@@ -54,46 +45,13 @@ def _kinds(L, rows, h, wd, k, width):
     return out
 
 
-_rand = {}
-
-
-def _rand_case(rows, h, wd, c, k):
-    """drawn once per shape and left unchanged"""
-    import torch
-    key = (rows, h, wd, c, k)
-    if key not in _rand:
-        g = torch.Generator(device="cuda").manual_seed(6262 + rows + 31 * h + 977 * wd + c + 7 * k)
-        x = torch.randn((rows, h, wd, c), device="cuda", generator=g).half()
-        w = (torch.randn((k, 3, 3, c), device="cuda", generator=g) * (9 * c) ** -0.5).half()
-        b = torch.randn((k,), device="cuda", generator=g).half()
-        r = torch.randn((rows, h, wd, k), device="cuda", generator=g).half()
-        _rand[key] = (x, w, b, r)
-    return _rand[key]
-
-
-_ref = {}
-
-
-def _algo0(elf, rows, h, wd, c, k, use_res, relu):
-    """algo 0's output; computed once per case"""
-    import torch
-    key = (rows, h, wd, c, k, use_res, relu)
-    if key not in _ref:
-        x, w, b, r = _rand_case(rows, h, wd, c, k)
-        y = torch.full((rows, h, wd, k), float("nan"), device="cuda", dtype=torch.float16)
-        assert _run(elf.lib(), x, w, b, r if use_res else None, y, rows, h, wd, c, k, relu, 0) == 0
-        torch.cuda.synchronize()
-        assert not bool(torch.isnan(y).any())
-        _ref[key] = y
-    return _ref[key]
-
-
 def _check_against_algo0(elf, rows, h, wd, c, k, use_res, relu, width):
     import torch
-    x, w, b, res = _rand_case(rows, h, wd, c, k)
-    want = _algo0(elf, rows, h, wd, c, k, use_res, relu)
-    buf, y = _guarded(rows, h, wd, k)
-    assert _run(elf.lib(), x, w, b, res if use_res else None, y, rows, h, wd, c, k, relu, 1, width) == 0
+    shape = (rows, h, wd, c, k)
+    x, w, b, res = cc.rand_case(_seed(*shape), *shape)
+    want = cc.algo0_ref(elf.lib(), _seed(*shape), shape, use_res, relu)
+    buf, y = cc.guarded(rows, h, wd, k)
+    assert _launch(elf.lib(), x, w, b, res if use_res else None, y, relu, width) == 0
     torch.cuda.synchronize()
     print("%s width %s res %d relu %d: %d of %d elements differ from algo 0"
           % ((rows, h, wd, c, k), width, use_res, relu, int((y != want).sum().item()), y.numel()))
@@ -143,13 +101,13 @@ def test_repeated_launches(elf, width):
     (width 2 of 2 items: no split) again one each through the explicit entry.  20 launches into fresh NaN-filled outputs: the first is
     algo 0's, every later one the first's.  A half-tile read before it has landed gives tiles that come and go."""
     import torch
-    rows, h, wd, c, k = 4, 9, 9, 64, 256
-    x, w, b, r = _rand_case(rows, h, wd, c, k)
-    want = _algo0(elf, rows, h, wd, c, k, True, 1)
+    shape = rows, h, wd, c, k = 4, 9, 9, 64, 256
+    x, w, b, r = cc.rand_case(_seed(*shape), *shape)
+    want = cc.algo0_ref(elf.lib(), _seed(*shape), shape, True, 1)
     first = None
     for i in range(20):
         y = torch.full((rows, h, wd, k), float("nan"), device="cuda", dtype=torch.float16)
-        assert _run(elf.lib(), x, w, b, r, y, rows, h, wd, c, k, 1, 1, width) == 0
+        assert _launch(elf.lib(), x, w, b, r, y, 1, width) == 0
         torch.cuda.synchronize()
         if first is None:
             first = y
@@ -165,22 +123,13 @@ def test_non_square_board_exact_integers(elf):
     import torch
     rows, h, wd, c, k, width = 7, 5, 37, 128, 256, 2
     assert _kinds(elf.lib(), rows, h, wd, k, width) == [[F] * 3] * 2
-    g = torch.Generator(device="cuda").manual_seed(4711)
-    ri = lambda shape, lo, hi: torch.randint(lo, hi + 1, shape, device="cuda", generator=g)
-    x = ri((rows, h, wd, c), -1, 1).half()
-    w = (ri((k, 3, 3, c), -1, 1) * (ri((k, 3, 3, c), 0, 3) == 0)).half()
-    b = ri((k,), -8, 8).half()
-    r = ri((rows, h, wd, k), -8, 8).half()
+    d = cc.int_case(4711, rows, h, wd, c, k)      # this one case has a seed of its own
+    x, w, b, r, conv = d["x"], d["w"], d["b"], d["r"], d["conv"]
     assert not torch.equal(w, w.flip(1)) and not torch.equal(w, w.flip(2))
-    xp = torch.nn.functional.pad(x.float(), (0, 0, 1, 1, 1, 1))
-    conv = torch.zeros((rows, h, wd, k), device="cuda", dtype=torch.float32)
-    for ky in range(3):
-        for kx in range(3):
-            conv += xp[:, ky:ky + h, kx:kx + wd, :] @ w[:, ky, kx, :].float().t()
     assert conv.abs().max().item() < 1024
     ref = torch.relu(conv + b.float() + r.float())
-    buf, y = _guarded(rows, h, wd, k)
-    assert _run(elf.lib(), x, w, b, r, y, rows, h, wd, c, k, 1, 1, width) == 0
+    buf, y = cc.guarded(rows, h, wd, k)
+    assert _launch(elf.lib(), x, w, b, r, y, 1, width) == 0
     torch.cuda.synchronize()
     bad = int((y.float() != ref).sum().item())   # a NaN left in y differs from everything
     print("5 x 37: %d of %d differ" % (bad, y.numel()))

@@ -2,59 +2,20 @@
 is exact -- small integers, so every partial sum is an integer fp32 and fp16 hold exactly and any differing element is a wrong
 halo, layout, swizzle or pipeline timing, never rounding -- then bit for bit against algo 0 (same K order, same MFMA), a race
 screen (repeated launches return the bits of the first), and the shapes it refuses."""
-import ctypes as C
-
 import pytest
+
+import conv_cases as cc
+from conv_cases import elf  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-ALGO = 1
+
+def _seed(rows, h, wd, c, k):
+    return 77 + rows + 1000 * h + c + 7 * k
 
 
-@pytest.fixture(scope="module")
-def elf(built):
-    import elf_amd
-    return elf_amd
-
-
-def _conv_fp32(x, w):
-    """conv2d(x, w, padding=1) in fp32 for NHWC x [rows,h,w,C] and w [K,3,3,C] as its nine taps (test_gpu_net_conv._conv_fp32)"""
-    import torch
-    rows, h, wd = x.shape[0], x.shape[1], x.shape[2]
-    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))
-    out = torch.zeros((rows, h, wd, w.shape[0]), device=x.device, dtype=torch.float32)
-    for ky in range(3):
-        for kx in range(3):
-            out += xp[:, ky:ky + h, kx:kx + wd, :] @ w[:, ky, kx, :].t()
-    return out
-
-
-def _run(L, x, w, b, r, y, rows, n, relu, algo, c, k):
-    import torch
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    return L.elfnet_conv3x3_f16(p(x), p(w), p(b), p(r), p(y), rows, n, n, c, k, int(relu), algo,
-                                C.c_void_p(torch.cuda.current_stream().cuda_stream))
-
-
-_ints = {}
-
-
-def _int_case(rows, n, c, k):
-    """x in {-1,0,1}; w in {-1,0,1} with about 3/4 zeros, drawn per element so it is asymmetric in (k,c) and in (ky,kx); integer
-    bias and res.  |partial sum| <= 9 c / 4 + spread, far below 2048, |result| below 2048: exact in fp32 and in fp16."""
-    import torch
-    key = (rows, n, c, k)
-    if key not in _ints:
-        g = torch.Generator(device="cuda").manual_seed(77 + rows + 1000 * n + c + 7 * k)
-        ri = lambda shape, lo, hi: torch.randint(lo, hi + 1, shape, device="cuda", generator=g)
-        x = ri((rows, n, n, c), -1, 1).half()
-        w = (ri((k, 3, 3, c), -1, 1) * (ri((k, 3, 3, c), 0, 3) == 0)).half()
-        b = ri((k,), -8, 8).half()
-        r = ri((rows, n, n, k), -8, 8).half()
-        conv = _conv_fp32(x.float(), w.float())
-        assert conv.abs().max().item() < 1024 and not torch.equal(w, w.flip(1)) and not torch.equal(w, w.flip(2))
-        _ints[key] = dict(x=x, w=w, b=b, r=r, conv=conv)
-    return _ints[key]
+def _rseed(rows, h, wd, c, k):
+    return 4242 + rows
 
 
 @pytest.mark.parametrize("relu", [0, 1])
@@ -69,15 +30,14 @@ def test_exact_integers(elf, rows, n, c, k, use_res, relu):
     """equality with the nine-tap fp32 form; y is prefilled with NaN, and one guard row of NaN behind y's last row stays NaN (the
     tail tile's stores are masked)"""
     import torch
-    d = _int_case(rows, n, c, k)
+    d = cc.int_case(_seed(rows, n, n, c, k), rows, n, n, c, k)
     ref = d["conv"] + d["b"].float()
     if use_res:
         ref = ref + d["r"].float()
     if relu:
         ref = torch.relu(ref)
-    buf = torch.full((rows * n * n + 1, k), float("nan"), device="cuda", dtype=torch.float16)
-    y = buf[:rows * n * n].view(rows, n, n, k)
-    rc = _run(elf.lib(), d["x"], d["w"], d["b"], d["r"] if use_res else None, y, rows, n, relu, ALGO, c, k)
+    buf, y = cc.guarded(rows, n, n, k)
+    rc = cc.launch(elf.lib(), "plain", d["x"], d["w"], d["b"], d["r"] if use_res else None, y, relu)
     assert rc == 0
     torch.cuda.synchronize()
     bad = int((y.float() != ref).sum().item())   # a NaN left in y differs from everything
@@ -95,7 +55,7 @@ def test_all_ones_halo(elf, n):
     w = torch.ones((ch, 3, 3, ch), device="cuda", dtype=torch.float16)
     b = torch.zeros((ch,), device="cuda", dtype=torch.float16)
     y = torch.full((rows, n, n, ch), float("nan"), device="cuda", dtype=torch.float16)
-    assert _run(elf.lib(), x, w, b, None, y, rows, n, 0, ALGO, ch, ch) == 0
+    assert cc.launch(elf.lib(), "plain", x, w, b, None, y, 0) == 0
     torch.cuda.synchronize()
     i = torch.arange(n, device="cuda")
     on = 3 - ((i == 0) | (i == n - 1)).long()           # taps on the board along one axis
@@ -104,33 +64,17 @@ def test_all_ones_halo(elf, n):
     assert bool((y.float() == want[None, :, :, None]).all())
 
 
-_rand = {}
-
-
-def _rand_case(rows):
-    import torch
-    if rows not in _rand:
-        g = torch.Generator(device="cuda").manual_seed(4242 + rows)
-        n, ch = 19, 256
-        x = torch.randn((rows, n, n, ch), device="cuda", generator=g).half()
-        w = (torch.randn((ch, 3, 3, ch), device="cuda", generator=g) * (9 * ch) ** -0.5).half()
-        b = torch.randn((ch,), device="cuda", generator=g).half()
-        r = torch.randn((rows, n, n, ch), device="cuda", generator=g).half()
-        _rand[rows] = (x, w, b, r)
-    return _rand[rows]
-
-
 def test_bit_equal_with_algo_0(elf):
     """rows 48 x 19 x 19 with skip: the shipped kernel keeps algo 0's accumulation chain (tap-major K; in every 32-channel block
     one 32x32x16 MFMA over channels {0..7, 16..23}, the next over {8..15, 24..31}, as CK hands them out) and its epilogue
     sequence, so the two outputs are the same bits"""
     import torch
     rows = 48
-    x, w, b, r = _rand_case(rows)
+    x, w, b, r = cc.rand_case(_rseed(rows, 19, 19, 256, 256), rows, 19, 19, 256, 256)
     ys = []
-    for algo in (0, 1):
+    for how in ("algo0", "plain"):
         y = torch.full((rows, 19, 19, 256), float("nan"), device="cuda", dtype=torch.float16)
-        assert _run(elf.lib(), x, w, b, r, y, rows, 19, 1, algo, 256, 256) == 0
+        assert cc.launch(elf.lib(), how, x, w, b, r, y, 1) == 0
         ys.append(y)
     torch.cuda.synchronize()
     print("%d of %d elements differ between algo 1 and algo 0" % (int((ys[0] != ys[1]).sum().item()), ys[0].numel()))
@@ -143,11 +87,11 @@ def test_repeated_launches_return_the_same_bits(elf, rows, launches):
     same inputs launched again and again return the bits of the first launch; at 2048 rows every CU is busy for 11 rounds, which
     is where a read placed too early shows."""
     import torch
-    x, w, b, r = _rand_case(rows)
+    x, w, b, r = cc.rand_case(_rseed(rows, 19, 19, 256, 256), rows, 19, 19, 256, 256)
     first = None
     for i in range(launches):
         y = torch.full((rows, 19, 19, 256), float("nan"), device="cuda", dtype=torch.float16)
-        assert _run(elf.lib(), x, w, b, r, y, rows, 19, 1, ALGO, 256, 256) == 0
+        assert cc.launch(elf.lib(), "plain", x, w, b, r, y, 1) == 0
         torch.cuda.synchronize()
         if first is None:
             first = y
@@ -165,6 +109,6 @@ def test_unsupported_shapes_are_refused(elf, c, k):
     w = torch.zeros((k, 3, 3, c), device="cuda", dtype=torch.float16)
     b = torch.zeros((k,), device="cuda", dtype=torch.float16)
     y = torch.full((rows, n, n, k), 7.0, device="cuda", dtype=torch.float16)
-    assert _run(elf.lib(), x, w, b, None, y, rows, n, 0, ALGO, c, k) < 0
+    assert cc.launch(elf.lib(), "plain", x, w, b, None, y, 0) < 0
     torch.cuda.synchronize()
     assert bool((y == 7.0).all())

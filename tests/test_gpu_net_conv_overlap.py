@@ -9,29 +9,18 @@ import ctypes as C
 
 import pytest
 
+import conv_cases as cc
+from conv_cases import elf  # noqa: F401  (the fixture)
+
 pytestmark = pytest.mark.gpu
 
-NEVER = 1 << 30   # a round wider than any launch here: one item per workgroup, never split
+
+def _seed(rows, h, wd, c, k):
+    return 99 + rows + 1000 * h + 31 * wd + c + 7 * k
 
 
-@pytest.fixture(scope="module")
-def elf(built):
-    import elf_amd
-    return elf_amd
-
-
-def _run(L, x, w, b, r, y, rows, h, wd, c, k, relu, algo, width):
-    import torch
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    return L.elfnet_conv3x3_f16_width(p(x), p(w), p(b), p(r), p(y), rows, h, wd, c, k, int(relu), algo, width,
-                                      C.c_void_p(torch.cuda.current_stream().cuda_stream))
-
-
-def _guarded(rows, h, wd, k):
-    """y prefilled with NaN, and one guard row of NaN behind its last row"""
-    import torch
-    buf = torch.full((rows * h * wd + 1, k), float("nan"), device="cuda", dtype=torch.float16)
-    return buf, buf[:rows * h * wd].view(rows, h, wd, k)
+def _rseed(rows, h, wd, c, k):
+    return 5151 + rows + 31 * h + 977 * wd + c + 7 * k
 
 
 def _chains(L, rows, h, wd, k, width):
@@ -50,38 +39,12 @@ def _chains(L, rows, h, wd, k, width):
     return out
 
 
-_rand = {}
-
-
-def _rand_case(rows, h, wd, c, k):
-    """test_gpu_net_conv_tail._rand_case's recipe; drawn once per shape and left unchanged"""
-    import torch
-    key = (rows, h, wd, c, k)
-    if key not in _rand:
-        g = torch.Generator(device="cuda").manual_seed(5151 + rows + 31 * h + 977 * wd + c + 7 * k)
-        x = torch.randn((rows, h, wd, c), device="cuda", generator=g).half()
-        w = (torch.randn((k, 3, 3, c), device="cuda", generator=g) * (9 * c) ** -0.5).half()
-        b = torch.randn((k,), device="cuda", generator=g).half()
-        r = torch.randn((rows, h, wd, k), device="cuda", generator=g).half()
-        _rand[key] = (x, w, b, r)
-    return _rand[key]
-
-
-_ref = {}
-
-
 def _reference(elf, rows, h, wd, c, k, use_res, relu, algo):
-    """algo 0's output, or algo 1's with one item per workgroup; computed once per case"""
-    import torch
-    key = (rows, h, wd, c, k, use_res, relu, algo)
-    if key not in _ref:
-        x, w, b, r = _rand_case(rows, h, wd, c, k)
-        y = torch.full((rows, h, wd, k), float("nan"), device="cuda", dtype=torch.float16)
-        assert _run(elf.lib(), x, w, b, r if use_res else None, y, rows, h, wd, c, k, relu, algo, NEVER) == 0
-        torch.cuda.synchronize()
-        assert not bool(torch.isnan(y).any())
-        _ref[key] = y
-    return _ref[key]
+    """algo 0's output, or algo 1's with one item per workgroup (cc.ALONE); computed once per case"""
+    shape = (rows, h, wd, c, k)
+    if algo == 0:
+        return cc.algo0_ref(elf.lib(), _rseed(*shape), shape, use_res, relu)
+    return cc.cached_ref(elf.lib(), "linear", _rseed(*shape), shape, use_res, relu, cc.ALONE)
 
 
 F, H0, H1 = -1, 0, 1
@@ -107,9 +70,9 @@ def test_chains_are_bit_equal_with_algo_0_and_with_one_item_per_workgroup(elf, r
     if (rows, k, width) == (3, 512, 3):
         # workgroup 1: ids 1, 4, 7 (and the half id 10); id 4 is the partial tile of column 0, id 7 a full tile of column 1
         assert chains[1][:3] == [(1, 0, F), (4, 0, F), (2, 1, F)]
-    x, w, b, res = _rand_case(rows, h, wd, c, k)
-    buf, y = _guarded(rows, h, wd, k)
-    assert _run(L, x, w, b, res if use_res else None, y, rows, h, wd, c, k, relu, 1, width) == 0
+    x, w, b, res = cc.rand_case(_rseed(rows, h, wd, c, k), rows, h, wd, c, k)
+    buf, y = cc.guarded(rows, h, wd, k)
+    assert cc.launch(L, "linear", x, w, b, res if use_res else None, y, relu, width) == 0
     torch.cuda.synchronize()
     for name, algo in (("algo 0", 0), ("algo 1, one item per workgroup", 1)):
         want = _reference(elf, rows, h, wd, c, k, use_res, relu, algo)
@@ -117,39 +80,6 @@ def test_chains_are_bit_equal_with_algo_0_and_with_one_item_per_workgroup(elf, r
               % ((rows, h, wd, c, k), width, use_res, relu, int((y != want).sum().item()), y.numel(), name))
         assert torch.equal(y, want), name
     assert bool(torch.isnan(buf[-1]).all())
-
-
-def _conv_fp32(x, w):
-    """conv2d(x, w, padding=1) in fp32 for NHWC x [rows,h,w,C] and w [K,3,3,C] as its nine taps"""
-    import torch
-    rows, h, wd = x.shape[0], x.shape[1], x.shape[2]
-    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))
-    out = torch.zeros((rows, h, wd, w.shape[0]), device=x.device, dtype=torch.float32)
-    for ky in range(3):
-        for kx in range(3):
-            out += xp[:, ky:ky + h, kx:kx + wd, :] @ w[:, ky, kx, :].t()
-    return out
-
-
-_ints = {}
-
-
-def _int_case(rows, h, wd, c, k):
-    """test_gpu_net_conv_pipeline._int_case's recipe: x in {-1,0,1}; w in {-1,0,1} with about 3/4 zeros, asymmetric in (k,c) and
-    in (ky,kx); integer bias and res.  Every partial sum is an integer below 2048 in magnitude: exact in fp32 and in fp16."""
-    import torch
-    key = (rows, h, wd, c, k)
-    if key not in _ints:
-        g = torch.Generator(device="cuda").manual_seed(99 + rows + 1000 * h + 31 * wd + c + 7 * k)
-        ri = lambda shape, lo, hi: torch.randint(lo, hi + 1, shape, device="cuda", generator=g)
-        x = ri((rows, h, wd, c), -1, 1).half()
-        w = (ri((k, 3, 3, c), -1, 1) * (ri((k, 3, 3, c), 0, 3) == 0)).half()
-        b = ri((k,), -8, 8).half()
-        r = ri((rows, h, wd, k), -8, 8).half()
-        conv = _conv_fp32(x.float(), w.float())
-        assert conv.abs().max().item() < 1024 and not torch.equal(w, w.flip(1)) and not torch.equal(w, w.flip(2))
-        _ints[key] = dict(x=x, w=w, b=b, r=r, conv=conv)
-    return _ints[key]
 
 
 @pytest.mark.parametrize("relu", [0, 1])
@@ -162,14 +92,14 @@ def test_non_square_boards_exact_integers(elf, h, wd, c, use_res, relu):
     import torch
     rows, k, width = 7, 256, 2
     assert [[hf for _, _, hf in ch] for ch in _chains(elf.lib(), rows, h, wd, k, width)] == [[F] * 3] * 2
-    d = _int_case(rows, h, wd, c, k)
+    d = cc.int_case(_seed(rows, h, wd, c, k), rows, h, wd, c, k)
     ref = d["conv"] + d["b"].float()
     if use_res:
         ref = ref + d["r"].float()
     if relu:
         ref = torch.relu(ref)
-    buf, y = _guarded(rows, h, wd, k)
-    assert _run(elf.lib(), d["x"], d["w"], d["b"], d["r"] if use_res else None, y, rows, h, wd, c, k, relu, 1, width) == 0
+    buf, y = cc.guarded(rows, h, wd, k)
+    assert cc.launch(elf.lib(), "linear", d["x"], d["w"], d["b"], d["r"] if use_res else None, y, relu, width) == 0
     torch.cuda.synchronize()
     bad = int((y.float() != ref).sum().item())   # a NaN left in y differs from everything
     print("h %d w %d c %d res %d relu %d: %d of %d differ" % (h, wd, c, use_res, relu, bad, y.numel()))
@@ -190,8 +120,8 @@ def test_tap_masks_are_the_items_own(elf, width):
     i = torch.arange(n, device="cuda")
     cnt = 3 - (i == 0).int() - (i == n - 1).int()
     want = (c * cnt[:, None] * cnt[None, :]).float()[None, :, :, None].expand(rows, n, n, k)
-    buf, y = _guarded(rows, n, n, k)
-    assert _run(elf.lib(), x, w, b, None, y, rows, n, n, c, k, 0, 1, width) == 0
+    buf, y = cc.guarded(rows, n, n, k)
+    assert cc.launch(elf.lib(), "linear", x, w, b, None, y, 0, width) == 0
     torch.cuda.synchronize()
     bad = int((y.float() != want).sum().item())
     print("width %d: %d of %d differ" % (width, bad, y.numel()))
@@ -208,12 +138,12 @@ def test_a_nan_weight_row_reaches_its_own_channel_only(elf, ch):
     channel is what it was"""
     import torch
     rows, h, wd, c, k, width = POISON
-    x, w, b, r = _rand_case(rows, h, wd, c, k)
+    x, w, b, r = cc.rand_case(_rseed(rows, h, wd, c, k), rows, h, wd, c, k)
     want = _reference(elf, rows, h, wd, c, k, True, 0, 0)
     wn = w.clone()
     wn[ch] = float("nan")
-    buf, y = _guarded(rows, h, wd, k)
-    assert _run(elf.lib(), x, wn, b, r, y, rows, h, wd, c, k, 0, 1, width) == 0
+    buf, y = cc.guarded(rows, h, wd, k)
+    assert cc.launch(elf.lib(), "linear", x, wn, b, r, y, 0, width) == 0
     torch.cuda.synchronize()
     nan = torch.isnan(y)
     print("channel %d: %d NaN in it of %d, %d NaN elsewhere" % (ch, int(nan[..., ch].sum().item()), rows * h * wd,
@@ -230,12 +160,12 @@ def test_a_nan_in_x_stays_in_its_own_item(elf):
     import torch
     rows, h, wd, c, k, width = POISON
     assert _chains(elf.lib(), rows, h, wd, k, width)[0][1] == (2, 0, F)
-    x, w, b, r = _rand_case(rows, h, wd, c, k)
+    x, w, b, r = cc.rand_case(_rseed(rows, h, wd, c, k), rows, h, wd, c, k)
     want = _reference(elf, rows, h, wd, c, k, True, 0, 0)
     xn = x.clone()
     xn[1, 12, 11, 5] = float("nan")
-    buf, y = _guarded(rows, h, wd, k)
-    assert _run(elf.lib(), xn, w, b, r, y, rows, h, wd, c, k, 0, 1, width) == 0
+    buf, y = cc.guarded(rows, h, wd, k)
+    assert cc.launch(elf.lib(), "linear", xn, w, b, r, y, 0, width) == 0
     torch.cuda.synchronize()
     hit = torch.zeros((rows, h, wd), device="cuda", dtype=torch.bool)
     hit[1, 11:14, 10:13] = True
@@ -249,12 +179,12 @@ def test_a_nan_in_x_stays_in_its_own_item(elf):
 def test_a_nan_row_of_res_reaches_its_own_row_only(elf):
     import torch
     rows, h, wd, c, k, width = POISON
-    x, w, b, r = _rand_case(rows, h, wd, c, k)
+    x, w, b, r = cc.rand_case(_rseed(rows, h, wd, c, k), rows, h, wd, c, k)
     want = _reference(elf, rows, h, wd, c, k, True, 0, 0)
     rn = r.clone()
     rn[1, 12, 11] = float("nan")
-    buf, y = _guarded(rows, h, wd, k)
-    assert _run(elf.lib(), x, w, b, rn, y, rows, h, wd, c, k, 0, 1, width) == 0
+    buf, y = cc.guarded(rows, h, wd, k)
+    assert cc.launch(elf.lib(), "linear", x, w, b, rn, y, 0, width) == 0
     torch.cuda.synchronize()
     hit = torch.zeros((rows, h, wd), device="cuda", dtype=torch.bool)
     hit[1, 12, 11] = True
@@ -271,12 +201,12 @@ def test_repeated_launches(elf, rows, h, wd, c, k, width):
     fresh NaN-filled outputs all return the bits of the first, and the first is algo 0's.  A first K tile read before it has
     landed gives wrong tiles that come and go from launch to launch."""
     import torch
-    x, w, b, r = _rand_case(rows, h, wd, c, k)
+    x, w, b, r = cc.rand_case(_rseed(rows, h, wd, c, k), rows, h, wd, c, k)
     want = _reference(elf, rows, h, wd, c, k, True, 1, 0)
     first = None
     for i in range(20):
         y = torch.full((rows, h, wd, k), float("nan"), device="cuda", dtype=torch.float16)
-        assert _run(elf.lib(), x, w, b, r, y, rows, h, wd, c, k, 1, 1, width) == 0
+        assert cc.launch(elf.lib(), "linear", x, w, b, r, y, 1, width) == 0
         torch.cuda.synchronize()
         if first is None:
             first = y

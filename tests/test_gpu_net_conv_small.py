@@ -10,63 +10,26 @@ import ctypes as C
 
 import pytest
 
+import conv_cases as cc
+from conv_cases import NAN, elf  # noqa: F401  (elf: the fixture)
+
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def elf(built):
-    import elf_amd
-    return elf_amd
+def _seed(rows, h, wd, c, k):
+    return 77 + rows + 1000 * h + 31 * wd + c + 7 * k
 
 
-def _conv_fp32(x, w):
-    """conv2d(x, w, padding=1) in fp32 for NHWC x [rows,h,w,C] and w [K,3,3,C] as its nine taps (test_gpu_net_conv._conv_fp32)"""
-    import torch
-    rows, h, wd = x.shape[0], x.shape[1], x.shape[2]
-    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))
-    out = torch.zeros((rows, h, wd, w.shape[0]), device=x.device, dtype=torch.float32)
-    for ky in range(3):
-        for kx in range(3):
-            out += xp[:, ky:ky + h, kx:kx + wd, :] @ w[:, ky, kx, :].t()
-    return out
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+def _rseed(rows, h, wd, c, k):
+    return 4242 + rows + h + c + k
 
 
 def _small(L, x, w, b, r, y, rows, h, wd, relu, c, k):
-    import torch
-    return L.elfnet_conv3x3_small_f16(_p(x), _p(w), _p(b), _p(r), _p(y), rows, h, wd, c, k, int(relu),
-                                      C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return cc.launch(L, "small", x, w, b, r, y, relu, shape=(rows, h, wd, c, k))
 
 
 def _algo0(L, x, w, b, r, y, rows, h, wd, relu, c, k):
-    import torch
-    return L.elfnet_conv3x3_f16(_p(x), _p(w), _p(b), _p(r), _p(y), rows, h, wd, c, k, int(relu), 0,
-                                C.c_void_p(torch.cuda.current_stream().cuda_stream))
-
-
-_ints = {}
-
-
-def _int_case(rows, h, wd, c, k):
-    """test_gpu_net_conv_native._int_case's recipe: x in {-1,0,1}; w in {-1,0,1} with about 3/4 zeros, drawn per element so it is
-    asymmetric in (k,c) and in (ky,kx); integer bias and res.  |partial sum| <= 9 c / 4 + spread, far below 2048, |result| below
-    2048: exact in fp32 and in fp16."""
-    import torch
-    key = (rows, h, wd, c, k)
-    if key not in _ints:
-        g = torch.Generator(device="cuda").manual_seed(77 + rows + 1000 * h + 31 * wd + c + 7 * k)
-        ri = lambda shape, lo, hi: torch.randint(lo, hi + 1, shape, device="cuda", generator=g)
-        x = ri((rows, h, wd, c), -1, 1).half()
-        w = (ri((k, 3, 3, c), -1, 1) * (ri((k, 3, 3, c), 0, 3) == 0)).half()
-        b = ri((k,), -8, 8).half()
-        r = ri((rows, h, wd, k), -8, 8).half()
-        conv = _conv_fp32(x.float(), w.float())
-        assert conv.abs().max().item() < 1024 and not torch.equal(w, w.flip(1)) and not torch.equal(w, w.flip(2))
-        _ints[key] = dict(x=x, w=w, b=b, r=r, conv=conv)
-    return _ints[key]
+    return cc.launch(L, "algo0", x, w, b, r, y, relu, shape=(rows, h, wd, c, k))
 
 
 @pytest.mark.parametrize("relu", [0, 1])
@@ -86,15 +49,13 @@ def test_exact_integers(elf, rows, h, wd, c, k, use_res, relu):
     """equality with the nine-tap fp32 form; y is prefilled with NaN, and one guard row of NaN behind y's last row stays NaN (the
     tail tile's stores are masked)"""
     import torch
-    d = _int_case(rows, h, wd, c, k)
+    d = cc.int_case(_seed(rows, h, wd, c, k), rows, h, wd, c, k)
     ref = d["conv"] + d["b"].float()
     if use_res:
         ref = ref + d["r"].float()
     if relu:
         ref = torch.relu(ref)
-    m = rows * h * wd
-    buf = torch.full((m + 1, k), float("nan"), device="cuda", dtype=torch.float16)
-    y = buf[:m].view(rows, h, wd, k)
+    buf, y = cc.guarded(rows, h, wd, k)
     rc = _small(elf.lib(), d["x"], d["w"], d["b"], d["r"] if use_res else None, y, rows, h, wd, relu, c, k)
     assert rc == 0
     torch.cuda.synchronize()
@@ -122,24 +83,20 @@ def test_all_ones_halo(elf, n):
     assert bool((y.float() == want[None, :, :, None]).all())
 
 
-_rand = {}
+_first = {}
 
 
-def _rand_case(rows, n, c, k):
-    """test_gpu_net_conv_native._rand_case's recipe"""
+def _first_launch(rows, n, c, k):
+    """cc.rand_case's operands and y, the first launch of the small entry on them, with skip and ReLU; nobody writes it again"""
     import torch
     key = (rows, n, c, k)
-    if key not in _rand:
-        g = torch.Generator(device="cuda").manual_seed(4242 + rows + n + c + k)
-        x = torch.randn((rows, n, n, c), device="cuda", generator=g).half()
-        w = (torch.randn((k, 3, 3, c), device="cuda", generator=g) * (9 * c) ** -0.5).half()
-        b = torch.randn((k,), device="cuda", generator=g).half()
-        r = torch.randn((rows, n, n, k), device="cuda", generator=g).half()
+    if key not in _first:
+        x, w, b, r = cc.rand_case(_rseed(rows, n, n, c, k), rows, n, n, c, k)
         y = torch.full((rows, n, n, k), float("nan"), device="cuda", dtype=torch.float16)
         assert _small(__import__("elf_amd").lib(), x, w, b, r, y, rows, n, n, 1, c, k) == 0
         torch.cuda.synchronize()
-        _rand[key] = (x, w, b, r, y)   # y: the first launch of the new entry, with skip and ReLU; nobody writes it again
-    return _rand[key]
+        _first[key] = (x, w, b, r, y)
+    return _first[key]
 
 
 @pytest.mark.parametrize("rows,n,c,k", [(16, 19, 256, 256), (3, 9, 128, 64)])
@@ -148,7 +105,7 @@ def test_bit_equal_with_algo_0(elf, rows, n, c, k):
     32-channel block one 32x32x16 MFMA over channels {0..7, 16..23}, the next over {8..15, 24..31}) and its epilogue sequence, so
     the two outputs are the same bits"""
     import torch
-    x, w, b, r, got = _rand_case(rows, n, c, k)
+    x, w, b, r, got = _first_launch(rows, n, c, k)
     y0 = torch.full((rows, n, n, k), float("nan"), device="cuda", dtype=torch.float16)
     assert _algo0(elf.lib(), x, w, b, r, y0, rows, n, n, 1, c, k) == 0
     torch.cuda.synchronize()
@@ -162,7 +119,7 @@ def test_repeated_launches_return_the_same_bits(elf):
     same 16-row inputs launched 20 times return the bits of the first launch."""
     import torch
     rows = 16
-    x, w, b, r, first = _rand_case(rows, 19, 256, 256)
+    x, w, b, r, first = _first_launch(rows, 19, 256, 256)
     assert not bool(torch.isnan(first).any())
     for i in range(1, 20):
         y = torch.full((rows, 19, 19, 256), float("nan"), device="cuda", dtype=torch.float16)
@@ -175,7 +132,7 @@ def test_repeated_launches_return_the_same_bits(elf):
 def test_a_row_does_not_depend_on_its_batch(elf, row):
     """a row of the 16-row call, run as a 1-row call (other tiles, other tails), returns the bits it has in the batch"""
     import torch
-    x, w, b, r, batch = _rand_case(16, 19, 256, 256)
+    x, w, b, r, batch = _first_launch(16, 19, 256, 256)
     x1, r1 = x[row:row + 1].contiguous(), r[row:row + 1].contiguous()
     y = torch.full((1, 19, 19, 256), float("nan"), device="cuda", dtype=torch.float16)
     assert _small(elf.lib(), x1, w, b, r1, y, 1, 19, 19, 1, 256, 256) == 0
@@ -201,7 +158,8 @@ def test_refusals_leave_y_alone(elf, case):
         px = py          # c == k == 64: y's buffer is large enough to be read as x
     elif case == "y_is_res":
         pr = py
-    rc = elf.lib().elfnet_conv3x3_small_f16(C.c_void_p(px), _p(w), _p(b), C.c_void_p(pr), C.c_void_p(py), rows, n, n, c, k, 1, st)
+    rc = elf.lib().elfnet_conv3x3_small_f16(C.c_void_p(px), cc.ptr(w), cc.ptr(b), C.c_void_p(pr), C.c_void_p(py), rows, n, n, c, k, 1,
+                                            st)
     assert rc < 0
     torch.cuda.synchronize()
     assert bool((y == 7.0).all())
@@ -289,38 +247,13 @@ def test_whole_net_replays_from_a_graph_to_the_same_bits(elf):
 
 # ------------------------------------------------------------------------------------------------ what only this kernel has
 
-NAN = float("nan")
-
-
-def _guarded(rows, h, wd, k):
-    """y prefilled with NaN, and one guard row of NaN behind its last row (test_gpu_net_edges._guarded)"""
-    import torch
-    buf = torch.full((rows * h * wd + 1, k), NAN, device="cuda", dtype=torch.float16)
-    return buf, buf[:rows * h * wd].view(rows, h, wd, k)
-
-
-def _carve(t, guard):
-    """test_gpu_net_edges._carve: a copy of t inside a larger NaN-filled fp16 buffer, at least `guard` elements of NaN in front and
-    behind, at an address that is 16-byte and not 32-byte aligned.  -> (the copy, front guard, back guard)"""
-    import torch
-    n = t.numel()
-    buf = torch.full((guard + n + guard + 32,), NAN, device="cuda", dtype=torch.float16)
-    o = guard
-    while (buf.data_ptr() + 2 * o) % 32 != 16:
-        o += 1
-    v = buf[o:o + n].view(t.shape)
-    v.copy_(t)
-    assert v.data_ptr() % 32 == 16 and o >= guard and buf.numel() - (o + n) >= guard
-    return v, buf[:o], buf[o + n:]
-
-
 def test_more_workgroups_than_are_resident(elf):
     """Three workgroups of 48 KiB LDS fit a CU, 768 on the chip's 256 CUs.  200 rows of 9 x 9 are 16 200 positions = 254 tiles x
     4 channel columns = 1 016 workgroups: with and without skip, with and without ReLU, the result is the integer nine-tap form and
     algo 0's output bit for bit; the guard row behind y stays NaN (test_gpu_net_edges.test_algo_1_beyond_one_round_of_workgroups)."""
     import torch
     rows, h, wd, c, k = 200, 9, 9, 64, 256
-    d = _int_case(rows, h, wd, c, k)
+    d = cc.int_case(_seed(rows, h, wd, c, k), rows, h, wd, c, k)
     assert (rows * h * wd + 63) // 64 == 254 and 254 * (k // 64) == 1016 > 3 * 256
     for use_res in (False, True):
         for relu in (0, 1):
@@ -330,9 +263,9 @@ def test_more_workgroups_than_are_resident(elf):
                 ref = ref + r.float()
             if relu:
                 ref = torch.relu(ref)
-            buf, y = _guarded(rows, h, wd, k)
+            buf, y = cc.guarded(rows, h, wd, k)
             assert _small(elf.lib(), d["x"], d["w"], d["b"], r, y, rows, h, wd, relu, c, k) == 0
-            buf0, y0 = _guarded(rows, h, wd, k)
+            buf0, y0 = cc.guarded(rows, h, wd, k)
             assert _algo0(elf.lib(), d["x"], d["w"], d["b"], r, y0, rows, h, wd, relu, c, k) == 0
             torch.cuda.synchronize()
             bad = int((y.float() != ref).sum().item())   # a NaN left in y differs from everything
@@ -354,7 +287,7 @@ def test_one_nan_next_to_the_tail(elf, pos):
     assert rows * h * wd == 5 * 64 + 41 and 5 * 64 + 32 == 352
     i, j = divmod(pos, wd)
     assert (i, j) in ((18, 18), (18, 9), (18, 10))
-    d = _int_case(rows, h, wd, c, k)
+    d = cc.int_case(_seed(rows, h, wd, c, k), rows, h, wd, c, k)
     clean = d["conv"] + d["b"].float()
     x = d["x"].clone()
     touched = torch.zeros((rows, h, wd), device="cuda", dtype=torch.bool)
@@ -363,7 +296,7 @@ def test_one_nan_next_to_the_tail(elf, pos):
     for ch in (0, 100, c - 1):
         keep = x[0, i, j, ch].item()
         x[0, i, j, ch] = NAN
-        buf, y = _guarded(rows, h, wd, k)
+        buf, y = cc.guarded(rows, h, wd, k)
         assert _small(elf.lib(), x, d["w"], d["b"], None, y, rows, h, wd, 0, c, k) == 0
         torch.cuda.synchronize()
         yf = y.float()
@@ -382,11 +315,11 @@ def test_res_behind_the_last_row(elf, rows, h, wd, c, k):
     (16-byte, not 32-byte aligned); no ReLU, so a skip value taken from behind res would reach the result as NaN: the result is
     the integer form exactly and both guards of y are still all NaN."""
     import torch
-    d = _int_case(rows, h, wd, c, k)
+    d = cc.int_case(_seed(rows, h, wd, c, k), rows, h, wd, c, k)
     guard = (wd + 2) * max(c, k)
     assert rows * h * wd % 64 != 0    # there are rows behind M in the last tile
-    r, _, _ = _carve(d["r"], guard)
-    y, front, back = _carve(torch.full((rows, h, wd, k), NAN, device="cuda", dtype=torch.float16), guard)
+    r, _, _ = cc.carve(d["r"], guard)
+    y, front, back = cc.carve(torch.full((rows, h, wd, k), NAN, device="cuda", dtype=torch.float16), guard)
     ref = d["conv"] + d["b"].float() + d["r"].float()
     assert _small(elf.lib(), d["x"], d["w"], d["b"], r, y, rows, h, wd, 0, c, k) == 0
     torch.cuda.synchronize()
@@ -414,7 +347,7 @@ def test_the_first_refused_weight_size(elf):
 def test_the_top_of_the_accepted_range(elf):
     """The largest call the entry takes at c = k = 64 on 19 x 19: rows * 361 * 64 < 2^30 elements, x and y just below 2^31 bytes
     each, so the kernel's 32-bit byte offsets (position * 128 plus a tap's distance) are as large as they get.  One more row is
-    refused.  x in {-1, 0, 1}, the integer weights and bias of _int_case; one launch, no skip, no ReLU.  Three slices of two boards
+    refused.  x in {-1, 0, 1}, the integer weights and bias of cc.int_case; one launch, no skip, no ReLU.  Three slices of two boards
     each -- the first two, the two around byte offset 2^30 of x, the last two -- equal the integer nine-tap form of those boards
     alone; no row of y is left NaN and the guard row behind y still is."""
     import time
@@ -425,7 +358,7 @@ def test_the_top_of_the_accepted_range(elf):
     assert rows * h * wd * c < 2 ** 30 <= (rows + 1) * h * wd * c and rows == 46474
     m = rows * h * wd
     assert 2 ** 31 - 2 * h * wd * c <= m * c * 2 < 2 ** 31
-    d = _int_case(2, h, wd, c, k)
+    d = cc.int_case(_seed(2, h, wd, c, k), 2, h, wd, c, k)
     w, b = d["w"], d["b"]
     g = torch.Generator(device="cuda").manual_seed(2 ** 30)
     x = torch.randint(-1, 2, (rows, h, wd, c), device="cuda", dtype=torch.int8, generator=g).half()
@@ -443,7 +376,7 @@ def test_the_top_of_the_accepted_range(elf):
     for lo in (0, mid - 1, rows - 2):
         xs = x[lo:lo + 2]
         assert bool((xs != 0).any())
-        ref = _conv_fp32(xs.float(), w.float()) + b.float()
+        ref = cc.conv_fp32(xs.float(), w.float()) + b.float()
         bad = int((y[lo:lo + 2].float() != ref).sum().item())
         print("boards %d and %d: %d of %d differ" % (lo, lo + 1, bad, ref.numel()))
         assert bad == 0

@@ -3,33 +3,20 @@ elf_amd/csrc/net_conv3x3.hip): where the last round of work items is at most hal
 of 256 positions x 128 channels.  The round width is given explicitly, so a few tiles reach every branch of the rule.  Every
 comparison is exact: bit for bit against algo 0, against algo 1 with a width that never splits, against the integer nine-tap
 form, and launch against launch; y is prefilled with NaN and has a NaN guard row behind it."""
-import ctypes as C
-
 import pytest
+
+import conv_cases as cc
+from conv_cases import elf  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-NEVER = 1 << 30   # a round wider than any launch here: never split
+
+def _seed(rows, h, wd, c, k):
+    return 99 + rows + 1000 * h + 31 * wd + c + 7 * k
 
 
-@pytest.fixture(scope="module")
-def elf(built):
-    import elf_amd
-    return elf_amd
-
-
-def _run(L, x, w, b, r, y, rows, h, wd, c, k, relu, algo, width):
-    import torch
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    return L.elfnet_conv3x3_f16_width(p(x), p(w), p(b), p(r), p(y), rows, h, wd, c, k, int(relu), algo, width,
-                                      C.c_void_p(torch.cuda.current_stream().cuda_stream))
-
-
-def _guarded(rows, h, wd, k):
-    """y prefilled with NaN, and one guard row of NaN behind its last row"""
-    import torch
-    buf = torch.full((rows * h * wd + 1, k), float("nan"), device="cuda", dtype=torch.float16)
-    return buf, buf[:rows * h * wd].view(rows, h, wd, k)
+def _rseed(rows, h, wd, c, k):
+    return 5151 + rows + 31 * h + 977 * wd + c + 7 * k
 
 
 def _groups(L, rows, h, wd, k, width):
@@ -38,38 +25,12 @@ def _groups(L, rows, h, wd, k, width):
     return tiles * (k // 256), L.elfnet_conv3x3_f16_plan(tiles, k // 256, width, 0, None, None, None)
 
 
-_rand = {}
-
-
-def _rand_case(rows, h, wd, c, k):
-    """test_gpu_net_conv_pipeline._rand_case's recipe; drawn once per shape and left unchanged"""
-    import torch
-    key = (rows, h, wd, c, k)
-    if key not in _rand:
-        g = torch.Generator(device="cuda").manual_seed(5151 + rows + 31 * h + 977 * wd + c + 7 * k)
-        x = torch.randn((rows, h, wd, c), device="cuda", generator=g).half()
-        w = (torch.randn((k, 3, 3, c), device="cuda", generator=g) * (9 * c) ** -0.5).half()
-        b = torch.randn((k,), device="cuda", generator=g).half()
-        r = torch.randn((rows, h, wd, k), device="cuda", generator=g).half()
-        _rand[key] = (x, w, b, r)
-    return _rand[key]
-
-
-_ref = {}
-
-
 def _reference(elf, rows, h, wd, c, k, use_res, relu, algo):
-    """algo 0's output, or algo 1's with a width that never splits; computed once per case"""
-    import torch
-    key = (rows, h, wd, c, k, use_res, relu, algo)
-    if key not in _ref:
-        x, w, b, r = _rand_case(rows, h, wd, c, k)
-        y = torch.full((rows, h, wd, k), float("nan"), device="cuda", dtype=torch.float16)
-        assert _run(elf.lib(), x, w, b, r if use_res else None, y, rows, h, wd, c, k, relu, algo, NEVER) == 0
-        torch.cuda.synchronize()
-        assert not bool(torch.isnan(y).any())
-        _ref[key] = y
-    return _ref[key]
+    """algo 0's output, or algo 1's with a width that never splits (cc.ALONE); computed once per case"""
+    shape = (rows, h, wd, c, k)
+    if algo == 0:
+        return cc.algo0_ref(elf.lib(), _rseed(*shape), shape, use_res, relu)
+    return cc.cached_ref(elf.lib(), "linear", _rseed(*shape), shape, use_res, relu, cc.ALONE)
 
 
 # rows, h, w, Cin, K, round width, whether the rule splits
@@ -96,9 +57,9 @@ def test_split_launch_is_bit_equal_with_algo_0_and_with_the_unsplit_launch(elf, 
     total, groups = _groups(L, rows, h, wd, k, width)
     r = total % width
     assert groups == (total + r if split else total), (total, groups)
-    x, w, b, res = _rand_case(rows, h, wd, c, k)
-    buf, y = _guarded(rows, h, wd, k)
-    assert _run(L, x, w, b, res if use_res else None, y, rows, h, wd, c, k, relu, 1, width) == 0
+    x, w, b, res = cc.rand_case(_rseed(rows, h, wd, c, k), rows, h, wd, c, k)
+    buf, y = cc.guarded(rows, h, wd, k)
+    assert cc.launch(L, "linear", x, w, b, res if use_res else None, y, relu, width) == 0
     torch.cuda.synchronize()
     for name, algo in (("algo 0", 0), ("algo 1 unsplit", 1)):
         want = _reference(elf, rows, h, wd, c, k, use_res, relu, algo)
@@ -111,45 +72,12 @@ def test_split_launch_is_bit_equal_with_algo_0_and_with_the_unsplit_launch(elf, 
 def test_a_negative_width_launches_nothing(elf):
     import torch
     rows, h, wd, c, k = 3, 19, 19, 64, 256
-    x, w, b, _ = _rand_case(rows, h, wd, c, k)
-    buf, y = _guarded(rows, h, wd, k)
-    assert _run(elf.lib(), x, w, b, None, y, rows, h, wd, c, k, 1, 1, -1) == -1
-    assert _run(elf.lib(), x, w, b, None, y, rows, h, wd, c, k, 1, 2, 4) == -1
+    x, w, b, _ = cc.rand_case(_rseed(rows, h, wd, c, k), rows, h, wd, c, k)
+    buf, y = cc.guarded(rows, h, wd, k)
+    assert cc.launch(elf.lib(), "linear", x, w, b, None, y, 1, -1) == -1
+    assert cc.launch(elf.lib(), "linear", x, w, b, None, y, 1, 4, algo=2) == -1
     torch.cuda.synchronize()
     assert bool(torch.isnan(buf).all())
-
-
-def _conv_fp32(x, w):
-    """conv2d(x, w, padding=1) in fp32 for NHWC x [rows,h,w,C] and w [K,3,3,C] as its nine taps"""
-    import torch
-    rows, h, wd = x.shape[0], x.shape[1], x.shape[2]
-    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))
-    out = torch.zeros((rows, h, wd, w.shape[0]), device=x.device, dtype=torch.float32)
-    for ky in range(3):
-        for kx in range(3):
-            out += xp[:, ky:ky + h, kx:kx + wd, :] @ w[:, ky, kx, :].t()
-    return out
-
-
-_ints = {}
-
-
-def _int_case(rows, h, wd, c, k):
-    """test_gpu_net_conv_pipeline._int_case's recipe: x in {-1,0,1}; w in {-1,0,1} with about 3/4 zeros, asymmetric in (k,c) and
-    in (ky,kx); integer bias and res.  Every partial sum is an integer below 2048 in magnitude: exact in fp32 and in fp16."""
-    import torch
-    key = (rows, h, wd, c, k)
-    if key not in _ints:
-        g = torch.Generator(device="cuda").manual_seed(99 + rows + 1000 * h + 31 * wd + c + 7 * k)
-        ri = lambda shape, lo, hi: torch.randint(lo, hi + 1, shape, device="cuda", generator=g)
-        x = ri((rows, h, wd, c), -1, 1).half()
-        w = (ri((k, 3, 3, c), -1, 1) * (ri((k, 3, 3, c), 0, 3) == 0)).half()
-        b = ri((k,), -8, 8).half()
-        r = ri((rows, h, wd, k), -8, 8).half()
-        conv = _conv_fp32(x.float(), w.float())
-        assert conv.abs().max().item() < 1024 and not torch.equal(w, w.flip(1)) and not torch.equal(w, w.flip(2))
-        _ints[key] = dict(x=x, w=w, b=b, r=r, conv=conv)
-    return _ints[key]
 
 
 @pytest.mark.parametrize("relu", [0, 1])
@@ -162,14 +90,14 @@ def test_non_square_boards_exact_integers(elf, h, wd, c, use_res, relu):
     import torch
     rows, k, width = 20, 256, 2
     assert _groups(elf.lib(), rows, h, wd, k, width) == (3, 4)
-    d = _int_case(rows, h, wd, c, k)
+    d = cc.int_case(_seed(rows, h, wd, c, k), rows, h, wd, c, k)
     ref = d["conv"] + d["b"].float()
     if use_res:
         ref = ref + d["r"].float()
     if relu:
         ref = torch.relu(ref)
-    buf, y = _guarded(rows, h, wd, k)
-    assert _run(elf.lib(), d["x"], d["w"], d["b"], d["r"] if use_res else None, y, rows, h, wd, c, k, relu, 1, width) == 0
+    buf, y = cc.guarded(rows, h, wd, k)
+    assert cc.launch(elf.lib(), "linear", d["x"], d["w"], d["b"], d["r"] if use_res else None, y, relu, width) == 0
     torch.cuda.synchronize()
     bad = int((y.float() != ref).sum().item())   # a NaN left in y differs from everything
     print("h %d w %d c %d res %d relu %d: %d of %d differ" % (h, wd, c, use_res, relu, bad, y.numel()))
@@ -184,12 +112,12 @@ def test_a_nan_weight_row_reaches_its_own_channel_only(elf, ch):
     import torch
     rows, h, wd, c, k, width = 3, 19, 19, 64, 256, 4
     assert _groups(elf.lib(), rows, h, wd, k, width) == (5, 6)
-    x, w, b, r = _rand_case(rows, h, wd, c, k)
+    x, w, b, r = cc.rand_case(_rseed(rows, h, wd, c, k), rows, h, wd, c, k)
     want = _reference(elf, rows, h, wd, c, k, True, 0, 0)
     wn = w.clone()
     wn[ch] = float("nan")
-    buf, y = _guarded(rows, h, wd, k)
-    assert _run(elf.lib(), x, wn, b, r, y, rows, h, wd, c, k, 0, 1, width) == 0
+    buf, y = cc.guarded(rows, h, wd, k)
+    assert cc.launch(elf.lib(), "linear", x, wn, b, r, y, 0, width) == 0
     torch.cuda.synchronize()
     nan = torch.isnan(y)
     print("channel %d: %d NaN in it of %d, %d NaN elsewhere" % (ch, int(nan[..., ch].sum().item()), rows * h * wd,
@@ -208,12 +136,12 @@ def test_repeated_split_launches(elf, c):
     import torch
     rows, h, wd, k, width = 4, 19, 19, 256, 4
     assert _groups(elf.lib(), rows, h, wd, k, width) == (6, 8)
-    x, w, b, r = _rand_case(rows, h, wd, c, k)
+    x, w, b, r = cc.rand_case(_rseed(rows, h, wd, c, k), rows, h, wd, c, k)
     want = _reference(elf, rows, h, wd, c, k, True, 1, 0)
     first = None
     for i in range(20):
         y = torch.full((rows, h, wd, k), float("nan"), device="cuda", dtype=torch.float16)
-        assert _run(elf.lib(), x, w, b, r, y, rows, h, wd, c, k, 1, 1, width) == 0
+        assert cc.launch(elf.lib(), "linear", x, w, b, r, y, 1, width) == 0
         torch.cuda.synchronize()
         if first is None:
             first = y

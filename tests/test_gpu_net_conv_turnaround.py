@@ -14,45 +14,26 @@ B. Epilogue values: one board of 19 x 19, C = 64, K = 256, width 1 (both tiles i
 The reference is algo 0 on the same inputs, bit for bit; in A the nine-tap integers and in B a numpy float32 model of the contract
 (include/elf_amd.h: float(half(acc)) + float(bias), + float(res), fmaxf(., 0), one rounding to fp16) are a second one.  y is
 prefilled with NaN and has a NaN guard row behind it."""
-import ctypes as C
-
 import numpy as np
 import pytest
+
+import conv_cases as cc
+from conv_cases import RES_RELU, elf  # noqa: F401  (elf: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def elf(built):
-    import elf_amd
-    return elf_amd
-
-
-def _run(L, x, w, b, r, y, rows, h, wd, c, k, relu, algo, width):
-    import torch
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    return L.elfnet_conv3x3_f16_width(p(x), p(w), p(b), p(r), p(y), rows, h, wd, c, k, int(relu), algo, width, st)
-
-
-def _guarded(rows, h, wd, k):
-    import torch
-    buf = torch.full((rows * h * wd + 1, k), float("nan"), device="cuda", dtype=torch.float16)
-    return buf, buf[:rows * h * wd].view(rows, h, wd, k)
-
-
-def _bits(t):
-    import torch
-    return t.contiguous().view(torch.int16)
+def _seed(rows, h, wd, c, k):
+    return 8191 + rows + 31 * h + 977 * wd + c + 7 * k
 
 
 def _both(elf, x, w, b, r, rows, h, wd, c, k, relu, width):
     """algo 1 at `width` and algo 0 on the same inputs; asserts the guard row and returns (y1, y0)"""
     import torch
-    buf1, y1 = _guarded(rows, h, wd, k)
-    buf0, y0 = _guarded(rows, h, wd, k)
-    assert _run(elf.lib(), x, w, b, r, y1, rows, h, wd, c, k, relu, 1, width) == 0
-    assert _run(elf.lib(), x, w, b, r, y0, rows, h, wd, c, k, relu, 0, 0) == 0
+    buf1, y1 = cc.guarded(rows, h, wd, k)
+    buf0, y0 = cc.guarded(rows, h, wd, k)
+    assert cc.launch(elf.lib(), "linear", x, w, b, r, y1, relu, width) == 0
+    assert cc.launch(elf.lib(), "algo0", x, w, b, r, y0, relu) == 0
     torch.cuda.synchronize()
     assert bool(torch.isnan(buf1[-1]).all()) and bool(torch.isnan(buf0[-1]).all())
     return y1, y0
@@ -84,7 +65,7 @@ def _ones_case(elf, rows, h, wd, k):
         w = torch.ones((k, 3, 3, c), device="cuda", dtype=torch.float16)
         b = torch.zeros((k,), device="cuda", dtype=torch.float16)
         y0 = torch.full((rows, h, wd, k), float("nan"), device="cuda", dtype=torch.float16)
-        assert _run(elf.lib(), x, w, b, None, y0, rows, h, wd, c, k, 0, 0, 0) == 0
+        assert cc.launch(elf.lib(), "algo0", x, w, b, None, y0, 0) == 0
         torch.cuda.synchronize()
         rowc = np.array([(i > 0) + 1 + (i < h - 1) for i in range(h)])
         colc = np.array([(j > 0) + 1 + (j < wd - 1) for j in range(wd)])
@@ -98,14 +79,14 @@ def _ones_case(elf, rows, h, wd, k):
 def test_decode_counts_the_taps_on_the_board(elf, rows, h, wd, k, width):
     import torch
     x, w, b, y0, taps = _ones_case(elf, rows, h, wd, k)
-    buf, y = _guarded(rows, h, wd, k)
-    assert _run(elf.lib(), x, w, b, None, y, rows, h, wd, 64, k, 0, 1, width) == 0
+    buf, y = cc.guarded(rows, h, wd, k)
+    assert cc.launch(elf.lib(), "linear", x, w, b, None, y, 0, width) == 0
     torch.cuda.synchronize()
     bad = int((y.float() != taps).sum().item())   # a NaN left in y differs from everything
     print("%s width %d: %d of %d differ from the nine-tap integers, %d from algo 0"
-          % ((rows, h, wd, k), width, bad, y.numel(), int((_bits(y) != _bits(y0)).sum().item())))
+          % ((rows, h, wd, k), width, bad, y.numel(), int((cc.bits(y) != cc.bits(y0)).sum().item())))
     assert bad == 0
-    assert torch.equal(_bits(y), _bits(y0))
+    assert torch.equal(cc.bits(y), cc.bits(y0))
     assert bool(torch.isnan(buf[-1]).all())
 
 
@@ -118,13 +99,13 @@ def test_repeated_launches_of_two_chains(elf, rows, h, wd, k, width):
     first = None
     for i in range(20):
         y = torch.full((rows, h, wd, k), float("nan"), device="cuda", dtype=torch.float16)
-        assert _run(elf.lib(), x, w, b, None, y, rows, h, wd, 64, k, 0, 1, width) == 0
+        assert cc.launch(elf.lib(), "linear", x, w, b, None, y, 0, width) == 0
         torch.cuda.synchronize()
         if first is None:
             first = y
-            assert torch.equal(_bits(y), _bits(y0)), "the first launch differs from algo 0"
+            assert torch.equal(cc.bits(y), cc.bits(y0)), "the first launch differs from algo 0"
         else:
-            assert torch.equal(_bits(y), _bits(first)), "launch %d differs from the first" % i
+            assert torch.equal(cc.bits(y), cc.bits(first)), "launch %d differs from the first" % i
 
 
 # ------------------------------------------------------------------------------------------------------- B. epilogue values
@@ -197,7 +178,7 @@ def _epilogue_case(elf, probes, use_res, relu, expect=None, zero_sign_is_algo0s=
         x, w, b, r, where = _case(probes, rot, 99 + rot)
         t = lambda a: torch.from_numpy(a).cuda()
         y1, y0 = _both(elf, t(x), t(w), t(b), t(r) if use_res else None, 1, H, W, CIN, K, relu, 1)
-        g1, g0 = _bits(y1).cpu().numpy().reshape(H * W, K), _bits(y0).cpu().numpy().reshape(H * W, K)
+        g1, g0 = cc.bits(y1).cpu().numpy().reshape(H * W, K), cc.bits(y0).cpu().numpy().reshape(H * W, K)
         m = _model(x, w, b, r if use_res else None, relu)
         mb = m.view(np.int16)
         print("res %d relu %d rot %d: %d of %d elements differ from algo 0" % (use_res, relu, rot, int((g1 != g0).sum()), g1.size))
@@ -216,7 +197,6 @@ def _epilogue_case(elf, probes, use_res, relu, expect=None, zero_sign_is_algo0s=
     return seen
 
 
-RES_RELU = [(False, 0), (False, 1), (True, 0), (True, 1)]
 ONE, MONE, INF, MINF, PZ, MZ = 0x3C00, 0xBC00, 0x7C00, 0xFC00, 0x0000, 0x8000
 
 
@@ -295,13 +275,9 @@ RANDOM = [(1, 9, 9, 0), (1, 1, 257, 0), (20, 9, 9, 2)]
 def test_random_data_is_bit_equal_with_algo_0(elf, c, k, use_res, relu):
     import torch
     for rows, h, wd, width in RANDOM:
-        g = torch.Generator(device="cuda").manual_seed(8191 + rows + 31 * h + 977 * wd + c + 7 * k)
-        x = torch.randn((rows, h, wd, c), device="cuda", generator=g).half()
-        w = (torch.randn((k, 3, 3, c), device="cuda", generator=g) * (9 * c) ** -0.5).half()
-        b = torch.randn((k,), device="cuda", generator=g).half()
-        r = torch.randn((rows, h, wd, k), device="cuda", generator=g).half()
+        x, w, b, r = cc.rand_case(_seed(rows, h, wd, c, k), rows, h, wd, c, k)
         y1, y0 = _both(elf, x, w, b, r if use_res else None, rows, h, wd, c, k, relu, width)
         print("%s width %d res %d relu %d: %d of %d elements differ from algo 0"
-              % ((rows, h, wd, c, k), width, use_res, relu, int((_bits(y1) != _bits(y0)).sum().item()), y1.numel()))
+              % ((rows, h, wd, c, k), width, use_res, relu, int((cc.bits(y1) != cc.bits(y0)).sum().item()), y1.numel()))
         assert not bool(torch.isnan(y0).any())
-        assert torch.equal(_bits(y1), _bits(y0))
+        assert torch.equal(cc.bits(y1), cc.bits(y0))

@@ -18,91 +18,19 @@ import ctypes as C
 
 import pytest
 
+import conv_cases as cc
+from conv_cases import NAN, elf  # noqa: F401  (elf: the fixture)
+
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
 INF = float("inf")
 
-
-@pytest.fixture(scope="module")
-def elf(built):
-    import elf_amd
-    return elf_amd
-
-
 ENTRIES = [0, 1, "small"]   # elfnet_conv3x3_f16's two algos and elfnet_conv3x3_small_f16
+HOW = {0: "algo0", 1: "plain", "small": "small"}     # conv_cases.launch's names of them
 
 
-def _run(L, x, w, b, r, y, rows, h, wd, c, k, relu, algo):
-    """one call of the entry `algo` names: the small entry takes the same arguments but for the algo"""
-    import torch
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    if algo == "small":
-        return L.elfnet_conv3x3_small_f16(p(x), p(w), p(b), p(r), p(y), rows, h, wd, c, k, int(relu),
-                                          C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert algo in (0, 1)
-    return L.elfnet_conv3x3_f16(p(x), p(w), p(b), p(r), p(y), rows, h, wd, c, k, int(relu), algo,
-                                C.c_void_p(torch.cuda.current_stream().cuda_stream))
-
-
-def _guarded(rows, h, wd, k):
-    """y prefilled with NaN, and one guard row of NaN behind its last row"""
-    import torch
-    buf = torch.full((rows * h * wd + 1, k), NAN, device="cuda", dtype=torch.float16)
-    return buf, buf[:rows * h * wd].view(rows, h, wd, k)
-
-
-def _conv_fp32(x, w):
-    """conv2d(x, w, padding=1) in fp32 for NHWC x [rows,h,w,C] and w [K,3,3,C] as its nine taps"""
-    import torch
-    rows, h, wd = x.shape[0], x.shape[1], x.shape[2]
-    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))
-    out = torch.zeros((rows, h, wd, w.shape[0]), device=x.device, dtype=torch.float32)
-    for ky in range(3):
-        for kx in range(3):
-            out += xp[:, ky:ky + h, kx:kx + wd, :] @ w[:, ky, kx, :].t()
-    return out
-
-
-_ints = {}
-
-
-def _int_case(rows, h, wd, c, k):
-    """test_gpu_net_conv_pipeline._int_case's recipe: x in {-1,0,1}; w in {-1,0,1} with about 3/4 zeros, drawn per element so it is
-    asymmetric in (k,c) and in (ky,kx); integer bias and res.  Every partial sum is an integer below 2048 in magnitude: exact in
-    fp32 and in fp16.  Drawn once per shape and left unchanged (the tests that poison an operand work on a clone)."""
-    import torch
-    key = (rows, h, wd, c, k)
-    if key not in _ints:
-        g = torch.Generator(device="cuda").manual_seed(77 + rows + 1000 * h + 31 * wd + c + 7 * k)
-        ri = lambda shape, lo, hi: torch.randint(lo, hi + 1, shape, device="cuda", generator=g)
-        x = ri((rows, h, wd, c), -1, 1).half()
-        w = (ri((k, 3, 3, c), -1, 1) * (ri((k, 3, 3, c), 0, 3) == 0)).half()
-        b = ri((k,), -8, 8).half()
-        r = ri((rows, h, wd, k), -8, 8).half()
-        conv = _conv_fp32(x.float(), w.float())
-        assert conv.abs().max().item() < 1024 and not torch.equal(w, w.flip(1)) and not torch.equal(w, w.flip(2))
-        _ints[key] = dict(x=x, w=w, b=b, r=r, conv=conv)
-    return _ints[key]
-
-
-def _epilogue_fp32(conv, b, r, relu):
-    """the header's sequence on an fp32 convolution result: rounded to fp16, + bias (+ res) in fp32, max(., 0) as fmax (a NaN
-    becomes 0), rounded to fp16.  On the integer cases neither rounding changes a value."""
-    import torch
-    v = conv.half().float() + b.float()
-    if r is not None:
-        v = v + r.float()
-    if relu:
-        v = torch.fmax(v, torch.zeros((), device=v.device))
-    return v.half()
-
-
-def _differing(y, ref):
-    """the number of elements that are neither equal as values (-0 equals +0, Inf equals Inf) nor NaN in both"""
-    import torch
-    y, ref = y.float(), ref.float()
-    return int((~((y == ref) | (torch.isnan(y) & torch.isnan(ref)))).sum().item())
+def _seed(rows, h, wd, c, k):
+    return 77 + rows + 1000 * h + 31 * wd + c + 7 * k
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -116,7 +44,7 @@ def test_algo_1_beyond_one_round_of_workgroups(elf, rows, h, wd, c, k):
     """More workgroups than the 256 CUs: with and without skip, with and without ReLU, algo 1 equals the integer nine-tap form and
     is algo 0's output bit for bit; the guard row behind y stays NaN."""
     import torch
-    d = _int_case(rows, h, wd, c, k)
+    d = cc.int_case(_seed(rows, h, wd, c, k), rows, h, wd, c, k)
     assert (rows * h * wd + 255) // 256 * (k // 256) > 256
     for use_res in (False, True):
         for relu in (0, 1):
@@ -126,10 +54,10 @@ def test_algo_1_beyond_one_round_of_workgroups(elf, rows, h, wd, c, k):
                 ref = ref + r.float()
             if relu:
                 ref = torch.relu(ref)
-            buf, y = _guarded(rows, h, wd, k)
-            assert _run(elf.lib(), d["x"], d["w"], d["b"], r, y, rows, h, wd, c, k, relu, 1) == 0
-            buf0, y0 = _guarded(rows, h, wd, k)
-            assert _run(elf.lib(), d["x"], d["w"], d["b"], r, y0, rows, h, wd, c, k, relu, 0) == 0
+            buf, y = cc.guarded(rows, h, wd, k)
+            assert cc.launch(elf.lib(), "plain", d["x"], d["w"], d["b"], r, y, relu) == 0
+            buf0, y0 = cc.guarded(rows, h, wd, k)
+            assert cc.launch(elf.lib(), "algo0", d["x"], d["w"], d["b"], r, y0, relu) == 0
             torch.cuda.synchronize()
             bad = int((y.float() != ref).sum().item())   # a NaN left in y differs from everything
             bits = int((y.view(torch.int16) != y0.view(torch.int16)).sum().item())
@@ -143,21 +71,6 @@ def test_algo_1_beyond_one_round_of_workgroups(elf, rows, h, wd, c, k):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # B. locality, bounds and alignment
 
-def _carve(t, guard):
-    """A copy of t inside a larger NaN-filled fp16 buffer, at least `guard` elements of NaN in front and behind, starting at an
-    address that is 16-byte and not 32-byte aligned (the ABI promises 16).  -> (the copy, front guard, back guard)"""
-    import torch
-    n = t.numel()
-    buf = torch.full((guard + n + guard + 32,), NAN, device="cuda", dtype=torch.float16)
-    o = guard
-    while (buf.data_ptr() + 2 * o) % 32 != 16:
-        o += 1
-    v = buf[o:o + n].view(t.shape)
-    v.copy_(t)
-    assert v.data_ptr() % 32 == 16 and o >= guard and buf.numel() - (o + n) >= guard
-    return v, buf[:o], buf[o + n:]
-
-
 @pytest.mark.parametrize("algo", ENTRIES)
 @pytest.mark.parametrize("rows,h,wd,c,k,res", [(5, 9, 9, 256, 256, None), (5, 9, 9, 256, 256, "r"), (5, 9, 9, 256, 256, "x"),
                                                (11, 5, 7, 64, 256, None), (11, 5, 7, 64, 256, "r")])
@@ -166,24 +79,24 @@ def test_guarded_operands_at_16_byte_alignment(elf, rows, h, wd, c, k, res, algo
     aligned; no ReLU, so a NaN read from outside an operand reaches the result.  The result is the integer nine-tap form
     exactly, and both guards of y are still all NaN.  res == "x" passes x itself as the skip (c == k), which the ABI allows."""
     import torch
-    d = _int_case(rows, h, wd, c, k)
+    d = cc.int_case(_seed(rows, h, wd, c, k), rows, h, wd, c, k)
     guard = (wd + 2) * max(c, k)
-    x, _, _ = _carve(d["x"], guard)
-    w, _, _ = _carve(d["w"], guard)
-    b, _, _ = _carve(d["b"], guard)
+    x, _, _ = cc.carve(d["x"], guard)
+    w, _, _ = cc.carve(d["w"], guard)
+    b, _, _ = cc.carve(d["b"], guard)
     r = None
     ref = d["conv"] + d["b"].float()
     if res == "r":
-        r, _, _ = _carve(d["r"], guard)
+        r, _, _ = cc.carve(d["r"], guard)
         ref = ref + d["r"].float()
     elif res == "x":
         assert c == k
         r = x
         ref = ref + d["x"].float()
-    y, front, back = _carve(torch.full((rows, h, wd, k), NAN, device="cuda", dtype=torch.float16), guard)
+    y, front, back = cc.carve(torch.full((rows, h, wd, k), NAN, device="cuda", dtype=torch.float16), guard)
     for t in (x, w, b, y) + ((r,) if r is not None else ()):
         assert t.data_ptr() % 32 == 16
-    assert _run(elf.lib(), x, w, b, r, y, rows, h, wd, c, k, 0, algo) == 0
+    assert cc.launch(elf.lib(), HOW[algo], x, w, b, r, y, 0) == 0
     torch.cuda.synchronize()
     bad = int((y.float() != ref).sum().item())
     print("%s res %s algo %s: %d of %d differ" % ((rows, h, wd, c, k), res, algo, bad, y.numel()))
@@ -216,7 +129,7 @@ def test_one_poisoned_input_element(elf, poison, c, algo):
     rows, h, wd, k = 5, 9, 9, 256
     assert [(b * h + i) * wd + j for b, i, j in POISON_SITES[6:]] == [255, 256, 404, 7, 31, 32, 63, 64, 383, 384]
     assert (0 * h + 0) * wd + 8 == 8 and (0, 0, 8) in POISON_SITES and rows * h * wd == 6 * 64 + 21
-    d = _int_case(rows, h, wd, c, k)
+    d = cc.int_case(_seed(rows, h, wd, c, k), rows, h, wd, c, k)
     clean = d["conv"] + d["b"].float()
     x = d["x"].clone()
     for (b, i, j) in POISON_SITES:
@@ -225,8 +138,8 @@ def test_one_poisoned_input_element(elf, poison, c, algo):
             x[b, i, j, ch] = poison
             touched = torch.zeros((rows, h, wd), device="cuda", dtype=torch.bool)
             touched[b, max(i - 1, 0):i + 2, max(j - 1, 0):j + 2] = True
-            buf, y = _guarded(rows, h, wd, k)
-            assert _run(elf.lib(), x, d["w"], d["b"], None, y, rows, h, wd, c, k, 0, algo) == 0
+            buf, y = cc.guarded(rows, h, wd, k)
+            assert cc.launch(elf.lib(), HOW[algo], x, d["w"], d["b"], None, y, 0) == 0
             torch.cuda.synchronize()
             yf = y.float()
             assert bool(torch.isfinite(yf[~touched]).all()), (b, i, j, ch)
@@ -235,8 +148,8 @@ def test_one_poisoned_input_element(elf, poison, c, algo):
             if poison != poison:
                 assert bool(torch.isnan(yf[touched]).all()), (b, i, j, ch)
             else:
-                ref = _conv_fp32(x.float(), d["w"].float()) + d["b"].float()
-                assert _differing(y, ref) == 0, (b, i, j, ch)
+                ref = cc.conv_fp32(x.float(), d["w"].float()) + d["b"].float()
+                assert cc.differing(y, ref) == 0, (b, i, j, ch)
             assert bool(torch.isnan(buf[-1]).all())
             x[b, i, j, ch] = keep
     assert torch.equal(x, d["x"])
@@ -271,18 +184,18 @@ def test_one_poisoned_weight_at_the_k_seams(elf, k0, ky, kx, where, c, algo):
 def _one_poisoned_weight(elf, k0, ky, kx, ch, c, algo):
     import torch
     rows, h, wd, k = 5, 9, 9, 256
-    d = _int_case(rows, h, wd, c, k)
+    d = cc.int_case(_seed(rows, h, wd, c, k), rows, h, wd, c, k)
     w = d["w"].clone()
     w[k0, ky, kx, ch] = INF
-    ref = _conv_fp32(d["x"].float(), w.float()) + d["b"].float()
+    ref = cc.conv_fp32(d["x"].float(), w.float()) + d["b"].float()
     clean = d["conv"] + d["b"].float()
-    buf, y = _guarded(rows, h, wd, k)
-    assert _run(elf.lib(), d["x"], w, d["b"], None, y, rows, h, wd, c, k, 0, algo) == 0
+    buf, y = cc.guarded(rows, h, wd, k)
+    assert cc.launch(elf.lib(), HOW[algo], d["x"], w, d["b"], None, y, 0) == 0
     torch.cuda.synchronize()
     yf = y.float()
     others = torch.arange(k, device="cuda") != k0
     assert bool((yf[..., others] == clean[..., others]).all())
-    assert _differing(y, ref) == 0
+    assert cc.differing(y, ref) == 0
     # stated directly, not through the reference: the source cell of output (i, j) is (i + ky - 1, j + kx - 1)
     i = torch.arange(h, device="cuda")[:, None] + (ky - 1)
     j = torch.arange(wd, device="cuda")[None, :] + (kx - 1)
@@ -325,8 +238,8 @@ def test_two_roundings_not_one_at_a_tie(elf, algo):
     want = torch.where(kinds == 9, 2304.0, torch.where(kinds == 6, 1538.0, 1026.0))
     assert torch.equal((acc.half().float() + 1).half().float(), want) and (acc + 1).half()[1, 1] == 2306   # the two sequences
     for relu in (0, 1):
-        buf, y = _guarded(rows, n, n, ch)
-        assert _run(elf.lib(), x, w, b, None, y, rows, n, n, ch, ch, relu, algo) == 0
+        buf, y = cc.guarded(rows, n, n, ch)
+        assert cc.launch(elf.lib(), HOW[algo], x, w, b, None, y, relu) == 0
         torch.cuda.synchronize()
         print("algo %s relu %d: interior %s edge %s corner %s" % (algo, relu, y[0, 4, 4, 0].item(), y[0, 0, 4, 0].item(), y[0, 0, 0, 0].item()))
         assert bool((y.float() == want[None, :, :, None]).all())
@@ -347,8 +260,8 @@ def test_the_first_rounding_overflows_to_inf(elf, algo):
     want = torch.where(kinds == 9, INF, torch.where(kinds == 6, 32768.0, 16384.0))
     assert torch.equal(((8192 * kinds).float().half().float() - 16384).half().float(), want)
     for relu in (0, 1):
-        buf, y = _guarded(rows, n, n, ch)
-        assert _run(elf.lib(), x, w, b, None, y, rows, n, n, ch, ch, relu, algo) == 0
+        buf, y = cc.guarded(rows, n, n, ch)
+        assert cc.launch(elf.lib(), HOW[algo], x, w, b, None, y, relu) == 0
         torch.cuda.synchronize()
         assert bool((y.float() == want[None, :, :, None]).all())
         assert bool(torch.isnan(buf[-1]).all())
@@ -375,7 +288,7 @@ def test_subnormal_inputs_and_outputs(elf, wshift, oshift, algo):
     flushed at the MFMA's inputs, at either rounding or in between.  The expected values are made on the host."""
     import torch
     rows, n, ch = 2, 9, 256
-    d = _int_case(rows, n, n, ch, ch)
+    d = cc.int_case(_seed(rows, n, n, ch, ch), rows, n, n, ch, ch)
     xi, wi, bi, ri = (d[key].float() for key in ("x", "w", "b", "r"))
     x = _scaled(xi, 24)
     w = (wi * 2.0 ** wshift).half()
@@ -393,8 +306,8 @@ def test_subnormal_inputs_and_outputs(elf, wshift, oshift, algo):
             assert float(ints.abs().max().item()) < 1024
             want = (ints.cpu().double() * 2.0 ** -oshift).half()      # exact: |ints| < 2^10, so ints * 2^-24 is an fp16 subnormal
             assert torch.equal(want.double() * 2.0 ** oshift, ints.cpu().double())
-            buf, y = _guarded(rows, n, n, ch)
-            assert _run(elf.lib(), x, w, b, r if use_res else None, y, rows, n, n, ch, ch, relu, algo) == 0
+            buf, y = cc.guarded(rows, n, n, ch)
+            assert cc.launch(elf.lib(), HOW[algo], x, w, b, r if use_res else None, y, relu) == 0
             torch.cuda.synchronize()
             got = y.cpu()
             bad = int((got.double() != want.double()).sum().item())
@@ -413,12 +326,12 @@ def test_relu_turns_nan_into_zero(elf, use_res, algo):
     with skip, one res element; the reference is torch.fmax(v, 0).  With relu = 0 the same NaNs come through."""
     import torch
     rows, n, ch = 2, 9, 256
-    d = _int_case(rows, n, n, ch, ch)
+    d = cc.int_case(_seed(rows, n, n, ch, ch), rows, n, n, ch, ch)
     x, b, r = d["x"].clone(), d["b"].clone(), d["r"].clone()
     x[1, 4, 4, 17] = NAN
     b[200] = NAN
     r[0, 2, 3, 5] = NAN
-    v = _conv_fp32(x.float(), d["w"].float()) + b.float()
+    v = cc.conv_fp32(x.float(), d["w"].float()) + b.float()
     if use_res:
         v = v + r.float()
     nan = torch.isnan(v)
@@ -429,8 +342,8 @@ def test_relu_turns_nan_into_zero(elf, use_res, algo):
         expect[0, 2, 3, 5] = True
     assert torch.equal(nan, expect)
     for relu in (1, 0):
-        buf, y = _guarded(rows, n, n, ch)
-        assert _run(elf.lib(), x, d["w"], b, r if use_res else None, y, rows, n, n, ch, ch, relu, algo) == 0
+        buf, y = cc.guarded(rows, n, n, ch)
+        assert cc.launch(elf.lib(), HOW[algo], x, d["w"], b, r if use_res else None, y, relu) == 0
         torch.cuda.synchronize()
         if relu:
             want = torch.fmax(v, torch.zeros((), device="cuda"))
@@ -438,7 +351,7 @@ def test_relu_turns_nan_into_zero(elf, use_res, algo):
             assert bool((y.float() == want).all())
             assert bool((y.view(torch.int16)[nan] == 0).all())      # +0, not -0
         else:
-            assert _differing(y, v) == 0 and torch.equal(torch.isnan(y), nan)
+            assert cc.differing(y, v) == 0 and torch.equal(torch.isnan(y), nan)
         assert bool(torch.isnan(buf[-1]).all())
 
 
@@ -453,7 +366,7 @@ def test_the_first_refused_size(elf, algo):
     b = torch.zeros((ch,), device="cuda", dtype=torch.float16)
     y = torch.full((1, 32, 32, ch), 7.0, device="cuda", dtype=torch.float16)
     assert 4096 * 32 * 32 * ch == 2 ** 30
-    assert _run(elf.lib(), x, w, b, None, y, 4096, 32, 32, ch, ch, 1, algo) < 0
+    assert cc.launch(elf.lib(), HOW[algo], x, w, b, None, y, 1, shape=(4096, 32, 32, ch, ch)) < 0
     torch.cuda.synchronize()
     assert bool((y == 7.0).all())
 
@@ -577,7 +490,7 @@ def test_bias_act_special_values(elf, name):
                 assert _bias_act(elf.lib(), dtype, y, bd if use_bias else None, rd if use_res else None, 64, 8, relu) == 0
                 torch.cuda.synchronize()
                 got = y.cpu()
-                bad = _differing(got, want)
+                bad = cc.differing(got, want)
                 if relu and not use_bias and not use_res:
                     assert x.view(torch.int16)[18, 0].item() == -32768 and bool(torch.isnan(x[6, 0]))
                     print("%s relu(-0) has the bits 0x%04x, relu(NaN) 0x%04x"
@@ -599,15 +512,15 @@ def test_algo_0_at_channel_counts_that_need_padding(elf, c, k, use_res):
     they are no multiple of its 128-channel and 32-deep tiles: the integer nine-tap form exactly, with and without ReLU"""
     import torch
     rows, h, wd = 3, 9, 9
-    d = _int_case(rows, h, wd, c, k)
+    d = cc.int_case(_seed(rows, h, wd, c, k), rows, h, wd, c, k)
     for relu in (0, 1):
         ref = d["conv"] + d["b"].float()
         if use_res:
             ref = ref + d["r"].float()
         if relu:
             ref = torch.relu(ref)
-        buf, y = _guarded(rows, h, wd, k)
-        assert _run(elf.lib(), d["x"], d["w"], d["b"], d["r"] if use_res else None, y, rows, h, wd, c, k, relu, 0) == 0
+        buf, y = cc.guarded(rows, h, wd, k)
+        assert cc.launch(elf.lib(), "algo0", d["x"], d["w"], d["b"], d["r"] if use_res else None, y, relu) == 0
         torch.cuda.synchronize()
         bad = int((y.float() != ref).sum().item())
         print("c %d k %d res %d relu %d: %d of %d differ" % (c, k, use_res, relu, bad, y.numel()))

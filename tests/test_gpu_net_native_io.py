@@ -10,61 +10,19 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import conv_cases as cc
+from conv_cases import elf  # noqa: F401  (the fixture)
+
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def elf(built):
-    import elf_amd
-    return elf_amd
+INTS = dict(res=False, limit=288)      # cc.int_case without res: |sum| <= 9 * 32 = 288, far below 2048: exact in fp32 and in fp16
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _conv_in(L, x, w, b, y, rows, n, c, k, relu):
-    return L.elfnet_conv3x3_in_f16(_p(x), _p(w), _p(b), _p(y), rows, n, n, c, k, int(relu), _stream())
-
-
-def _conv_nine_taps(x, w):
-    """conv2d(x, w, padding=1) for NHWC x [rows,h,w,C] and w [K,3,3,C] as its nine taps, in x's dtype (fp32 or fp64)"""
-    import torch
-    rows, h, wd = x.shape[0], x.shape[1], x.shape[2]
-    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))
-    out = torch.zeros((rows, h, wd, w.shape[0]), device=x.device, dtype=x.dtype)
-    for ky in range(3):
-        for kx in range(3):
-            out += xp[:, ky:ky + h, kx:kx + wd, :] @ w[:, ky, kx, :].t()
-    return out
+def _seed(rows, h, wd, c, k):
+    return 911 + rows + 1000 * h + c + 7 * k
 
 
 # ------------------------------------------------------------------------------------------------ input conv, exact
-
-_ints = {}
-
-
-def _int_case(rows, n, c, k):
-    """x in {-1,0,1}; w in {-1,0,1} with about 3/4 zeros, drawn per element so it is asymmetric in (k,c) and in both taps; integer
-    bias.  |sum| <= 9 * 32 = 288, far below 2048: exact in fp32 and in fp16."""
-    import torch
-    key = (rows, n, c, k)
-    if key not in _ints:
-        g = torch.Generator(device="cuda").manual_seed(911 + rows + 1000 * n + c + 7 * k)
-        ri = lambda shape, lo, hi: torch.randint(lo, hi + 1, shape, device="cuda", generator=g)
-        x = ri((rows, n, n, c), -1, 1).half()
-        w = (ri((k, 3, 3, c), -1, 1) * (ri((k, 3, 3, c), 0, 3) == 0)).half()
-        b = ri((k,), -8, 8).half()
-        conv = _conv_nine_taps(x.float(), w.float())
-        assert conv.abs().max().item() <= 288 and not torch.equal(w, w.flip(1)) and not torch.equal(w, w.flip(2))
-        _ints[key] = dict(x=x, w=w, b=b, conv=conv)
-    return _ints[key]
-
 
 @pytest.mark.parametrize("relu", [0, 1])
 @pytest.mark.parametrize("rows,n,c,k", [(3, 19, 18, 256),     # 1083 positions: a tail tile
@@ -78,13 +36,12 @@ def _int_case(rows, n, c, k):
 def test_input_conv_exact_integers(elf, rows, n, c, k, relu):
     """equality with the nine-tap fp32 form; y is prefilled with NaN, and one guard row of NaN behind y's last row stays NaN"""
     import torch
-    d = _int_case(rows, n, c, k)
+    d = cc.int_case(_seed(rows, n, n, c, k), rows, n, n, c, k, **INTS)
     ref = d["conv"] + d["b"].float()
     if relu:
         ref = torch.relu(ref)
-    buf = torch.full((rows * n * n + 1, k), float("nan"), device="cuda", dtype=torch.float16)
-    y = buf[:rows * n * n].view(rows, n, n, k)
-    assert _conv_in(elf.lib(), d["x"], d["w"], d["b"], y, rows, n, c, k, relu) == 0
+    buf, y = cc.guarded(rows, n, n, k)
+    assert cc.conv_in(elf.lib(), d["x"], d["w"], d["b"], y, rows, n, n, c, k, relu) == 0
     torch.cuda.synchronize()
     bad = int((y.float() != ref).sum().item())   # a NaN left in y differs from everything
     print("rows %d n %d c %d k %d relu %d: %d of %d differ" % (rows, n, c, k, relu, bad, y.numel()))
@@ -101,7 +58,7 @@ def test_input_conv_all_ones_halo(elf, n):
     w = torch.ones((k, 3, 3, c), device="cuda", dtype=torch.float16)
     b = torch.zeros((k,), device="cuda", dtype=torch.float16)
     y = torch.full((rows, n, n, k), float("nan"), device="cuda", dtype=torch.float16)
-    assert _conv_in(elf.lib(), x, w, b, y, rows, n, c, k, 0) == 0
+    assert cc.conv_in(elf.lib(), x, w, b, y, rows, n, n, c, k, 0) == 0
     torch.cuda.synchronize()
     i = torch.arange(n, device="cuda")
     on = 3 - ((i == 0) | (i == n - 1)).long()           # taps on the board along one axis
@@ -155,14 +112,14 @@ def test_input_conv_real_feature_rows_against_fp64(elf):
     import torch
     L = elf.lib()
     rows, n, c, k, s, x, w, b = _real_case(elf)
-    conv64 = _conv_nine_taps(x.double(), w.double()).cpu().numpy()
+    conv64 = cc.conv_fp32(x.double(), w.double()).cpu().numpy()
     r1 = conv64.astype(np.float16).astype(np.float32)
     ref = np.maximum(r1 + b.cpu().numpy().astype(np.float32)[None, None, None, :], np.float32(0)).astype(np.float16)
     y = torch.full((rows, n, n, k), float("nan"), device="cuda", dtype=torch.float16)
-    assert _conv_in(L, x, w, b, y, rows, n, c, k, 1) == 0
+    assert cc.conv_in(L, x, w, b, y, rows, n, n, c, k, 1) == 0
     pair = torch.nn.functional.conv2d(s, w.permute(0, 3, 1, 2), None, 1, 1)
     assert pair.is_contiguous(memory_format=torch.channels_last)
-    assert L.elfnet_bias_act_f16(_p(pair), _p(b), None, rows * n * n, k, 1, _stream()) == 0
+    assert L.elfnet_bias_act_f16(cc.ptr(pair), cc.ptr(b), None, rows * n * n, k, 1, cc.stream()) == 0
     torch.cuda.synchronize()
     got = y.cpu().numpy()
     got_pair = pair.permute(0, 2, 3, 1).contiguous().cpu().numpy()
@@ -178,12 +135,6 @@ def test_input_conv_real_feature_rows_against_fp64(elf):
 
 
 # ------------------------------------------------------------------------------------------------ heads
-
-def _heads_struct(t, ch, vh):
-    from elf_amd._lib import ElfNetHeads
-    names = ("pconv_w", "pconv_b", "vconv_w", "vconv_b", "pi_w", "pi_b", "v1_w", "v1_b", "v2_w", "v2_b")
-    return ElfNetHeads(*[t[nm].data_ptr() for nm in names], ch, vh)
-
 
 def _upload(a):
     """name -> fp16 device tensor of every array in `a` (all of them exactly representable)"""
@@ -245,8 +196,9 @@ def _run_heads(L, t, ch, vh, rows, n, stride=None, want_logits=True):
     pi, value, logits = nan(rows, stride), nan(rows + 1), nan(rows, stride) if want_logits else None
     nb = L.elfnet_heads_workspace(rows, n, n)
     ws = torch.empty((nb,), device="cuda", dtype=torch.uint8)
-    hd = _heads_struct(t, ch, vh)
-    rc = L.elfnet_heads_f16(_p(t["act"]), C.byref(hd), rows, n, n, _p(pi), stride, _p(value), _p(logits), _p(ws), nb, _stream())
+    hd = cc.heads_struct(t, ch, vh)
+    rc = L.elfnet_heads_f16(cc.ptr(t["act"]), C.byref(hd), rows, n, n, cc.ptr(pi), stride, cc.ptr(value), cc.ptr(logits), cc.ptr(ws), nb,
+                            cc.stream())
     torch.cuda.synchronize()
     return rc, pi, value, logits
 
@@ -314,7 +266,7 @@ def test_repeated_launches_return_the_same_bits(elf):
     first = None
     for i in range(20):
         y = torch.full((rows, n, n, k), float("nan"), device="cuda", dtype=torch.float16)
-        assert _conv_in(L, x, w, b, y, rows, n, c, k, 1) == 0
+        assert cc.conv_in(L, x, w, b, y, rows, n, n, c, k, 1) == 0
         torch.cuda.synchronize()
         if first is None:
             first = y

@@ -20,107 +20,22 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import conv_cases as cc
+from conv_cases import NAN, elf  # noqa: F401  (elf: the fixture)
+
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
 INF = float("inf")
 PI_REL, PI_SUM, V_ABS = 1e-4, 1e-5, 2.0 ** -20      # test_heads_exact's bounds
 
 
-@pytest.fixture(scope="module")
-def elf(built):
-    import elf_amd
-    return elf_amd
+# test_gpu_net_native_io's integer recipe (no res, |sum| <= 9 * 32 = 288) on an h x wd board, and not degenerate: the convolution is
+# not all zero and on a non-square board the nine-tap form of the same memory read as wd x h differs
+INTS = dict(res=False, limit=288, not_degenerate=True)
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _conv_in(L, x, w, b, y, rows, h, wd, c, k, relu):
-    return L.elfnet_conv3x3_in_f16(_p(x), _p(w), _p(b), _p(y), rows, h, wd, c, k, int(relu), _stream())
-
-
-def _conv_nine_taps(x, w):
-    """conv2d(x, w, padding=1) for NHWC x [rows,h,w,C] and w [K,3,3,C] as its nine taps, in x's dtype"""
-    import torch
-    rows, h, wd = x.shape[0], x.shape[1], x.shape[2]
-    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))
-    out = torch.zeros((rows, h, wd, w.shape[0]), device=x.device, dtype=x.dtype)
-    for ky in range(3):
-        for kx in range(3):
-            out += xp[:, ky:ky + h, kx:kx + wd, :] @ w[:, ky, kx, :].t()
-    return out
-
-
-def _guarded(rows, h, wd, k):
-    """y prefilled with NaN, and one guard row of NaN behind its last row"""
-    import torch
-    buf = torch.full((rows * h * wd + 1, k), NAN, device="cuda", dtype=torch.float16)
-    return buf, buf[:rows * h * wd].view(rows, h, wd, k)
-
-
-def _epilogue_fp32(conv, b, relu):
-    """the header's sequence on an fp32 convolution result: rounded to fp16, + bias in fp32, max(., 0) as fmax (a NaN becomes 0),
-    rounded to fp16"""
-    import torch
-    v = conv.half().float() + b.float()
-    if relu:
-        v = torch.fmax(v, torch.zeros((), device=v.device))
-    return v.half()
-
-
-def _differing(y, ref):
-    """the number of elements that are neither equal as values (-0 equals +0, Inf equals Inf) nor NaN in both"""
-    import torch
-    y, ref = y.float(), ref.float()
-    return int((~((y == ref) | (torch.isnan(y) & torch.isnan(ref)))).sum().item())
-
-
-def _carve(t, guard, mod, rem):
-    """A copy of t inside a larger NaN-filled buffer of t's type, at least `guard` elements of NaN in front and behind, starting
-    at an address that is `rem` modulo `mod` bytes.  -> (the copy, front guard, back guard)"""
-    import torch
-    n, es = t.numel(), t.element_size()
-    buf = torch.full((guard + n + guard + mod,), NAN, device="cuda", dtype=t.dtype)
-    o = guard
-    while (buf.data_ptr() + es * o) % mod != rem:
-        o += 1
-    v = buf[o:o + n].view(t.shape)
-    v.copy_(t)
-    assert v.data_ptr() % mod == rem and o >= guard and buf.numel() - (o + n) >= guard
-    return v, buf[:o], buf[o + n:]
-
-
-_ints = {}
-
-
-def _int_case(rows, h, wd, c, k):
-    """test_gpu_net_native_io._int_case's recipe on an h x wd board: x in {-1,0,1}; w in {-1,0,1} with about 3/4 zeros, drawn per
-    element so it is asymmetric in (k,c) and in both taps; integer bias.  |sum| <= 9 * 32 = 288: every partial sum is an integer far
-    below 2048, exact in fp32 and in fp16.  Not degenerate: the convolution is not all zero, the weights change under either flip,
-    and on a non-square board the nine-tap form of the same memory read as wd x h differs.  Drawn once per shape, left unchanged."""
-    import torch
-    key = (rows, h, wd, c, k)
-    if key not in _ints:
-        g = torch.Generator(device="cuda").manual_seed(4242 + rows + 1000 * h + 31 * wd + c + 7 * k)
-        ri = lambda shape, lo, hi: torch.randint(lo, hi + 1, shape, device="cuda", generator=g)
-        x = ri((rows, h, wd, c), -1, 1).half()
-        w = (ri((k, 3, 3, c), -1, 1) * (ri((k, 3, 3, c), 0, 3) == 0)).half()
-        b = ri((k,), -8, 8).half()
-        conv = _conv_nine_taps(x.float(), w.float())
-        assert conv.abs().max().item() <= 288 and bool((conv != 0).any())
-        assert not torch.equal(w, w.flip(1)) and not torch.equal(w, w.flip(2))
-        if h != wd:
-            swapped = _conv_nine_taps(x.float().view(rows, wd, h, c), w.float()).view(rows, h, wd, k)
-            assert not torch.equal(swapped, conv)
-        _ints[key] = dict(x=x, w=w, b=b, conv=conv)
-    return _ints[key]
+def _seed(rows, h, wd, c, k):
+    return 4242 + rows + 1000 * h + 31 * wd + c + 7 * k
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -139,12 +54,12 @@ def _int_case(rows, h, wd, c, k):
 def test_input_conv_shapes_exact_integers(elf, rows, h, wd, c, k, relu):
     """equality with the nine-tap fp32 form; y is prefilled with NaN, and the guard row of NaN behind y's last row stays NaN"""
     import torch
-    d = _int_case(rows, h, wd, c, k)
+    d = cc.int_case(_seed(rows, h, wd, c, k), rows, h, wd, c, k, **INTS)
     ref = d["conv"] + d["b"].float()
     if relu:
         ref = torch.relu(ref)
-    buf, y = _guarded(rows, h, wd, k)
-    assert _conv_in(elf.lib(), d["x"], d["w"], d["b"], y, rows, h, wd, c, k, relu) == 0
+    buf, y = cc.guarded(rows, h, wd, k)
+    assert cc.conv_in(elf.lib(), d["x"], d["w"], d["b"], y, rows, h, wd, c, k, relu) == 0
     torch.cuda.synchronize()
     bad = int((y.float() != ref).sum().item())   # a NaN left in y differs from everything
     print("%s relu %d: %d of %d differ" % ((rows, h, wd, c, k), relu, bad, y.numel()))
@@ -166,28 +81,28 @@ def test_input_conv_one_poisoned_input_element(elf, rows, n, b, i, j, poison):
     +Inf: a finite sum plus Inf)."""
     import torch
     c, k = 18, 64
-    d = _int_case(rows, n, n, c, k)
+    d = cc.int_case(_seed(rows, n, n, c, k), rows, n, n, c, k, **INTS)
     w = torch.ones((k, 3, 3, c), device="cuda", dtype=torch.float16)
     if n == 19:
         assert (i * n + j) == 64 and 0 < i < n - 1 and 0 < j < n - 1 and ((i - 1) * n + j - 1) // 64 != ((i + 1) * n + j + 1) // 64
     L = elf.lib()
-    _, clean = _guarded(rows, n, n, k)
-    assert _conv_in(L, d["x"], w, d["b"], clean, rows, n, n, c, k, 0) == 0
+    _, clean = cc.guarded(rows, n, n, k)
+    assert cc.conv_in(L, d["x"], w, d["b"], clean, rows, n, n, c, k, 0) == 0
     torch.cuda.synchronize()
     assert bool(torch.isfinite(clean).all())
-    assert bool((clean.float() == _conv_nine_taps(d["x"].float(), w.float()) + d["b"].float()).all())
+    assert bool((clean.float() == cc.conv_fp32(d["x"].float(), w.float()) + d["b"].float()).all())
     touched = torch.zeros((rows, n, n), device="cuda", dtype=torch.bool)
     touched[b, max(i - 1, 0):i + 2, max(j - 1, 0):j + 2] = True
     assert int(touched.sum().item()) == (4 if n == 9 else 9)
     for ch in (0, c - 1):
         x = d["x"].clone()
         x[b, i, j, ch] = poison
-        buf, y = _guarded(rows, n, n, k)
-        assert _conv_in(L, x, w, d["b"], y, rows, n, n, c, k, 0) == 0
+        buf, y = cc.guarded(rows, n, n, k)
+        assert cc.conv_in(L, x, w, d["b"], y, rows, n, n, c, k, 0) == 0
         torch.cuda.synchronize()
         assert torch.equal(y[~touched].view(torch.int16), clean[~touched].view(torch.int16)), ch
         assert not bool(torch.isfinite(y[touched]).any()), ch
-        assert _differing(y, _conv_nine_taps(x.float(), w.float()) + d["b"].float()) == 0, ch
+        assert cc.differing(y, cc.conv_fp32(x.float(), w.float()) + d["b"].float()) == 0, ch
         if poison != poison:
             assert bool(torch.isnan(y[touched]).all()), ch
         else:
@@ -204,18 +119,18 @@ def test_input_conv_one_nan_weight(elf, k0, ky, kx):
     the ReLU channel k0 is 0 (fmaxf) and the others are unchanged."""
     import torch
     rows, n, c, k = 2, 9, 18, 256
-    d = _int_case(rows, n, n, c, k)
+    d = cc.int_case(_seed(rows, n, n, c, k), rows, n, n, c, k, **INTS)
     w = d["w"].clone()
     w[k0, ky, kx, c - 1] = NAN
     others = torch.arange(k, device="cuda") != k0
     L = elf.lib()
     for relu in (0, 1):
-        _, clean = _guarded(rows, n, n, k)
-        assert _conv_in(L, d["x"], d["w"], d["b"], clean, rows, n, n, c, k, relu) == 0
-        buf, y = _guarded(rows, n, n, k)
-        assert _conv_in(L, d["x"], w, d["b"], y, rows, n, n, c, k, relu) == 0
+        _, clean = cc.guarded(rows, n, n, k)
+        assert cc.conv_in(L, d["x"], d["w"], d["b"], clean, rows, n, n, c, k, relu) == 0
+        buf, y = cc.guarded(rows, n, n, k)
+        assert cc.conv_in(L, d["x"], w, d["b"], y, rows, n, n, c, k, relu) == 0
         torch.cuda.synchronize()
-        ref = _conv_nine_taps(d["x"].float(), w.float()) + d["b"].float()
+        ref = cc.conv_fp32(d["x"].float(), w.float()) + d["b"].float()
         assert bool(torch.isnan(ref[..., k0]).all()) and bool(torch.isfinite(ref[..., others]).all())
         assert bool(torch.isfinite(clean).all())
         assert torch.equal(y[..., others].view(torch.int16), clean[..., others].view(torch.int16)), relu
@@ -223,7 +138,7 @@ def test_input_conv_one_nan_weight(elf, k0, ky, kx):
             assert bool((y[..., k0].view(torch.int16) == 0).all())
         else:
             assert bool(torch.isnan(y[..., k0]).all())
-            assert _differing(y, ref) == 0
+            assert cc.differing(y, ref) == 0
         assert bool(torch.isnan(buf[-1]).all())
 
 
@@ -234,16 +149,16 @@ def test_input_conv_guarded_operands_at_the_weakest_alignment(elf, rows, h, wd, 
     ReLU, so a NaN read from outside an operand would reach the result.  The result is the unguarded run's bit for bit and the
     integer nine-tap form; y's guards stay NaN."""
     import torch
-    d = _int_case(rows, h, wd, c, k)
+    d = cc.int_case(_seed(rows, h, wd, c, k), rows, h, wd, c, k, **INTS)
     guard = (wd + 2) * max(c, k)
-    x, _, _ = _carve(d["x"], guard, 16, 4)
-    w, _, _ = _carve(d["w"], guard, 32, 16)
-    b, _, _ = _carve(d["b"], guard, 32, 16)
-    y, front, back = _carve(torch.full((rows, h, wd, k), NAN, device="cuda", dtype=torch.float16), guard, 32, 16)
+    x, _, _ = cc.carve(d["x"], guard, 16, 4)
+    w, _, _ = cc.carve(d["w"], guard, 32, 16)
+    b, _, _ = cc.carve(d["b"], guard, 32, 16)
+    y, front, back = cc.carve(torch.full((rows, h, wd, k), NAN, device="cuda", dtype=torch.float16), guard, 32, 16)
     assert x.data_ptr() % 16 == 4 and w.data_ptr() % 32 == 16 and b.data_ptr() % 32 == 16
-    _, plain = _guarded(rows, h, wd, k)
-    assert _conv_in(elf.lib(), d["x"], d["w"], d["b"], plain, rows, h, wd, c, k, 0) == 0
-    assert _conv_in(elf.lib(), x, w, b, y, rows, h, wd, c, k, 0) == 0
+    _, plain = cc.guarded(rows, h, wd, k)
+    assert cc.conv_in(elf.lib(), d["x"], d["w"], d["b"], plain, rows, h, wd, c, k, 0) == 0
+    assert cc.conv_in(elf.lib(), x, w, b, y, rows, h, wd, c, k, 0) == 0
     torch.cuda.synchronize()
     assert torch.equal(y.view(torch.int16), plain.view(torch.int16))
     assert bool((y.float() == d["conv"] + d["b"].float()).all())
@@ -280,11 +195,11 @@ def test_input_conv_two_roundings_not_one_at_a_tie(elf, c, xv):
     kinds = _cell_kinds(n)
     acc = (t * kinds + 1).float()
     assert 2048 < acc[1, 1] < 4096 and acc[1, 1] % 2 == 1 and acc[0, 1] + 1 < 2048
-    want = _epilogue_fp32(acc, b[0], 0).float()
+    want = cc.epilogue_fp32(acc, b[0], None, 0).float()
     assert want[1, 1] == 9 * t and (acc + 1).half()[1, 1] == 9 * t + 2 and want[0, 1] == 6 * t + 2 and want[0, 0] == 4 * t + 2
     for relu in (0, 1):
-        buf, y = _guarded(rows, n, n, k)
-        assert _conv_in(elf.lib(), x, w, b, y, rows, n, n, c, k, relu) == 0
+        buf, y = cc.guarded(rows, n, n, k)
+        assert cc.conv_in(elf.lib(), x, w, b, y, rows, n, n, c, k, relu) == 0
         torch.cuda.synchronize()
         print("c %d relu %d: interior %s edge %s corner %s" % (c, relu, y[0, 4, 4, 0].item(), y[0, 0, 4, 0].item(), y[0, 0, 0, 0].item()))
         assert bool((y.float() == want[None, :, :, None]).all())
@@ -304,12 +219,12 @@ def test_input_conv_first_rounding_overflows_to_inf(elf, c, xv, wv, bv):
     b = torch.full((k,), bv, device="cuda", dtype=torch.float16)
     kinds = _cell_kinds(n)
     acc = (t * kinds).float()
-    want = _epilogue_fp32(acc, b[0], 0).float()
+    want = cc.epilogue_fp32(acc, b[0], None, 0).float()
     assert want[1, 1] == INF and bool(torch.isfinite((acc + bv).half()[1, 1])) and acc[1, 1] < 2.0 ** 24
     assert want[0, 1] == 6 * t + bv and want[0, 0] == 4 * t + bv
     for relu in (0, 1):
-        buf, y = _guarded(rows, n, n, k)
-        assert _conv_in(elf.lib(), x, w, b, y, rows, n, n, c, k, relu) == 0
+        buf, y = cc.guarded(rows, n, n, k)
+        assert cc.conv_in(elf.lib(), x, w, b, y, rows, n, n, c, k, relu) == 0
         torch.cuda.synchronize()
         assert bool((y.float() == want[None, :, :, None]).all())
         assert bool(torch.isnan(buf[-1]).all())
@@ -335,7 +250,7 @@ def test_input_conv_subnormal_inputs_and_outputs(elf, wshift, oshift):
     be flushed at the MFMA's inputs, at either rounding or in between.  The expected values are made on the host."""
     import torch
     rows, n, c, k = 2, 9, 18, 64
-    d = _int_case(rows, n, n, c, k)
+    d = cc.int_case(_seed(rows, n, n, c, k), rows, n, n, c, k, **INTS)
     xi, wi, bi = (d[key].float() for key in ("x", "w", "b"))
     x = _scaled(xi, 24)
     w = (wi * 2.0 ** wshift).half()
@@ -349,8 +264,8 @@ def test_input_conv_subnormal_inputs_and_outputs(elf, wshift, oshift):
         assert float(ints.abs().max().item()) < 1024
         want = (ints.cpu().double() * 2.0 ** -oshift).half()      # exact: |ints| < 2^10
         assert torch.equal(want.double() * 2.0 ** oshift, ints.cpu().double())
-        buf, y = _guarded(rows, n, n, k)
-        assert _conv_in(elf.lib(), x, w, b, y, rows, n, n, c, k, relu) == 0
+        buf, y = cc.guarded(rows, n, n, k)
+        assert cc.conv_in(elf.lib(), x, w, b, y, rows, n, n, c, k, relu) == 0
         torch.cuda.synchronize()
         got = y.cpu()
         bad = int((got.double() != want.double()).sum().item())
@@ -368,12 +283,12 @@ def test_input_conv_relu_turns_nan_into_zero(elf):
     NaN and Inf come through."""
     import torch
     rows, n, c, k = 2, 9, 18, 64
-    d = _int_case(rows, n, n, c, k)
+    d = cc.int_case(_seed(rows, n, n, c, k), rows, n, n, c, k, **INTS)
     x, b = d["x"].clone(), d["b"].clone()
     x[1, 4, 4, 7] = NAN
     x[0, 2, 2, 3] = INF
     b[20] = NAN
-    v = _conv_nine_taps(x.float(), d["w"].float()) + b.float()
+    v = cc.conv_fp32(x.float(), d["w"].float()) + b.float()
     nan = torch.isnan(v)
     must = torch.zeros_like(nan)
     must[1, 3:6, 3:6, :] = True
@@ -383,8 +298,8 @@ def test_input_conv_relu_turns_nan_into_zero(elf):
     assert bool(nan[must].all()) and not bool(nan[~may].any())
     assert bool((v == INF).any()) and bool((v == -INF).any()) and bool(torch.isfinite(v[~may]).all())
     for relu in (1, 0):
-        buf, y = _guarded(rows, n, n, k)
-        assert _conv_in(elf.lib(), x, d["w"], b, y, rows, n, n, c, k, relu) == 0
+        buf, y = cc.guarded(rows, n, n, k)
+        assert cc.conv_in(elf.lib(), x, d["w"], b, y, rows, n, n, c, k, relu) == 0
         torch.cuda.synchronize()
         if relu:
             want = torch.fmax(v, torch.zeros((), device="cuda"))
@@ -392,7 +307,7 @@ def test_input_conv_relu_turns_nan_into_zero(elf):
             assert bool((y.float() == want).all())
             assert bool((y.view(torch.int16)[nan] == 0).all())      # +0, not -0
         else:
-            assert _differing(y, v) == 0 and torch.equal(torch.isnan(y), nan)
+            assert cc.differing(y, v) == 0 and torch.equal(torch.isnan(y), nan)
         assert bool(torch.isnan(buf[-1]).all())
 
 
@@ -411,8 +326,8 @@ def test_input_conv_negative_zero_passes_without_relu(elf):
     host = (torch.tensor(-2.0 ** -26, dtype=torch.float32).half().float() + torch.tensor(-0.0)).half()
     assert int(host.view(torch.int16).item()) == -32768
     for relu in (0, 1):
-        buf, y = _guarded(rows, n, n, k)
-        assert _conv_in(elf.lib(), x, w, b, y, rows, n, n, c, k, relu) == 0
+        buf, y = cc.guarded(rows, n, n, k)
+        assert cc.conv_in(elf.lib(), x, w, b, y, rows, n, n, c, k, relu) == 0
         torch.cuda.synchronize()
         assert bool((y.float() == 0).all())
         if not relu:
@@ -424,14 +339,6 @@ def test_input_conv_negative_zero_passes_without_relu(elf):
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # heads: reference and driver
-
-HEAD_NAMES = ("pconv_w", "pconv_b", "vconv_w", "vconv_b", "pi_w", "pi_b", "v1_w", "v1_b", "v2_w", "v2_b")
-
-
-def _heads_struct(t, ch, vh):
-    from elf_amd._lib import ElfNetHeads
-    return ElfNetHeads(*[t[nm].data_ptr() for nm in HEAD_NAMES], ch, vh)
-
 
 def _upload(a):
     """name -> fp16 device tensor of every array in `a`; every finite value must be an fp16 value"""
@@ -533,8 +440,9 @@ def _run_heads(L, t, ch, vh, rows, h, wd, stride=None, ws=None, ws_bytes=None):
     if ws is None:
         ws_bytes = L.elfnet_heads_workspace(rows, h, wd)
         ws = torch.empty((ws_bytes,), device="cuda", dtype=torch.uint8)
-    hd = _heads_struct(t, ch, vh)
-    rc = L.elfnet_heads_f16(_p(t["act"]), C.byref(hd), rows, h, wd, _p(pi), stride, _p(value), _p(logits), _p(ws), ws_bytes, _stream())
+    hd = cc.heads_struct(t, ch, vh)
+    rc = L.elfnet_heads_f16(cc.ptr(t["act"]), C.byref(hd), rows, h, wd, cc.ptr(pi), stride, cc.ptr(value), cc.ptr(logits), cc.ptr(ws),
+                            ws_bytes, cc.stream())
     torch.cuda.synchronize()
     return rc, pi, value, logits
 
@@ -607,9 +515,9 @@ def test_heads_guarded_operands_at_the_weakest_alignment(elf):
     assert rc == 0
     where = dict(act=(32, 16), pconv_w=(32, 16), vconv_w=(32, 16), pi_w=(8, 4))
     t = {}
-    for nm in ("act",) + HEAD_NAMES:
+    for nm in ("act",) + cc.HEAD_NAMES:
         mod, rem = where.get(nm, (4, 2))
-        t[nm], _, _ = _carve(plain[nm], 2 * (d + 1) + ch, mod, rem)
+        t[nm], _, _ = cc.carve(plain[nm], 2 * (d + 1) + ch, mod, rem)
         assert t[nm].data_ptr() % mod == rem
     sentinel = 0x5A5A5A5A
     need = rows * 3 * d
@@ -826,14 +734,14 @@ def test_input_conv_boards_do_not_depend_on_the_batch(elf):
     w = (torch.randn((k, 3, 3, c), device="cuda", generator=g) * (9 * c) ** -0.5).half()
     b = torch.randn((k,), device="cuda", generator=g).half()
     L = elf.lib()
-    _, y = _guarded(rows, n, n, k)
-    assert _conv_in(L, x, w, b, y, rows, n, n, c, k, 0) == 0
+    _, y = cc.guarded(rows, n, n, k)
+    assert cc.conv_in(L, x, w, b, y, rows, n, n, c, k, 0) == 0
     torch.cuda.synchronize()
     assert bool(torch.isfinite(y).all())
     for i in (0, 1, 205, 409):
-        buf, y1 = _guarded(1, n, n, k)
+        buf, y1 = cc.guarded(1, n, n, k)
         assert x[i].data_ptr() % 4 == 0
-        assert _conv_in(L, x[i], w, b, y1, 1, n, n, c, k, 0) == 0
+        assert cc.conv_in(L, x[i], w, b, y1, 1, n, n, c, k, 0) == 0
         torch.cuda.synchronize()
         assert torch.equal(y1[0].view(torch.int16), y[i].view(torch.int16)), i
         assert bool(torch.isnan(buf[-1]).all())

@@ -14,7 +14,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import conv_cases as cc
 import trained_like as tl
+from conv_cases import elf  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -28,12 +30,6 @@ ROUTES = {
     "native-small": ("NativeInferenceNet", dict(small_max_positions=1 << 20), ("elfnet_conv3x3_small_f16", None), False),
 }
 CASE_ROUTES = [(c[0], r) for c in tl.CASES for r in ROUTES if c[3] % 256 == 0 or not ROUTES[r][3]]
-
-
-@pytest.fixture(scope="module")
-def elf(built):
-    import elf_amd
-    return elf_amd
 
 
 class _Calls:
@@ -71,10 +67,6 @@ def _case(name):
     return _cases[name]
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _run(elf, name, route):
     """one call of the route with its `_conv` shadowed on the instance by a wrapper that clones (x, res, y) of every call.
     -> dict(inf, conv = its own `_conv`, out, rec = [(x, conv module, res, y)], acts = the activation after every trunk convolution, logits or None)"""
@@ -109,8 +101,8 @@ def _run(elf, name, route):
         pi, v, logits = nan(rows, d + 1), nan(rows), nan(rows, d + 1)
         nb = inf.L.elfnet_heads_workspace(rows, n, n)
         ws = torch.empty((nb,), device="cuda", dtype=torch.uint8)
-        inf.check(inf.L.elfnet_heads_f16(_p(acts[-1]), C.byref(inf.heads), rows, n, n, _p(pi), d + 1, _p(v), _p(logits), _p(ws), nb,
-                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        inf.check(inf.L.elfnet_heads_f16(cc.ptr(acts[-1]), C.byref(inf.heads), rows, n, n, cc.ptr(pi), d + 1, cc.ptr(v), cc.ptr(logits),
+                                         cc.ptr(ws), nb, cc.stream()))
         torch.cuda.synchronize()
         assert torch.equal(pi, out["pi"]) and torch.equal(v, out["V"])
     _runs[key] = dict(inf=inf, conv=inner, out=out, rec=rec, acts=acts, logits=logits, native=native)
