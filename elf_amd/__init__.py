@@ -7,7 +7,7 @@ Importing never touches oracle/ and never falls back to a CPU implementation.
 from ._lib import ElfGoError, lib  # noqa: F401
 from .engine import (  # noqa: F401
     GoEngine, M_PASS, M_RESIGN, M_SKIP, M_INVALID, M_CLEAR, S_EMPTY, S_BLACK, S_WHITE,
-    coord, coord_xy, coord2action, action2coord, d4_transform, d4_inv_transform,
+    coord, coord_xy, coord2action, action2coord, d4_transform, d4_inv_transform, NUM_AGZ_PLANES, NUM_DF_PLANES,
 )
 
 __version__ = "0.1"

@@ -52,6 +52,16 @@ SIGNATURES = {
     "elfgo_candidates": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "elfgo_playout_cand": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "elfgo_own_run_cand": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
+    "elfgo_df_create": (_i, [_vp, C.POINTER(_vp)]),
+    "elfgo_df_destroy": (_i, [_vp]),
+    "elfgo_df_reset": (_i, [_vp, _vp, _i, _vp]),
+    "elfgo_df_copy": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "elfgo_df_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "elfgo_df_setup": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "elfgo_df_extract": (_i, [_vp, _vp, _vp, _i, _vp, _i64, _vp]),
+    "elfgo_df_placed": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "elfgo_extract_df": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
+    "elfgo_df_exp_table": (_i, [_i, _vp]),
     "elfmcts_create": (_i, [_vp, _i, _i, _i, _vp, C.POINTER(_vp)]),
     "elfmcts_destroy": (_i, [_vp]),
     "elfmcts_set_options": (_i, [_vp, _vp]),

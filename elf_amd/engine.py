@@ -18,6 +18,7 @@ from ._lib import check
 M_PASS, M_RESIGN, M_SKIP, M_INVALID, M_CLEAR = 0, 1, 2, 3, 4  # base/common.h:43-47
 S_EMPTY, S_BLACK, S_WHITE, S_OFF_BOARD = 0, 1, 2, 3           # base/common.h:36-39
 NUM_AGZ_PLANES = 18                                           # base/board_feature.h:38
+NUM_DF_PLANES = 25                                            # base/board_feature.h:18
 INFO_WORDS = 16
 INFO_FIELDS = ("ply", "next_player", "last_move", "last_move2", "ko_age", "simple_ko", "simple_ko_color",
                "b_cap", "w_cap", "terminated", "superko", "hist_len", "sk_len", "hash_lo", "hash_hi")
@@ -78,9 +79,12 @@ def action2coord(n, d4, a):
 
 
 class GoEngine:
-    """A pool of `capacity` boards of one size resident in HBM on `device`."""
+    """A pool of `capacity` boards of one size resident in HBM on `device`.
+    track_placed=True keeps, beside the slots, the ply at which every stone was placed (an ElfGoDf handle, include/elf_amd.h):
+    reset / copy / setup / forward go through the elfgo_df_* forms, extract_df() and placed() work, and playout() -- which
+    plays on the slots without the table -- raises."""
 
-    def __init__(self, board_size=19, capacity=4096, device=0):
+    def __init__(self, board_size=19, capacity=4096, device=0, track_placed=False):
         if not torch.cuda.is_available():
             raise RuntimeError("elf_amd.GoEngine needs a ROCm GPU (no CPU fallback exists)")
         self.L = _lib.lib()
@@ -95,6 +99,11 @@ class GoEngine:
         h = C.c_void_p()
         check(self.L.elfgo_create(self.n, self.capacity, device, zz.ctypes.data, C.byref(h)))
         self._h = h
+        self._df = None
+        if track_placed:
+            d = C.c_void_p()
+            check(self.L.elfgo_df_create(self._h, C.byref(d)))
+            self._df = d
 
     @classmethod
     def borrow(cls, handle, board_size, capacity, device):
@@ -105,6 +114,7 @@ class GoEngine:
         self.num_action = self.n * self.n + 1
         self._h = C.c_void_p(handle)
         self._borrowed = True
+        self._df = None   # whoever owns the engine plays on it without a table
         return self
 
     def close(self):
@@ -112,6 +122,9 @@ class GoEngine:
             if getattr(self, "_own", None):
                 self.L.elfgo_own_destroy(self._own[1])
                 self._own = None
+            if getattr(self, "_df", None):
+                self.L.elfgo_df_destroy(self._df)
+                self._df = None
             if not getattr(self, "_borrowed", False):
                 self.L.elfgo_destroy(self._h)
             self._h = None
@@ -147,13 +160,19 @@ class GoEngine:
     # ---- GoState surface (batched)
     def reset(self, ids=None):
         t, p, k = self._ids(ids)
-        check(self.L.elfgo_reset(self._h, p, k, self._stream()))
+        if self._df:
+            check(self.L.elfgo_df_reset(self._df, p, k, self._stream()))
+        else:
+            check(self.L.elfgo_reset(self._h, p, k, self._stream()))
 
     def copy(self, dst_ids, src_ids):
         d, dp, k = self._ids(dst_ids)
         s, sp, k2 = self._ids(src_ids)
         assert k == k2
-        check(self.L.elfgo_copy(self._h, dp, sp, k, self._stream()))
+        if self._df:
+            check(self.L.elfgo_df_copy(self._df, dp, sp, k, self._stream()))
+        else:
+            check(self.L.elfgo_copy(self._h, dp, sp, k, self._stream()))
 
     def setup(self, stones, ids=None, next_player=None):
         """Put stones on boards (elfgo_setup): stones [k, N*N] or [N*N] uint8 (0 empty, 1 black, 2 white, index a = x*N + y --
@@ -171,8 +190,9 @@ class GoEngine:
                 npl = npl.repeat(k)
             assert npl.numel() == k
         ok = torch.empty(k, dtype=torch.uint8, device=self.device)
-        check(self.L.elfgo_setup(self._h, p, C.c_void_p(st.data_ptr()), C.c_void_p(npl.data_ptr()) if npl is not None else None, k,
-                                 C.c_void_p(ok.data_ptr()), self._stream()))
+        fn, h = (self.L.elfgo_df_setup, self._df) if self._df else (self.L.elfgo_setup, self._h)
+        check(fn(h, p, C.c_void_p(st.data_ptr()), C.c_void_p(npl.data_ptr()) if npl is not None else None, k,
+                 C.c_void_p(ok.data_ptr()), self._stream()))
         return ok
 
     def forward(self, ids, moves):
@@ -181,7 +201,8 @@ class GoEngine:
         t, p, k = self._ids(ids, mv.numel())
         assert k == mv.numel()
         ok = torch.empty(k, dtype=torch.uint8, device=self.device)
-        check(self.L.elfgo_forward(self._h, p, C.c_void_p(mv.data_ptr()), k, C.c_void_p(ok.data_ptr()), self._stream()))
+        fn, h = (self.L.elfgo_df_forward, self._df) if self._df else (self.L.elfgo_forward, self._h)
+        check(fn(h, p, C.c_void_p(mv.data_ptr()), k, C.c_void_p(ok.data_ptr()), self._stream()))
         return ok
 
     def legal_mask(self, ids=None, n=None):
@@ -210,6 +231,34 @@ class GoEngine:
         assert tuple(out.stride()[1:]) == inner, "rows must be %s" % ("channels_last" if f16 else "contiguous [18,N,N]")
         stride = out.stride(0) if out.shape[0] > 1 else row
         check(self.L.elfgo_extract_agz_fmt(self._h, p, dp, k, C.c_void_p(out.data_ptr()), stride, 1 if f16 else 0, self._stream()))
+        return out
+
+    def extract_df(self, ids=None, d4=None, out=None, n=None):
+        """BoardFeature::extract, the reference's 25 DarkForest planes (liberty classes, simple ko, stones, exponential move
+        history, distance maps, colour indicators; include/elf_amd.h lists them), into `out` [k,25,N,N] float32 (allocated if
+        None; rows contiguous [25,N,N], any row stride).  A row whose slot id lies outside the pool is all zero.  Needs
+        track_placed=True: the history planes read the ply at which each stone was placed."""
+        if not self._df:
+            raise ValueError("extract_df needs GoEngine(..., track_placed=True)")
+        t, p, k = self._ids(ids, n)
+        d, dp = self._i32(d4, k)
+        row = NUM_DF_PLANES * self.n * self.n
+        if out is None:
+            out = torch.empty((k, NUM_DF_PLANES, self.n, self.n), dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.shape[0] >= k and out.dtype == torch.float32
+        assert tuple(out.stride()[1:]) == (self.n * self.n, self.n, 1), "rows must be contiguous [25,N,N]"
+        stride = out.stride(0) if out.shape[0] > 1 else row
+        check(self.L.elfgo_df_extract(self._df, p, dp, k, C.c_void_p(out.data_ptr()), stride, self._stream()))
+        return out
+
+    def placed(self, ids=None, n=None):
+        """-> int16 tensor [k, N*N], index a = x*N + y: the ply at which the stone on the point was placed (Info::last_placed);
+        entries of empty points are stale or 0.  Needs track_placed=True."""
+        if not self._df:
+            raise ValueError("placed needs GoEngine(..., track_placed=True)")
+        t, p, k = self._ids(ids, n)
+        out = torch.empty((k, self.n * self.n), dtype=torch.int16, device=self.device)
+        check(self.L.elfgo_df_placed(self._df, p, k, C.c_void_p(out.data_ptr()), self._stream()))
         return out
 
     def evaluate(self, ids=None, komi=7.5, n=None):
@@ -255,6 +304,8 @@ class GoEngine:
         hash_lo, hash_hi, ply, steps.
         self_atari_thres=t plays from the reference's FindAllCandidateMoves(board, player, t) instead (elfgo_playout_cand): the
         same list minus the self-ataris of t stones or more; None is elfgo_playout itself."""
+        if self._df:
+            raise ValueError("playout plays on the slots without the placement table: not on a track_placed engine")
         sd, t, p, k = self._seeds(seeds, ids)
         if out is None:
             out = torch.empty((k, 4), dtype=torch.int32, device=self.device)

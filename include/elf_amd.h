@@ -166,6 +166,52 @@ int elfgo_playout_cand(ElfGoEngine* e, const int32_t* ids, const uint64_t* seeds
 int elfgo_own_run_cand(ElfGoOwnership* o, const int32_t* ids, const uint64_t* seeds, int n, int playouts, int max_steps,
                        float komi, int self_atari_thres, int32_t* counts, int64_t* stats, void* stream);
 
+/* The reference's 25 DarkForest planes (BoardFeature::extract, base/board_feature.cc:43-237; what GameOptions.use_df_feature
+ * selects there) of board slots: fp32 [25][N][N] per row under D4 code d4[i], "ours" = the side to move:
+ *    0-2 / 3-5  our / the opponent's stones of groups with 1, 2, >= 3 liberties (getLibertyMap3binary)
+ *    6          the simple-ko point, whichever colour it binds (getSimpleKoLocation, board.cc:466-474)
+ *    7 / 8 / 9  our stones, the opponent's, empty points
+ *    10 / 11    on our / the opponent's stones (float)exp((last_placed - ply) / 10.0), last_placed = the ply at which the stone
+ *               was placed (getHistoryExp); bit-equal to the reference: the values come from elfgo_df_exp_table's table
+ *    14 / 15    Manhattan distance to our / the opponent's nearest stone, 0 on the stones, 10000 everywhere when the colour
+ *               has none (getDistanceMap)
+ *    16 / 17    all 1.0 when Black / White is to move
+ *    12, 13, 18-24  zero
+ * Planes 10 / 11 need Info::last_placed, which a board slot does not carry.  An ElfGoDf handle keeps it beside an engine: a
+ * table uint16 [capacity][N*N] in action order (a = x*N + y), zeroed at creation, plus the device copy of the exponent table.
+ * The elfgo_df_reset / _copy / _forward / _setup forms are the engine's calls of the same name (same arguments, same results,
+ * same stream) followed by the table's part: rows to 0; rows copied; ply p under the stone of an accepted placement at ply p
+ * (a pass, a resignation and a refused move change nothing; captured points keep their entry, which nothing reads: the
+ * reference only reads entries under stones); after an accepted set-up 1 under every stone and 0 elsewhere (PlaceHandicap
+ * plays at ply 1 and puts the ply back, board.cc:109-126), a refused row untouched.  ok may be NULL as in the engine's calls,
+ * then n must not exceed the capacity.
+ * THE TABLE FOLLOWS ONLY THESE FOUR CALLS.  Anything else that plays on the engine's slots leaves it stale: elfgo_reset /
+ * _copy / _forward / _setup called without the handle, every elfgo_playout* call, and the self-play / MCTS contexts that
+ * borrow an engine (elfsp_*, elfmcts_*).  Several handles may share an engine; destroy a handle before its engine. */
+typedef struct ElfGoDf ElfGoDf;
+int elfgo_df_create(ElfGoEngine* e, ElfGoDf** out);
+int elfgo_df_destroy(ElfGoDf* df);
+int elfgo_df_reset(ElfGoDf* df, const int32_t* ids, int n, void* stream);
+int elfgo_df_copy(ElfGoDf* df, const int32_t* dst_ids, const int32_t* src_ids, int n, void* stream);
+int elfgo_df_forward(ElfGoDf* df, const int32_t* ids, const int32_t* moves, int n, uint8_t* ok, void* stream);
+int elfgo_df_setup(ElfGoDf* df, const int32_t* ids, const uint8_t* stones, const uint8_t* next_player, int n, uint8_t* ok,
+                   void* stream);
+/* dst[i] = the 25 planes of slot ids[i] with that slot's table row; consecutive rows are stride_floats apart (>= 25*N*N; dst
+ * 4-byte aligned, rows need no further alignment).  d4 NULL = code 0, ids NULL = slots [0, n).  A row whose slot id lies
+ * outside the pool is all zero.  The slots and the table are only read; a slot may be named several times. */
+int elfgo_df_extract(ElfGoDf* df, const int32_t* ids, const int32_t* d4, int n, float* dst, int64_t stride_floats, void* stream);
+/* out[i] = the table row of slot ids[i] (uint16 [n][N*N]; zero for an id outside the pool) */
+int elfgo_df_placed(ElfGoDf* df, const int32_t* ids, int n, uint16_t* out, void* stream);
+/* The same kernel for callers that keep last_placed themselves: row i of placed_rows (uint16 [n][N*N], device) serves
+ * ids[i].  It takes the handle and not the engine because the exponent table on the device belongs to the handle (an engine
+ * carries no DarkForest state at all); the handle's own table is not read. */
+int elfgo_extract_df(ElfGoDf* df, const int32_t* ids, const int32_t* d4, int n, const uint16_t* placed_rows, float* dst,
+                     int64_t stride_floats, void* stream);
+/* Host only, no GPU needed: out_host[d] = (float)exp((0 - d) / 10.0) for d in [0, 2*N*N], 2*N*N + 1 floats -- the reference's own
+ * expression through the C library's double exp, evaluated once per handle; the kernel looks planes 10 / 11 up at
+ * d = ply - last_placed.  ELFGO_E_BADSIZE for a board size other than 19 or 9. */
+int elfgo_df_exp_table(int board_size, float* out_host);
+
 /* ------------------------------------------------------------------------------------------------
  * Device-resident MCTS (one tree per game) -- replaces, behind the same seams, the reference's
  *   elf/ai/tree_search/tree_search.h        TreeSearchT / TreeSearchSingleThreadT::batch_rollouts (:200-262)
