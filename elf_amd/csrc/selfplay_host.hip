@@ -1316,6 +1316,9 @@ int elfsp_search_log(const ElfSelfPlay* sp, int first, int n, ElfSpSearch* rec, 
 // k_playout_cand in candidates.cuh over the shared playout of playout.cuh, entry points in candidates_host.h (the ownership one
 // is ownership_host.h's own_run under CandPolicy), here for the same reason.
 #include "candidates_host.h"
+// Eye classes, two-eye life reading and the fast score (elfgo_life_map): k_life_map in life.cuh, entry point in life_host.h, here
+// for the same reason.
+#include "life_host.h"
 // DarkForest features (elfgo_df_*, elfgo_extract_df): k_extract_df and the placement-ply table's kernels in df_features.cuh,
 // entry points in df_host.h, here for the same reason.
 #include "df_host.h"

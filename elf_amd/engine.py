@@ -78,6 +78,24 @@ def action2coord(n, d4, a):
     return coord(n, x, y)
 
 
+SUMMARY_FIELDS = ("score_chinese", "score_japanese", "black_lives", "white_lives", "left", "top", "right", "bottom", "attacker",
+                  "living_black", "living_white", "reserved")
+EYE, FAKE_EYE, TRUE_EYE, SEMI_EYE = 1, 2, 4, 8   # Black's bits of LifeMap.eye; White's are these << 4
+
+
+class LifeMap:
+    """What GoEngine.life_map returns: the device tensors of elfgo_life_map, and getEyeColor derived from them."""
+
+    def __init__(self, eye, semi_move, alive, summary):
+        self.eye, self.semi_move, self.alive, self.summary = eye, semi_move, alive, summary
+
+    @property
+    def eye_colour(self):
+        """getEyeColor (base/board.cc:1916-1922) per point: 2 where it is White's true eye (asked first), 1 where Black's, else 0"""
+        white, black = (self.eye & (TRUE_EYE << 4)) != 0, (self.eye & TRUE_EYE) != 0
+        return white.to(torch.uint8) * 2 + (black & ~white).to(torch.uint8)
+
+
 class GoEngine:
     """A pool of `capacity` boards of one size resident in HBM on `device`.
     track_placed=True keeps, beside the slots, the ply at which every stone was placed (an ElfGoDf handle, include/elf_amd.h):
@@ -348,6 +366,50 @@ class GoEngine:
         check(self.L.elfgo_candidates(self._h, p, k, int(self_atari_thres), C.c_void_p(mask.data_ptr()), C.c_void_p(stones.data_ptr()),
                                       self._stream()))
         return mask, stones
+
+    def life_map(self, ids=None, n=None, regions=None):
+        """The reference's static life reading of each position, both colours at once (elfgo_life_map) -> LifeMap with device
+        tensors, index a = x*N + y:
+          eye uint8 [k, N*N]: Black's answers in bits 0-3, White's in bits 4-7: bit 0 isEye, 1 isFakeEye, 2 isTrueEye, 3 isSemiEye
+            (base/board.cc:1850-1914); isFakeEye is answered at every point, the others are 0 off empty points;
+          semi_move int16 [k, 2, N*N]: the action isSemiEye names where it holds for Black / White, else -1;
+          alive uint8 [k, N*N]: 1 on the stones of groups that live by two eyes (GivenGroupLives, board.cc:1108-1181);
+          summary int32 [k, 12]: see SUMMARY_FIELDS (getFastScore under both rules, OneGroupLives per colour over the box, the
+            box, GuessLDAttacker, living groups per colour in the box);
+          eye_colour uint8 [k, N*N]: getEyeColor (0 / 1 / 2), derived from eye.
+        regions: a host sequence of k boxes (left, top, right, bottom), half-open in x and y as the reference's Region; None =
+        getBoardBBox of each row.  A box outside 0 <= left <= right <= N, 0 <= top <= bottom <= N raises ValueError before
+        anything is launched.  A row whose slot id lies outside the pool gets maps 0, semi_move -1 and summary -1."""
+        t, p, k = self._ids(ids, n)
+        reg = None
+        if regions is not None:
+            r = np.asarray(regions, dtype=np.int64).reshape(-1, 4)
+            if r.shape[0] != k:
+                raise ValueError("regions must hold one box per row (%d), got %d" % (k, r.shape[0]))
+            ok = (0 <= r[:, 0]) & (r[:, 0] <= r[:, 2]) & (r[:, 2] <= self.n) & (0 <= r[:, 1]) & (r[:, 1] <= r[:, 3]) & (r[:, 3] <= self.n)
+            if not ok.all():
+                raise ValueError("box %s of row %d is not inside 0 <= left <= right <= N, 0 <= top <= bottom <= N"
+                                 % (tuple(int(v) for v in r[int(np.nonzero(~ok)[0][0])]), int(np.nonzero(~ok)[0][0])))
+            reg = torch.from_numpy(np.ascontiguousarray(r, dtype=np.int32)).to(self.device)
+        np_ = self.n * self.n
+        eye = torch.empty((k, np_), dtype=torch.uint8, device=self.device)
+        semi = torch.empty((k, 2, np_), dtype=torch.int16, device=self.device)
+        alive = torch.empty((k, np_), dtype=torch.uint8, device=self.device)
+        summary = torch.empty((k, len(SUMMARY_FIELDS)), dtype=torch.int32, device=self.device)
+        check(self.L.elfgo_life_map(self._h, p, k, C.c_void_p(reg.data_ptr()) if reg is not None else None, C.c_void_p(eye.data_ptr()),
+                                    C.c_void_p(semi.data_ptr()), C.c_void_p(alive.data_ptr()), C.c_void_p(summary.data_ptr()),
+                                    self._stream()))
+        return LifeMap(eye, semi, alive, summary)
+
+    def fast_score(self, ids=None, n=None, rule="chinese"):
+        """getFastScore (base/board.cc:1924-1952) from Black's side -> int32 tensor [k]: stones plus true eyes under "chinese",
+        true eyes plus captures under "japanese"; no komi, as in the reference."""
+        if rule not in ("chinese", "japanese"):
+            raise ValueError("rule must be 'chinese' or 'japanese'")
+        t, p, k = self._ids(ids, n)
+        summary = torch.empty((k, len(SUMMARY_FIELDS)), dtype=torch.int32, device=self.device)
+        check(self.L.elfgo_life_map(self._h, p, k, None, None, None, None, C.c_void_p(summary.data_ptr()), self._stream()))
+        return summary[:, 0 if rule == "chinese" else 1].contiguous()
 
     def ownership(self, seeds, ids=None, playouts=256, komi=7.5, max_steps=1 << 20, max_lanes=0, self_atari_thres=None):
         """Monte-Carlo ownership: `playouts` config-2 playouts from a private copy of each listed slot (the slots themselves are

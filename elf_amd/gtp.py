@@ -7,7 +7,8 @@ same replies ("= ..." / "? ..."), same coordinate letters (no 'I'): protocol_ver
 clear_board, play, genmove, showboard, final_score, list_commands, quit/exit.  On top of the reference's set (whose `u` / `h`
 commands are commented out, console_lib.py:196-204): undo, fixed_handicap, place_free_handicap, set_free_handicap, loadsgf,
 known_command -- what every GTP front-end sends -- over SelfPlay.setup / SelfPlay.undo; final_status_list and the private
-elf-ownership, elf-score_estimate, elf-ladders and elf-candidates over the per-point answers of the board engine; lz-genmove_analyze (Leela Zero's
+elf-ownership, elf-score_estimate, elf-ladders, elf-candidates, elf-eyes, elf-life and elf-fast_score over the per-point answers of
+the board engine; lz-genmove_analyze (Leela Zero's
 analysing genmove, what Sabaki and Lizzie send) and elf-analysis over the search's candidates and lines (SelfPlay.analyze).
 
     eng = GtpEngine(actor, board_size=19, mcts_rollout_per_thread=1600)     # actor(batch) -> dict(pi=..., V=...)
@@ -17,7 +18,7 @@ import inspect
 import sys
 
 from ._lib import ElfGoError
-from .engine import M_PASS
+from .engine import M_PASS, SEMI_EYE, TRUE_EYE
 
 M_RESIGN = 1   # base/common.h:44
 from .selfplay import SelfPlay
@@ -95,6 +96,9 @@ class GtpEngine:
         self.commands["elf-score_estimate"] = self.commands.pop("elf_score_estimate")
         self.commands["elf-ladders"] = self.commands.pop("elf_ladders")
         self.commands["elf-candidates"] = self.commands.pop("elf_candidates")
+        self.commands["elf-eyes"] = self.commands.pop("elf_eyes")
+        self.commands["elf-life"] = self.commands.pop("elf_life")
+        self.commands["elf-fast_score"] = self.commands.pop("elf_fast_score")
         self.commands["elf-analysis"] = self.commands.pop("elf_analysis")
         self.commands["lz-genmove_analyze"] = self.commands.pop("lz_genmove_analyze")
         # every finished search leaves its candidates and lines behind (elf-analysis): one small launch per move of one game
@@ -430,6 +434,39 @@ class GtpEngine:
         mask, stones = [t.cpu().numpy()[0] for t in self.boards.candidates(ids=[0], self_atari_thres=thres)]
         return True, " ".join(xy2move(a // self.n, a % self.n) + (":%d" % int(stones[a]) if stones[a] > 0 else "")
                               for a in range(self.n * self.n) if mask[a])
+
+    # ---- static life reading (GoEngine.life_map on game 0's current position)
+    def _vertex(self, a):
+        return xy2move(a // self.n, a % self.n)
+
+    def on_elf_eyes(self, items):
+        """The eyes of both colours in board order (a = x*N + y), like elf-ladders: VERTEX:b / VERTEX:w for a true eye (isTrueEye),
+        VERTEX:b?MOVE / VERTEX:w?MOVE for a semi-eye (isSemiEye: MOVE is the diagonal point that settles it); a point that is both
+        is listed both ways; empty if there is none."""
+        lm = self.boards.life_map(ids=[0])
+        eye, semi = lm.eye.cpu().numpy()[0], lm.semi_move.cpu().numpy()[0]
+        out = []
+        for a in range(self.n * self.n):
+            for c, tag in ((0, "b"), (1, "w")):
+                bits = int(eye[a]) >> (4 * c)
+                if bits & TRUE_EYE:
+                    out.append("%s:%s" % (self._vertex(a), tag))
+                if bits & SEMI_EYE:
+                    out.append("%s:%s?%s" % (self._vertex(a), tag, self._vertex(int(semi[c, a]))))
+        return True, " ".join(out)
+
+    def on_elf_life(self, items):
+        """The stones of the groups that live by two eyes (GivenGroupLives), in board order; a proof for the groups it lists, and
+        silent about every other group."""
+        alive = self.boards.life_map(ids=[0]).alive.cpu().numpy()[0]
+        return True, " ".join(self._vertex(a) for a in range(self.n * self.n) if alive[a])
+
+    def on_elf_fast_score(self, items):
+        """elf-fast_score [chinese|japanese]: getFastScore from Black's side, an integer; no komi is applied, as in the reference."""
+        rule = items[1] if len(items) > 1 else "chinese"
+        if rule not in ("chinese", "japanese"):
+            return False, "invalid rule"
+        return True, "%d" % int(self.boards.fast_score(ids=[0], rule=rule).cpu()[0])
 
     def on_list_commands(self, items):
         return True, "\n".join(self.commands.keys())

@@ -166,6 +166,30 @@ int elfgo_playout_cand(ElfGoEngine* e, const int32_t* ids, const uint64_t* seeds
 int elfgo_own_run_cand(ElfGoOwnership* o, const int32_t* ids, const uint64_t* seeds, int n, int playouts, int max_steps,
                        float komi, int self_atari_thres, int32_t* counts, int64_t* stats, void* stream);
 
+/* The reference's static life reading of a position, for both colours at once: eye classes (isEye, isFakeEye, isSemiEye,
+ * isTrueEye, getEyeColor, base/board.cc:1850-1922), groups that live by two eyes (GivenGroupLives / OneGroupLives,
+ * board.cc:1108-1221), the eye-and-stone score (getFastScore, board.cc:1924-1952) and the framing of a life-and-death problem
+ * (getBoardBBox, GuessLDAttacker, board.cc:1024-1106).  Per row i, a = x*N + y:
+ *     eye[i][a]          uint8: Black's answers in bits 0-3, White's in bits 4-7: bit 0 isEye, 1 isFakeEye, 2 isTrueEye,
+ *                        3 isSemiEye.  isFakeEye is answered at every point, stones included, as the reference function answers
+ *                        there; the other three are 0 off empty points.  None depends on legality or on a pending ko.
+ *     semi_move[i][c][a] int16, c = 0 Black / 1 White: the action of the *move isSemiEye writes where it returns true for that
+ *                        colour (the one empty diagonal that is no eye of the colour), else -1
+ *     alive[i][a]        uint8: 1 on every stone of a group for which GivenGroupLives holds (two true eyes of its colour next
+ *                        to THIS group, each with enough territory on its diagonals, and more than one liberty), else 0
+ *     summary[i]         int32 [12]: 0 getFastScore(RULE_CHINESE), 1 getFastScore(RULE_JAPANESE) (the slot's captures; the
+ *                        reference never writes _rollout_passes, so it is 0), 2 / 3 OneGroupLives(Black / White, box),
+ *                        4-7 the box left, top, right, bottom, 8 GuessLDAttacker(box) (1 Black, 2 White; White on a tie),
+ *                        9 / 10 living Black / White groups with a stone in the box, 11 zero (reserved)
+ * The box is the reference's half-open Region in x and y: regions int32 [n][4] (left, top, right, bottom), each value clamped
+ * into [0, N]; NULL = getBoardBBox of the row ((N, N, 0, 0) on an empty board: attacker White, nothing lives).  The scores are
+ * integers as the reference computes them; no komi.  Device pointers, row strides N*N, 2*N*N, N*N and 12; each output may be
+ * NULL, not all four.  ids NULL = slots [0, n).  A row whose slot id lies outside the pool gets maps 0, semi_move -1 and summary
+ * all -1.  The slots are only read; a slot may be named several times.  ELFGO_E_BADARG for a null engine, n <= 0, ids NULL with
+ * n above the capacity, or all four outputs NULL: nothing is launched. */
+int elfgo_life_map(ElfGoEngine* e, const int32_t* ids, int n, const int32_t* regions, uint8_t* eye, int16_t* semi_move,
+                   uint8_t* alive, int32_t* summary, void* stream);
+
 /* The reference's 25 DarkForest planes (BoardFeature::extract, base/board_feature.cc:43-237; what GameOptions.use_df_feature
  * selects there) of board slots: fp32 [25][N][N] per row under D4 code d4[i], "ours" = the side to move:
  *    0-2 / 3-5  our / the opponent's stones of groups with 1, 2, >= 3 liberties (getLibertyMap3binary)
