@@ -53,6 +53,8 @@ SIGNATURES = {
     "elfgo_playout_cand": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "elfgo_own_run_cand": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "elfgo_life_map": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "elfgo_region_moves": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "elfgo_ld_run": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "elfgo_df_create": (_i, [_vp, C.POINTER(_vp)]),
     "elfgo_df_destroy": (_i, [_vp]),
     "elfgo_df_reset": (_i, [_vp, _vp, _i, _vp]),

@@ -20,6 +20,8 @@
 //   box:    the region of OneGroupLives / GuessLDAttacker; getBoardBBox of the position when the caller gives none.  The
 //           attacker scan is one pass over the N steps of a line: lanes 0..31 take the rows of the box, lanes 32..63 its columns,
 //           each remembers the first and the last stone of its line inside the box.
+//   shared: the eye count of GivenGroupLives, the bounding box and the attacker scan are functions (life_count_eyes, life_bbox,
+//           life_attacker_counts) that k_playout_ld (region.cuh) calls too, beside life_true_eyes for callers that want no more.
 #pragma once
 #include "go_board.cuh"
 #include "engine_host.h"
@@ -39,6 +41,134 @@ __device__ __forceinline__ void life_diag4(const Board<N>& bd, u64 X, u64& d1, u
 __device__ __forceinline__ u64 life_ge1(u64 a, u64 b, u64 c, u64 d) { return a | b | c | d; }
 __device__ __forceinline__ u64 life_ge2(u64 a, u64 b, u64 c, u64 d) { return (a & b) | (c & d) | ((a | b) & (c | d)); }
 
+// The true eyes of both colours (isTrueEye, board.cc:1850-1914) of the board's current stones: k_life_map's eye algebra without
+// the fake / semi classes it also reports, for callers that only want GivenGroupLives (region.cuh).
+template <int N>
+__device__ __forceinline__ void life_true_eyes(const Board<N>& bd, u64& trueB, u64& trueW) {
+  const u64 B = bd.Bw, W = bd.Ww;
+  const u64 E = ~(B | W) & bd.mValid;
+  u64 nearEW, nearEB;
+  bd.dilate2(E | W, E | B, nearEW, nearEB);
+  const u64 eyeB = E & ~nearEW, eyeW = E & ~nearEB;
+  u64 w1, w2, w3, w4, b1, b2, b3, b4;
+  life_diag4<N>(bd, W, w1, w2, w3, w4);
+  life_diag4<N>(bd, B, b1, b2, b3, b4);
+  const u64 edge = bd.mEdge, inner = bd.mValid & ~bd.mEdge;
+  trueB = eyeB & ~((edge & life_ge1(w1, w2, w3, w4)) | (inner & life_ge2(w1, w2, w3, w4)));
+  trueW = eyeW & ~((edge & life_ge1(b1, b2, b3, b4)) | (inner & life_ge2(b1, b2, b3, b4)));
+}
+
+// The three functions below take the lane index as an argument, like Board::init: a kernel that calls them inside a loop
+// (k_playout_ld) passes an opaque copy, which keeps their per-lane constants from being hoisted and held across the loop.
+// getBoardBBox (:1024-1038) of the board's current stones; span[2] (LDS, this wave's) holds 0 on entry.
+template <int N>
+__device__ __forceinline__ void life_bbox(const Board<N>& bd, int lane, u32* span, int& left, int& top, int& right, int& bottom) {
+  using G = Geo<N>;
+  constexpr int R = G::R;
+  const u64 occ = bd.Bw | bd.Ww;
+  u32 xs = 0, ys = 0;
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    const u32 a = (u32)(k * 64 + lane);
+    const u32 x = __umul24(a, (u32)G::DN_M) >> G::DN_S, y = a - __umul24(x, (u32)N);
+    if (lane_bit(rl64(occ, k))) { xs |= 1u << x; ys |= 1u << y; }
+  }
+  if (xs) { atomicOr(&span[0], xs); atomicOr(&span[1], ys); }
+  Board<N>::wsync();
+  const u32 sx = (u32)rfl((int)span[0]), sy = (u32)rfl((int)span[1]);
+  left = sx ? (int)__builtin_ctz(sx) : N; right = sx ? 32 - (int)__builtin_clz(sx) : 0;
+  top = sy ? (int)__builtin_ctz(sy) : N; bottom = sy ? 32 - (int)__builtin_clz(sy) : 0;
+}
+
+// GivenGroupLives' eye count (:1108-1181), per (true eye, neighbour group): cnt[root] += 1 per qualifying eye of the group.
+// cnt[G::PP] and te[G::PP] (LDS, this wave's) hold 0 on entry; te ends as 1 / 2 on the true eyes of Black / White.
+template <int N>
+__device__ __forceinline__ void life_count_eyes(const Board<N>& bd, int lane, u64 trueB, u64 trueW, u32* cnt, unsigned char* te) {
+  using G = Geo<N>;
+  constexpr int R = G::R, S = G::S;
+  const Slot<N>* const L = bd.L;
+  const u64 T = trueB | trueW;
+  if (bal_ne64(T, 0ull)) {
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      if (lane_bit(rl64(trueB, k))) te[bd.idx[k]] = 1;
+      if (lane_bit(rl64(trueW, k))) te[bd.idx[k]] = 2;
+    }
+    Board<N>::wsync();
+#pragma unroll 1
+    for (int k = 0; k < R; ++k) {
+      const u64 tk = rl64(T, k);
+      if (tk == 0) continue;
+      if (lane_bit(tk)) {
+        const u32 a = (u32)(k * 64 + lane);
+        const int p = (int)(a + S + 1 + 2 * (__umul24(a, (u32)G::DN_M) >> G::DN_S));
+        const u32 mine = te[p];                          // 1 / 2
+        const u32 cb = mine == 2 ? 0x8000u : 0u;
+        // the four neighbours are own stones or border (label 0x8000: root 0)
+        const u32 g0 = L->pt[p - S], g1 = L->pt[p - 1], g2 = L->pt[p + S], g3 = L->pt[p + 1];
+        int off = 0, own = 0;
+        // the neighbour labels of a diagonal that is a true eye of the colour, else 0 (no stone carries label 0): two of its
+        // neighbours are neighbours of this eye too (read above), the two on its far sides are read here
+        u32 dn[4][4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int sx = (q & 2) ? S : -S, sy = (q & 1) ? 1 : -1;
+          const int dp = p + sx + sy;
+          const u32 dv = L->pt[dp];
+          dn[q][0] = dn[q][1] = dn[q][2] = dn[q][3] = 0;
+          if (dv == PT_BORDER) off++;
+          else if (dv == 0) {
+            if (te[dp] == mine) { dn[q][0] = (q & 2) ? g2 : g0; dn[q][1] = (q & 1) ? g3 : g1; dn[q][2] = L->pt[dp + sx]; dn[q][3] = L->pt[dp + sy]; }
+          } else if ((dv & 0x8000u) == cb) own++;
+        }
+        const u32 gs[4] = {g0, g1, g2, g3};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const u32 g = gs[j];
+          bool first = (g & 0x7FFFu) != 0;               // not the border
+#pragma unroll
+          for (int i = 0; i < j; ++i) first = first && gs[i] != g;   // an eye touched by several stones of the group counts once
+          if (first) {
+            int terr = own;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) terr += (dn[q][0] == g || dn[q][1] == g || dn[q][2] == g || dn[q][3] == g) ? 1 : 0;
+            const bool ok = off >= 1 ? (off + terr == 4) : (terr >= 3);
+            if (ok) atomicAdd(&cnt[g & 0x7FFFu], 1u);
+          }
+        }
+      }
+    }
+    Board<N>::wsync();
+  }
+}
+
+// GuessLDAttacker's two counts (:1040-1106) over the box: lanes 0..31 the rows of the box (fixed y, x runs), lanes 32..63 its columns
+template <int N>
+__device__ __forceinline__ void life_attacker_counts(const Board<N>& bd, int lane, int left, int top, int right, int bottom, int& black, int& white) {
+  constexpr int S = Geo<N>::S;
+  const Slot<N>* const L = bd.L;
+  black = 0; white = 0;
+  const int t = lane & 31;
+  const bool col = lane >= 32;
+  const bool active = col ? (t >= left && t < right) : (t >= top && t < bottom);
+  const int lo = col ? top : left, hi = col ? bottom : right;
+  u32 first = 0, last = 0;
+#pragma unroll   // the N reads are independent: all in flight before the first is consumed
+  for (int s = 0; s < N; ++s) {
+    const bool in = active && s >= lo && s < hi;
+    const int x = col ? t : s, y = col ? s : t;
+    const u32 v = L->pt[in ? (x + 1) * S + (y + 1) : 0];   // pt[0] is a border point
+    const u32 c = (in && (v & 0x7FFFu) != 0) ? ((v & 0x8000u) ? (u32)S_WHITE : (u32)S_BLACK) : 0u;
+    if (c) { if (!first) first = c; last = c; }
+  }
+  const u64 rows = 0xFFFFFFFFull, cols = ~rows;
+  const u64 fB = bal_eq(first, (u32)S_BLACK), fW = bal_eq(first, (u32)S_WHITE), lB = bal_eq(last, (u32)S_BLACK), lW = bal_eq(last, (u32)S_WHITE);
+  if (left > 0) { black += __popcll(fB & rows); white += __popcll(fW & rows); }
+  if (top > 0) { black += __popcll(fB & cols); white += __popcll(fW & cols); }
+  if (right < N) { black += __popcll(lB & rows); white += __popcll(lW & rows); }
+  if (bottom < N) { black += __popcll(lB & cols); white += __popcll(lW & cols); }
+}
+
 // eye [n][NP] uint8: Black's answers in bits 0-3, White's in bits 4-7: 1 isEye, 2 isFakeEye, 4 isTrueEye, 8 isSemiEye.
 // semi_move [n][2][NP] int16: the action of isSemiEye's *move where it returns true for that colour, else -1.
 // alive [n][NP] uint8: 1 on every stone of a group for which GivenGroupLives holds.  summary [n][12] int32: see include/elf_amd.h.
@@ -48,7 +178,7 @@ template <int N>
 __global__ __launch_bounds__(LIFE_WAVE) void k_life_map(Pool<N> pool, int capacity, const int32_t* ids, int n, const int32_t* regions,
                                                          uint8_t* eye, int16_t* semi_move, uint8_t* alive, int32_t* summary) {
   using G = Geo<N>;
-  constexpr int R = G::R, S = G::S, NP = G::NP;
+  constexpr int R = G::R, NP = G::NP;
   __shared__ Slot<N> lds;
   __shared__ u32 cnt[G::PP];             // per root: qualifying eyes (low half), bit 16 / 17: a living black / white stone of the group is in the box
   __shared__ unsigned char te[G::PP];    // per point (LDS index): 1 / 2 = true eye of Black / White
@@ -152,75 +282,11 @@ __global__ __launch_bounds__(LIFE_WAVE) void k_life_map(Pool<N> pool, int capaci
     const int c = v < 0 ? 0 : v > N ? N : v;
     left = rl(c, 0); top = rl(c, 1); right = rl(c, 2); bottom = rl(c, 3);
   } else {
-    const u64 occ = B | W;
-    u32 xs = 0, ys = 0;
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      const u32 a = (u32)(k * 64 + lane);
-      const u32 x = __umul24(a, (u32)G::DN_M) >> G::DN_S, y = a - __umul24(x, (u32)N);
-      if (lane_bit(rl64(occ, k))) { xs |= 1u << x; ys |= 1u << y; }
-    }
-    if (xs) { atomicOr(&span[0], xs); atomicOr(&span[1], ys); }
-    Board<N>::wsync();
-    const u32 sx = (u32)rfl((int)span[0]), sy = (u32)rfl((int)span[1]);
-    left = sx ? (int)__builtin_ctz(sx) : N; right = sx ? 32 - (int)__builtin_clz(sx) : 0;
-    top = sy ? (int)__builtin_ctz(sy) : N; bottom = sy ? 32 - (int)__builtin_clz(sy) : 0;
+    life_bbox<N>(bd, lane, span, left, top, right, bottom);
   }
 
   // ---- GivenGroupLives (:1108-1181), per (true eye, neighbour group)
-  const u64 T = trueB | trueW;
-  if (bal_ne64(T, 0ull)) {
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      if (lane_bit(rl64(trueB, k))) te[bd.idx[k]] = 1;
-      if (lane_bit(rl64(trueW, k))) te[bd.idx[k]] = 2;
-    }
-    Board<N>::wsync();
-#pragma unroll 1
-    for (int k = 0; k < R; ++k) {
-      const u64 tk = rl64(T, k);
-      if (tk == 0) continue;
-      if (lane_bit(tk)) {
-        const u32 a = (u32)(k * 64 + lane);
-        const int p = (int)(a + S + 1 + 2 * (__umul24(a, (u32)G::DN_M) >> G::DN_S));
-        const u32 mine = te[p];                          // 1 / 2
-        const u32 cb = mine == 2 ? 0x8000u : 0u;
-        // the four neighbours are own stones or border (label 0x8000: root 0)
-        const u32 g0 = L->pt[p - S], g1 = L->pt[p - 1], g2 = L->pt[p + S], g3 = L->pt[p + 1];
-        int off = 0, own = 0;
-        // the neighbour labels of a diagonal that is a true eye of the colour, else 0 (no stone carries label 0): two of its
-        // neighbours are neighbours of this eye too (read above), the two on its far sides are read here
-        u32 dn[4][4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int sx = (q & 2) ? S : -S, sy = (q & 1) ? 1 : -1;
-          const int dp = p + sx + sy;
-          const u32 dv = L->pt[dp];
-          dn[q][0] = dn[q][1] = dn[q][2] = dn[q][3] = 0;
-          if (dv == PT_BORDER) off++;
-          else if (dv == 0) {
-            if (te[dp] == mine) { dn[q][0] = (q & 2) ? g2 : g0; dn[q][1] = (q & 1) ? g3 : g1; dn[q][2] = L->pt[dp + sx]; dn[q][3] = L->pt[dp + sy]; }
-          } else if ((dv & 0x8000u) == cb) own++;
-        }
-        const u32 gs[4] = {g0, g1, g2, g3};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const u32 g = gs[j];
-          bool first = (g & 0x7FFFu) != 0;               // not the border
-#pragma unroll
-          for (int i = 0; i < j; ++i) first = first && gs[i] != g;   // an eye touched by several stones of the group counts once
-          if (first) {
-            int terr = own;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) terr += (dn[q][0] == g || dn[q][1] == g || dn[q][2] == g || dn[q][3] == g) ? 1 : 0;
-            const bool ok = off >= 1 ? (off + terr == 4) : (terr >= 3);
-            if (ok) atomicAdd(&cnt[g & 0x7FFFu], 1u);
-          }
-        }
-      }
-    }
-    Board<N>::wsync();
-  }
+  life_count_eyes<N>(bd, lane, trueB, trueW, cnt, te);
 
   // ---- alive row, OneGroupLives over the box (:1198-1221), living groups in the box
   u64 aliveBox = 0;   // living stones inside the box
@@ -248,29 +314,9 @@ __global__ __launch_bounds__(LIFE_WAVE) void k_life_map(Pool<N> pool, int capaci
     livingW += __popcll(bal_ne(c & 0x20000u, 0u));
   }
 
-  // ---- GuessLDAttacker (:1040-1106): lanes 0..31 the rows of the box (fixed y, x runs), lanes 32..63 its columns
-  int black = 0, white = 0;
-  {
-    const int t = lane & 31;
-    const bool col = lane >= 32;
-    const bool active = col ? (t >= left && t < right) : (t >= top && t < bottom);
-    const int lo = col ? top : left, hi = col ? bottom : right;
-    u32 first = 0, last = 0;
-#pragma unroll   // the N reads are independent: all in flight before the first is consumed
-    for (int s = 0; s < N; ++s) {
-      const bool in = active && s >= lo && s < hi;
-      const int x = col ? t : s, y = col ? s : t;
-      const u32 v = L->pt[in ? (x + 1) * S + (y + 1) : 0];   // pt[0] is a border point
-      const u32 c = (in && (v & 0x7FFFu) != 0) ? ((v & 0x8000u) ? (u32)S_WHITE : (u32)S_BLACK) : 0u;
-      if (c) { if (!first) first = c; last = c; }
-    }
-    const u64 rows = 0xFFFFFFFFull, cols = ~rows;
-    const u64 fB = bal_eq(first, (u32)S_BLACK), fW = bal_eq(first, (u32)S_WHITE), lB = bal_eq(last, (u32)S_BLACK), lW = bal_eq(last, (u32)S_WHITE);
-    if (left > 0) { black += __popcll(fB & rows); white += __popcll(fW & rows); }
-    if (top > 0) { black += __popcll(fB & cols); white += __popcll(fW & cols); }
-    if (right < N) { black += __popcll(lB & rows); white += __popcll(lW & rows); }
-    if (bottom < N) { black += __popcll(lB & cols); white += __popcll(lW & cols); }
-  }
+  // ---- GuessLDAttacker (:1040-1106)
+  int black, white;
+  life_attacker_counts<N>(bd, lane, left, top, right, bottom, black, white);
 
   // ---- getFastScore (:1924-1952): getEyeColor asks White first; the two true-eye sets are disjoint anyway
   const int eb = bd.popc_lanes(trueB & ~trueW), ew = bd.popc_lanes(trueW);

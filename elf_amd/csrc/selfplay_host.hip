@@ -1319,6 +1319,10 @@ int elfsp_search_log(const ElfSelfPlay* sp, int first, int n, ElfSpSearch* rec, 
 // Eye classes, two-eye life reading and the fast score (elfgo_life_map): k_life_map in life.cuh, entry point in life_host.h, here
 // for the same reason.
 #include "life_host.h"
+// Region move lists and life-and-death reading by region playouts (elfgo_region_moves, elfgo_ld_run): k_region_moves and
+// k_playout_ld in region.cuh over candidates.cuh, life.cuh and the ownership harness, entry points in region_host.h, here for the
+// same reason.
+#include "region_host.h"
 // DarkForest features (elfgo_df_*, elfgo_extract_df): k_extract_df and the placement-ply table's kernels in df_features.cuh,
 // entry points in df_host.h, here for the same reason.
 #include "df_host.h"

@@ -96,6 +96,52 @@ class LifeMap:
         return white.to(torch.uint8) * 2 + (black & ~white).to(torch.uint8)
 
 
+LD_INFO_FIELDS = ("left", "top", "right", "bottom", "attacker", "defender", "to_move", "lives")
+LD_STAT_FIELDS = ("lived", "survived", "defender_stones", "attacker_stones", "superko", "steps", "hash_sum", "reserved")
+
+
+class LdReading:
+    """What GoEngine.ld_read returns: the device tensors of elfgo_ld_run -- info int32 [k, 8] (LD_INFO_FIELDS), stats int64 [k, 8]
+    (LD_STAT_FIELDS), first int32 [k, 3, N*N + 1] (per first move, index N*N = pass: playouts, lived, survived) -- and what is
+    derived from them."""
+
+    def __init__(self, n, playouts, info, stats, first):
+        self.n, self.playouts, self.info, self.stats, self.first = n, playouts, info, stats, first
+
+    @property
+    def live_rate(self):
+        """playouts at whose end OneGroupLives(defender, box) holds / playouts -> float64 [k]"""
+        return self.stats[:, 0].to(torch.float64) / self.playouts
+
+    @property
+    def survive_rate(self):
+        """playouts at whose end the defender has a stone inside the box / playouts -> float64 [k]"""
+        return self.stats[:, 1].to(torch.float64) / self.playouts
+
+    def best_move(self):
+        """Per row the first move to play -> list of actions (a = x*N + y; N*N = pass; None where no playout made a move).  Among
+        the first moves with at least one playout: the largest lived / playouts when the side to move is the defender, the
+        smallest when it is the attacker; ratios are compared by integer cross-multiplication; ties go to the move with more
+        playouts, then to the smaller action."""
+        first = self.first.cpu().numpy().astype(np.int64)
+        info = self.info.cpu().numpy()
+        out = []
+        for i in range(first.shape[0]):
+            sign = 1 if info[i, 6] == info[i, 5] else -1
+            best = None
+            for a in np.nonzero(first[i, 0])[0]:
+                p, l = int(first[i, 0, a]), int(first[i, 1, a])
+                if best is None:
+                    best = (int(a), p, l)
+                    continue
+                _, bp, bl = best
+                d = sign * (l * bp - bl * p)       # > 0: a's ratio is the better one
+                if d > 0 or (d == 0 and p > bp):   # actions come in ascending order: a tie on both keeps the smaller
+                    best = (int(a), p, l)
+            out.append(None if best is None else best[0])
+        return out
+
+
 class GoEngine:
     """A pool of `capacity` boards of one size resident in HBM on `device`.
     track_placed=True keeps, beside the slots, the ply at which every stone was placed (an ElfGoDf handle, include/elf_amd.h):
@@ -171,6 +217,25 @@ class GoEngine:
         t = torch.as_tensor(v, dtype=torch.int32, device=self.device).contiguous()
         assert t.numel() == n
         return t, C.c_void_p(t.data_ptr())
+
+    def _boxes(self, regions, k, device_ok=False):
+        """k host boxes (left, top, right, bottom) -> device int32 [k, 4], or None for None; a box outside 0 <= left <= right <= N,
+        0 <= top <= bottom <= N raises ValueError.  device_ok (region_moves, ld_read): a device int32 tensor [k, 4] is used as it
+        is, unread by the host: the kernels clamp each value into [0, N], and a box with left > right or top > bottom is empty."""
+        if regions is None:
+            return None
+        if device_ok and isinstance(regions, torch.Tensor) and regions.is_cuda:
+            if regions.dtype != torch.int32 or tuple(regions.shape) != (k, 4):
+                raise ValueError("a device regions tensor must be int32 [%d, 4]" % k)
+            return regions.contiguous()
+        r = np.asarray(regions, dtype=np.int64).reshape(-1, 4)
+        if r.shape[0] != k:
+            raise ValueError("regions must hold one box per row (%d), got %d" % (k, r.shape[0]))
+        ok = (0 <= r[:, 0]) & (r[:, 0] <= r[:, 2]) & (r[:, 2] <= self.n) & (0 <= r[:, 1]) & (r[:, 1] <= r[:, 3]) & (r[:, 3] <= self.n)
+        if not ok.all():
+            raise ValueError("box %s of row %d is not inside 0 <= left <= right <= N, 0 <= top <= bottom <= N"
+                             % (tuple(int(v) for v in r[int(np.nonzero(~ok)[0][0])]), int(np.nonzero(~ok)[0][0])))
+        return torch.from_numpy(np.ascontiguousarray(r, dtype=np.int32)).to(self.device)
 
     def sync(self):
         check(self.L.elfgo_sync(self._h, self._stream()))
@@ -381,16 +446,7 @@ class GoEngine:
         getBoardBBox of each row.  A box outside 0 <= left <= right <= N, 0 <= top <= bottom <= N raises ValueError before
         anything is launched.  A row whose slot id lies outside the pool gets maps 0, semi_move -1 and summary -1."""
         t, p, k = self._ids(ids, n)
-        reg = None
-        if regions is not None:
-            r = np.asarray(regions, dtype=np.int64).reshape(-1, 4)
-            if r.shape[0] != k:
-                raise ValueError("regions must hold one box per row (%d), got %d" % (k, r.shape[0]))
-            ok = (0 <= r[:, 0]) & (r[:, 0] <= r[:, 2]) & (r[:, 2] <= self.n) & (0 <= r[:, 1]) & (r[:, 1] <= r[:, 3]) & (r[:, 3] <= self.n)
-            if not ok.all():
-                raise ValueError("box %s of row %d is not inside 0 <= left <= right <= N, 0 <= top <= bottom <= N"
-                                 % (tuple(int(v) for v in r[int(np.nonzero(~ok)[0][0])]), int(np.nonzero(~ok)[0][0])))
-            reg = torch.from_numpy(np.ascontiguousarray(r, dtype=np.int32)).to(self.device)
+        reg = self._boxes(regions, k)
         np_ = self.n * self.n
         eye = torch.empty((k, np_), dtype=torch.uint8, device=self.device)
         semi = torch.empty((k, 2, np_), dtype=torch.int16, device=self.device)
@@ -411,6 +467,19 @@ class GoEngine:
         check(self.L.elfgo_life_map(self._h, p, k, None, None, None, None, C.c_void_p(summary.data_ptr()), self._stream()))
         return summary[:, 0 if rule == "chinese" else 1].contiguous()
 
+    def _own_handle(self, max_lanes):
+        """the ElfGoOwnership scratch handle for `max_lanes`, made on first use and remade when max_lanes changes -> (max_lanes, handle)"""
+        own = getattr(self, "_own", None)
+        if own is None or own[0] != int(max_lanes):
+            if own is not None:
+                self.sync()
+                self.L.elfgo_own_destroy(own[1])
+                self._own = None
+            h = C.c_void_p()
+            check(self.L.elfgo_own_create(self._h, int(max_lanes), C.byref(h)))
+            self._own = own = (int(max_lanes), h)
+        return own
+
     def ownership(self, seeds, ids=None, playouts=256, komi=7.5, max_steps=1 << 20, max_lanes=0, self_atari_thres=None):
         """Monte-Carlo ownership: `playouts` config-2 playouts from a private copy of each listed slot (the slots themselves are
         only read), playout k of row i with seed seeds[i] + k * 0x9E3779B97F4A7C15 (mod 2^64).  Returns a dict:
@@ -421,15 +490,7 @@ class GoEngine:
         from the CU count).  self_atari_thres=t plays the candidate policy of playout(self_atari_thres=t)
         (elfgo_own_run_cand); None is elfgo_own_run itself."""
         sd, t, p, k = self._seeds(seeds, ids)
-        own = getattr(self, "_own", None)
-        if own is None or own[0] != int(max_lanes):
-            if own is not None:
-                self.sync()
-                self.L.elfgo_own_destroy(own[1])
-                self._own = None
-            h = C.c_void_p()
-            check(self.L.elfgo_own_create(self._h, int(max_lanes), C.byref(h)))
-            self._own = own = (int(max_lanes), h)
+        own = self._own_handle(max_lanes)
         counts = torch.empty((k, 2, self.n * self.n), dtype=torch.int32, device=self.device)
         stats = torch.empty((k, 4), dtype=torch.int64, device=self.device)
         if self_atari_thres is None:
@@ -443,3 +504,54 @@ class GoEngine:
                     own=(counts[:, 0] - counts[:, 1]).to(torch.float32) / playouts,
                     score_mean=stats[:, 0].to(torch.float64) / playouts - komi,
                     black_win_rate=stats[:, 1].to(torch.float64) / playouts)
+
+    def region_moves(self, ids=None, n=None, regions=None, self_atari_thres=1):
+        """The reference's Region lists for the side to move (elfgo_region_moves) -> (cand, valid, groups), uint8 [k, N*N], index
+        a = x*N + y: cand is FindAllCandidateMovesInRegion(board, box, next_player, self_atari_thres) (candidates()'s mask clipped
+        to the box), valid is FindAllValidMovesInRegion (the legal points inside the box), groups is 1 on every stone of a group
+        that has a stone inside the box (GroupInRegion).  regions: a host sequence of k boxes (left, top, right, bottom),
+        half-open, validated as life_map validates them (ValueError before anything is launched), or a device int32 tensor
+        [k, 4] that is used as it is, unvalidated (the kernel clamps each value into [0, N]; left > right or top > bottom is an
+        empty box); None = THE WHOLE BOARD, the
+        reference's nullptr -- not the bounding box that None means for life_map and ld_read.  A row whose slot id lies outside
+        the pool gets zeros."""
+        t, p, k = self._ids(ids, n)
+        reg = self._boxes(regions, k, device_ok=True)
+        np_ = self.n * self.n
+        cand = torch.empty((k, np_), dtype=torch.uint8, device=self.device)
+        valid = torch.empty((k, np_), dtype=torch.uint8, device=self.device)
+        groups = torch.empty((k, np_), dtype=torch.uint8, device=self.device)
+        check(self.L.elfgo_region_moves(self._h, p, k, C.c_void_p(reg.data_ptr()) if reg is not None else None, int(self_atari_thres),
+                                        C.c_void_p(cand.data_ptr()), C.c_void_p(valid.data_ptr()), C.c_void_p(groups.data_ptr()),
+                                        self._stream()))
+        return cand, valid, groups
+
+    def ld_read(self, seeds, ids=None, regions=None, playouts=256, self_atari_thres=3, attackers=None, max_steps=1 << 20, max_lanes=0):
+        """Life-and-death reading by region playouts (elfgo_ld_run) -> LdReading.  Per row: `playouts` playouts from a private
+        copy of the slot, playout k with seed seeds[i] + k * 0x9E3779B97F4A7C15 (mod 2^64), moves drawn from
+        FindAllCandidateMovesInRegion(board, box, next_player, self_atari_thres), each judged where it ends by
+        OneGroupLives(defender, box) and by the defender's stones left inside the box.  self_atari_thres defaults to 3: with 1
+        the attacker may not throw in, and the reading is blind to most killing moves.
+        regions: k host boxes as for life_map (ValueError before anything is launched) or a device int32 tensor [k, 4] used as it
+        is, unvalidated (clamped by the kernel; left > right or top > bottom is an empty box); None = getBoardBBox of each row.
+        attackers: per row 1 (Black) / 2 (White), anything else = GuessLDAttacker(box); None = guess every row.
+        The scratch handle is ownership()'s.  Unlike playout(), this works on a track_placed engine too: playout() raises there
+        because it plays on the slots without the placement table, while ld_read only reads the slots -- every playout runs on a
+        private copy -- so the table stays true."""
+        sd, t, p, k = self._seeds(seeds, ids)
+        reg = self._boxes(regions, k, device_ok=True)
+        att = None
+        if attackers is not None:
+            att = torch.as_tensor(attackers, dtype=torch.uint8, device=self.device).reshape(-1).contiguous()
+            if att.numel() != k:
+                raise ValueError("attackers must hold one colour per row (%d), got %d" % (k, att.numel()))
+        own = self._own_handle(max_lanes)
+        na = self.n * self.n + 1
+        info = torch.empty((k, 8), dtype=torch.int32, device=self.device)
+        stats = torch.empty((k, 8), dtype=torch.int64, device=self.device)
+        first = torch.empty((k, 3, na), dtype=torch.int32, device=self.device)
+        check(self.L.elfgo_ld_run(own[1], p, C.c_void_p(sd.data_ptr()), k, int(playouts), int(max_steps), int(self_atari_thres),
+                                  C.c_void_p(reg.data_ptr()) if reg is not None else None,
+                                  C.c_void_p(att.data_ptr()) if att is not None else None, C.c_void_p(info.data_ptr()),
+                                  C.c_void_p(stats.data_ptr()), C.c_void_p(first.data_ptr()), self._stream()))
+        return LdReading(self.n, int(playouts), info, stats, first)

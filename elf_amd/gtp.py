@@ -7,9 +7,9 @@ same replies ("= ..." / "? ..."), same coordinate letters (no 'I'): protocol_ver
 clear_board, play, genmove, showboard, final_score, list_commands, quit/exit.  On top of the reference's set (whose `u` / `h`
 commands are commented out, console_lib.py:196-204): undo, fixed_handicap, place_free_handicap, set_free_handicap, loadsgf,
 known_command -- what every GTP front-end sends -- over SelfPlay.setup / SelfPlay.undo; final_status_list and the private
-elf-ownership, elf-score_estimate, elf-ladders, elf-candidates, elf-eyes, elf-life and elf-fast_score over the per-point answers of
-the board engine; lz-genmove_analyze (Leela Zero's
-analysing genmove, what Sabaki and Lizzie send) and elf-analysis over the search's candidates and lines (SelfPlay.analyze).
+elf-ownership, elf-score_estimate, elf-ladders, elf-candidates, elf-region_candidates, elf-eyes, elf-life, elf-fast_score and
+elf-ld_read over the per-point answers of the board engine; lz-genmove_analyze (Leela Zero's analysing genmove, what Sabaki and
+Lizzie send) and elf-analysis over the search's candidates and lines (SelfPlay.analyze).
 
     eng = GtpEngine(actor, board_size=19, mcts_rollout_per_thread=1600)     # actor(batch) -> dict(pi=..., V=...)
     eng.loop()                                                               # stdin/stdout, or eng.command("genmove b")
@@ -75,7 +75,7 @@ HANDICAP_VERTICES = {2: ("D4", "Q16"), 3: ("D4", "Q16", "Q4"), 4: _H4, 5: _H4 + 
 
 class GtpEngine:
     def __init__(self, actor, board_size=19, komi=7.5, device=0, status_playouts=256, status_seed=1, status_self_atari_thres=None,
-                 **selfplay_options):
+                 ld_seed=1, ld_self_atari_thres=3, **selfplay_options):
         opts = dict(mcts_rollout_per_thread=1600, mcts_rollout_per_batch=8, mcts_puct=1.5, mcts_virtual_loss=1,
                     mcts_persistent_tree=True, policy_distri_cutoff=0, resign_thres=0.0, seed=1)
         opts.update(selfplay_options)
@@ -90,6 +90,8 @@ class GtpEngine:
         # None: the status playouts fill everything but the mover's own true eyes, and no seki is reported.  A threshold t: they
         # play the reference's candidate moves (no self-atari of t stones or more), and final_status_list reports seki
         self.status_self_atari_thres = None if status_self_atari_thres is None else int(status_self_atari_thres)
+        # elf-ld_read: the seed of its playouts and the candidate threshold (3: throw-ins of one or two stones stay in)
+        self.ld_seed, self.ld_self_atari_thres = int(ld_seed), int(ld_self_atari_thres)
         self.commands = {k[3:]: f for k, f in inspect.getmembers(self, predicate=inspect.ismethod) if k.startswith("on_")}
         # private extensions carry the "elf-" prefix (GTP 2, section 2.13); a method name cannot hold the hyphen
         self.commands["elf-ownership"] = self.commands.pop("elf_ownership")
@@ -99,6 +101,8 @@ class GtpEngine:
         self.commands["elf-eyes"] = self.commands.pop("elf_eyes")
         self.commands["elf-life"] = self.commands.pop("elf_life")
         self.commands["elf-fast_score"] = self.commands.pop("elf_fast_score")
+        self.commands["elf-region_candidates"] = self.commands.pop("elf_region_candidates")
+        self.commands["elf-ld_read"] = self.commands.pop("elf_ld_read")
         self.commands["elf-analysis"] = self.commands.pop("elf_analysis")
         self.commands["lz-genmove_analyze"] = self.commands.pop("lz_genmove_analyze")
         # every finished search leaves its candidates and lines behind (elf-analysis): one small launch per move of one game
@@ -467,6 +471,59 @@ class GtpEngine:
         if rule not in ("chinese", "japanese"):
             return False, "invalid rule"
         return True, "%d" % int(self.boards.fast_score(ids=[0], rule=rule).cpu()[0])
+
+    # ---- region lists and life-and-death reading (GoEngine.region_moves / ld_read on game 0's current position)
+    def _box(self, v1, v2):
+        """two vertices, opposite corners -> the half-open box (left, top, right, bottom) that holds both"""
+        (x1, y1), (x2, y2) = move2xy(v1), move2xy(v2)
+        if not all(0 <= v < self.n for v in (x1, y1, x2, y2)):
+            raise ValueError("off board")
+        return (min(x1, x2), min(y1, y2), max(x1, x2) + 1, max(y1, y2) + 1)
+
+    def on_elf_region_candidates(self, items):
+        """elf-region_candidates VERTEX VERTEX [thres]: elf-candidates inside the box whose opposite corners the two vertices are
+        (FindAllCandidateMovesInRegion), in elf-candidates' format; thres defaults to 1."""
+        if len(items) < 3:
+            return False, "two vertices expected"
+        try:
+            box = self._box(items[1], items[2])
+            thres = int(items[3]) if len(items) > 3 else 1
+        except (IndexError, ValueError):
+            return False, "invalid vertex"
+        mask = self.boards.region_moves(ids=[0], regions=[box], self_atari_thres=thres)[0].cpu().numpy()[0]
+        stones = self.boards.candidates(ids=[0], self_atari_thres=thres)[1].cpu().numpy()[0]
+        return True, " ".join(self._vertex(a) + (":%d" % int(stones[a]) if stones[a] > 0 else "")
+                              for a in range(self.n * self.n) if mask[a])
+
+    def on_elf_ld_read(self, items):
+        """elf-ld_read [VERTEX VERTEX] [playouts]: life-and-death reading of the box whose opposite corners the two vertices are
+        (none: the bounding box of the stones) by region playouts.  First line: `attacker b|w defender b|w to_move b|w lives a/b
+        survives a/b best VERTEX|pass|none` (a of b playouts ended with a living defender group in the box / a defender stone in
+        the box); then one line `VERTEX playouts lived survived` per first move, in board order, `pass` last.  Seed and threshold
+        are the constructor's ld_seed and ld_self_atari_thres: the same position gives the same reply."""
+        import numpy as np
+        args = items[1:]
+        box = None
+        try:
+            if len(args) >= 2 and not args[0].isdigit():
+                box = self._box(args[0], args[1])
+                args = args[2:]
+            playouts = int(args[0]) if args else self.status_playouts
+        except (IndexError, ValueError):
+            return False, "invalid arguments"
+        if playouts <= 0 or len(args) > 1:
+            return False, "invalid arguments"
+        rd = self.boards.ld_read(np.array([self.ld_seed], np.uint64), ids=[0], regions=None if box is None else [box],
+                                 playouts=playouts, self_atari_thres=self.ld_self_atari_thres)
+        info, stats, first = rd.info.cpu().numpy()[0], rd.stats.cpu().numpy()[0], rd.first.cpu().numpy()[0]
+        NP = self.n * self.n
+        name = lambda a: "pass" if a == NP else self._vertex(a)
+        best = rd.best_move()[0]
+        lines = ["attacker %s defender %s to_move %s lives %d/%d survives %d/%d best %s" % (
+            " bw"[int(info[4])], " bw"[int(info[5])], " bw"[int(info[6])], int(stats[0]), playouts, int(stats[1]), playouts,
+            "none" if best is None else name(best))]
+        lines += ["%s %d %d %d" % (name(a), int(first[0, a]), int(first[1, a]), int(first[2, a])) for a in range(NP + 1) if first[0, a]]
+        return True, "\n".join(lines)
 
     def on_list_commands(self, items):
         return True, "\n".join(self.commands.keys())

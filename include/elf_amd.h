@@ -190,6 +190,46 @@ int elfgo_own_run_cand(ElfGoOwnership* o, const int32_t* ids, const uint64_t* se
 int elfgo_life_map(ElfGoEngine* e, const int32_t* ids, int n, const int32_t* regions, uint8_t* eye, int16_t* semi_move,
                    uint8_t* alive, int32_t* summary, void* stream);
 
+/* The reference's Region move lists of board slots (base/board.cc), per row i, a = x*N + y, all uint8:
+ *     cand[i][a]   1 iff a is in FindAllCandidateMovesInRegion(board, &box, next_player, self_atari_thres) (:892-947): the
+ *                  legal points of the side to move inside the box that are neither its own true eye nor a self-atari of
+ *                  self_atari_thres stones or more -- elfgo_candidates' mask clipped to the box
+ *     valid[i][a]  1 iff a is in FindAllValidMovesInRegion(board, &box) (:970-1005): the legal points of the side to move
+ *                  inside the box
+ *     groups[i][a] 1 on every stone whose group has GroupInRegion(board, id, &box) (:1183-1196) true -- some stone of the
+ *                  group lies inside the box -- else 0
+ * regions int32 [n][4] = left, top, right, bottom, half-open in x and y like the reference's Region, each value clamped into
+ * [0, N].  regions NULL is the reference's nullptr, THE WHOLE BOARD -- unlike elfgo_life_map, where NULL means the bounding box
+ * of the stones.  Device pointers, row stride N*N; any output may be NULL, not all three.  ids NULL = slots [0, n).  A row
+ * whose slot id lies outside the pool gets zeros.  The slots are only read; a slot may be named several times.
+ * ELFGO_E_BADARG for a null engine, n <= 0, ids NULL with n above the capacity, or all three outputs NULL: nothing is launched. */
+int elfgo_region_moves(ElfGoEngine* e, const int32_t* ids, int n, const int32_t* regions, int self_atari_thres, uint8_t* cand,
+                       uint8_t* valid, uint8_t* groups, void* stream);
+
+/* Life-and-death reading by region playouts, on the scratch and launch geometry of an ElfGoOwnership handle.  Per row i:
+ *   - the box is regions[i] (as above, clamped); regions NULL = getBoardBBox of the row, elfgo_life_map's rule (NOT the whole
+ *     board);
+ *   - the attacker is attackers[i] where that is 1 (Black) or 2 (White), else GuessLDAttacker(box) of the source position
+ *     (attackers NULL = guess every row); the defender is the other colour;
+ *   - playout k < playouts works on a private copy of the slot with seed seeds[i] + k * 0x9E3779B97F4A7C15 (mod 2^64), the
+ *     counter RNG, x-major pick and GoState::terminated() of elfgo_playout_cand, and the move list
+ *     FindAllCandidateMovesInRegion(board, &box, next_player, self_atari_thres); it passes when the list is empty, stops at
+ *     termination or after max_steps moves, and is judged where it stands.
+ * Outputs (device pointers; the call zeroes them on `stream` first):
+ *     info[i]  int32 [8]: 0-3 the box used (left, top, right, bottom), 4 attacker, 5 defender, 6 side to move,
+ *              7 OneGroupLives(defender, box) of the source position
+ *     stats[i] int64 [8]: 0 playouts at whose end OneGroupLives(defender, box) holds ("lived"), 1 playouts at whose end the
+ *              defender has a stone inside the box ("survived"), 2 / 3 sum of the defender's / the attacker's stones inside
+ *              the box at the end, 4 super-ko endings, 5 steps played, 6 sum mod 2^64 of the end positions' hashes, 7 zero
+ *     first[i] int32 [3][N*N + 1]: per first move of the playout (action a; index N*N = pass): playouts, lived, survived.  A
+ *              playout that made no move is counted in stats only.
+ * Integer sums: the result does not depend on scheduling or on the handle's max_lanes.  Source slots are only read and may be
+ * named several times; a row whose slot id lies outside the pool is not played and keeps zeros.  ELFGO_E_BADARG for a null
+ * handle, seeds or output, n <= 0, playouts <= 0, ids NULL with n above the capacity, or n * playouts above 2^31 - 16. */
+int elfgo_ld_run(ElfGoOwnership* o, const int32_t* ids, const uint64_t* seeds, int n, int playouts, int max_steps,
+                 int self_atari_thres, const int32_t* regions, const uint8_t* attackers, int32_t* info, int64_t* stats,
+                 int32_t* first, void* stream);
+
 /* The reference's 25 DarkForest planes (BoardFeature::extract, base/board_feature.cc:43-237; what GameOptions.use_df_feature
  * selects there) of board slots: fp32 [25][N][N] per row under D4 code d4[i], "ours" = the side to move:
  *    0-2 / 3-5  our / the opponent's stones of groups with 1, 2, >= 3 liberties (getLibertyMap3binary)
