@@ -9,6 +9,9 @@ ZOBRIST_BIN = os.path.join(HERE, "data", "zobrist21.bin")
 
 _lib = None
 
+# row formats (include/elf_amd.h): the first two for every "s" row, the DarkForest one for ElfTrainBatch.s_format only
+ELFGO_FEAT_F32_NCHW, ELFGO_FEAT_F16_NHWC, ELFGO_FEAT_DF_F32_NCHW = 0, 1, 2
+
 # the sources every device kernel of libelf_amd.so is compiled from: measurements that are tied to the kernels' instruction
 # streams (profiles/pmc_issue.json, pmc_traffic.json) record this hash, and bench.py only prices against them while it matches
 KERNEL_SOURCES = ("go_board.cuh", "mcts.cuh", "train.cuh", "stl_emul.h", "engine_host.h", "elf_amd.hip", "mcts_capi.hip", "train_capi.hip",

@@ -64,8 +64,16 @@ def parse_record(board_size, rec):
                 values=np.asarray(res["values"], np.float32), seq=int(j.get("seq", 0)))
 
 
+# feature_format -> (ELFGO_FEAT_* code of ElfTrainBatch.s_format, planes of an "s" row)
+FEATURE_FORMATS = {"f32_nchw": (_lib.ELFGO_FEAT_F32_NCHW, 18), "f16_nhwc": (_lib.ELFGO_FEAT_F16_NHWC, 18),
+                   "df_f32_nchw": (_lib.ELFGO_FEAT_DF_F32_NCHW, 25)}
+
+
 class ReplayLoader:
     """HBM-resident replay store + one-launch batch extraction (k_replay_extract).
+    feature_format: "f32_nchw" / "f16_nhwc" = the 18 AGZ planes (extractStateExtAGZ) as fp32 [n, 18, N, N] / fp16 channels_last;
+    "df_f32_nchw" = the 25 DarkForest planes (BoardFeature::extract, the reference's "s" under use_df_feature) as fp32
+    [n, 25, N, N] -- what the DarkForest policy nets train on, with num_future_actions = 3.  `num_planes` is 18 or 25.
     keep_states=False (default, the trainer's mode): a sample replays from its record's checkpoint (the state after every 16th
     move, written once per put) -- at most 15 board steps instead of ~160, the same rows.  keep_states=True: the reference's own
     procedure (reset + forward x move_to), and the replayed GoState of sample i stays in board slot i of `self.engine`."""
@@ -80,9 +88,12 @@ class ReplayLoader:
         self.batchsize = int(batchsize)
         self.nfa = int(num_future_actions)
         self.max_moves = int(max_moves or 2 * self.n * self.n)   # BOARD_MAX_MOVE (go_common.h:15)
+        if feature_format not in FEATURE_FORMATS:
+            raise ValueError("feature_format must be 'f32_nchw', 'f16_nhwc' or 'df_f32_nchw'")
+        self.feature_format = feature_format
         self.f16 = feature_format == "f16_nhwc"
-        if not self.f16 and feature_format != "f32_nchw":
-            raise ValueError("feature_format must be 'f32_nchw' or 'f16_nhwc'")
+        # s_format of ElfTrainBatch, planes per row: 18 AGZ planes, or the 25 DarkForest planes (GameOptions.use_df_feature)
+        self._fmt, self.num_planes = FEATURE_FORMATS[feature_format]
         # the trainer prefetches: `batches_per_launch` train batches are drawn and extracted by ONE launch (sample_batches); the
         # replay of a sample is a dependent chain of ~160 board steps, so the kernel wants many samples in flight
         self.batches_per_launch = max(1, int(batches_per_launch))
@@ -131,7 +142,7 @@ class ReplayLoader:
         if self.f16:
             s = torch.empty((n, self.n, self.n, 18), dtype=torch.float16, device=dev).permute(0, 3, 1, 2)
         else:
-            s = torch.empty((n, 18, self.n, self.n), dtype=torch.float32, device=dev)
+            s = torch.empty((n, self.num_planes, self.n, self.n), dtype=torch.float32, device=dev)
         return dict(s=s, offline_a=torch.empty((n, self.nfa), dtype=torch.int64, device=dev),
                     winner=torch.empty(n, dtype=torch.float32, device=dev),
                     mcts_scores=torch.empty((n, self.na), dtype=torch.float32, device=dev),
@@ -148,7 +159,7 @@ class ReplayLoader:
         if n > self.batchsize * self.batches_per_launch:
             raise ValueError("more samples than the loader's batchsize x batches_per_launch")
         b = out if out is not None else self._alloc(n)
-        tb = TrainBatch(b["s"].data_ptr(), 18 * self.n * self.n, 1 if self.f16 else 0, self.nfa, b["offline_a"].data_ptr(),
+        tb = TrainBatch(b["s"].data_ptr(), self.num_planes * self.n * self.n, self._fmt, self.nfa, b["offline_a"].data_ptr(),
                         b["winner"].data_ptr(), b["mcts_scores"].data_ptr(), b["predicted_value"].data_ptr(), b["move_idx"].data_ptr(),
                         b["num_move"].data_ptr(), b["aug_code"].data_ptr(), b["selfplay_ver"].data_ptr())
         check(self.L.elftrain_extract(self._h, C.c_void_p(t[0].data_ptr()), C.c_void_p(t[1].data_ptr()), C.c_void_p(t[2].data_ptr()),

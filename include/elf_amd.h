@@ -684,8 +684,18 @@ int elfsp_search_log(const ElfSelfPlay* sp, int first, int n, ElfSpSearch* rec, 
  * ------------------------------------------------------------------------------------------------ */
 typedef struct ElfReplay ElfReplay;
 
+/* A third row format, for ElfTrainBatch.s_format only: the 25 DarkForest planes (BoardFeature::extract, see elfgo_df_extract)
+ * as fp32 [25][N][N] -- what the reference's "train" batch carries in "s" when GameOptions.use_df_feature is set
+ * (common/game_feature.h:98-102, :159-170; the DarkForest policy nets of df_model.py train on it with offline_a
+ * [num_future_actions]).  Rows need 4-byte alignment only and s_stride >= 25*N*N floats.  Info::last_placed of the replayed
+ * position is rebuilt from the record's move list; the exponents of planes 10 / 11 come from elfgo_df_exp_table's values.
+ * elfgo_extract_agz_fmt and elfmcts_set_feature_format refuse this value. */
+#define ELFGO_FEAT_DF_F32_NCHW 2
+
 typedef struct ElfTrainBatch {      /* device pointers, rows = samples; every pointer except s may be NULL */
-  void* s;                          /* "s" [n][18][N][N] in s_format (ELFGO_FEAT_*), rows s_stride elements apart */
+  void* s;                          /* "s" in s_format, rows s_stride elements apart (>= the row's size): ELFGO_FEAT_F32_NCHW fp32
+                                     * [n][18][N][N], ELFGO_FEAT_F16_NHWC fp16 [n][N][N][18] (extractStateExtAGZ), or
+                                     * ELFGO_FEAT_DF_F32_NCHW fp32 [n][25][N][N] (GameOptions.use_df_feature) */
   int64_t s_stride;
   int32_t s_format;
   int32_t num_future_actions;       /* GameOptions.num_future_actions */
