@@ -20,8 +20,9 @@
 //   box:    the region of OneGroupLives / GuessLDAttacker; getBoardBBox of the position when the caller gives none.  The
 //           attacker scan is one pass over the N steps of a line: lanes 0..31 take the rows of the box, lanes 32..63 its columns,
 //           each remembers the first and the last stone of its line inside the box.
-//   shared: the eye count of GivenGroupLives, the bounding box and the attacker scan are functions (life_count_eyes, life_bbox,
-//           life_attacker_counts) that k_playout_ld (region.cuh) calls too, beside life_true_eyes for callers that want no more.
+//   shared: the eye count of GivenGroupLives, the caller's box, the bounding box and the attacker scan are functions
+//           (life_count_eyes, life_region_read, life_bbox, life_attacker_counts) that the kernels of region.cuh call too, beside
+//           life_true_eyes for callers that want no more.
 #pragma once
 #include "go_board.cuh"
 #include "engine_host.h"
@@ -56,6 +57,15 @@ __device__ __forceinline__ void life_true_eyes(const Board<N>& bd, u64& trueB, u
   const u64 edge = bd.mEdge, inner = bd.mValid & ~bd.mEdge;
   trueB = eyeB & ~((edge & life_ge1(w1, w2, w3, w4)) | (inner & life_ge2(w1, w2, w3, w4)));
   trueW = eyeW & ~((edge & life_ge1(b1, b2, b3, b4)) | (inner & life_ge2(b1, b2, b3, b4)));
+}
+
+// The caller's box: regions[row] = {left, top, right, bottom}, half-open, clamped into [0, N]; wave-uniform.  One statement of the
+// rule for k_life_map and the region kernels (region.cuh).
+template <int N>
+__device__ __forceinline__ void life_region_read(const int32_t* regions, int row, int lane, int& left, int& top, int& right, int& bottom) {
+  const int v = lane < 4 ? regions[(size_t)row * 4 + lane] : 0;
+  const int c = v < 0 ? 0 : v > N ? N : v;
+  left = rl(c, 0); top = rl(c, 1); right = rl(c, 2); bottom = rl(c, 3);
 }
 
 // The three functions below take the lane index as an argument, like Board::init: a kernel that calls them inside a loop
@@ -278,9 +288,7 @@ __global__ __launch_bounds__(LIFE_WAVE) void k_life_map(Pool<N> pool, int capaci
   // ---- the box: the caller's, clamped, or getBoardBBox (:1024-1038)
   int left, top, right, bottom;
   if (regions) {
-    const int v = lane < 4 ? regions[(size_t)row * 4 + lane] : 0;
-    const int c = v < 0 ? 0 : v > N ? N : v;
-    left = rl(c, 0); top = rl(c, 1); right = rl(c, 2); bottom = rl(c, 3);
+    life_region_read<N>(regions, row, lane, left, top, right, bottom);
   } else {
     life_bbox<N>(bd, lane, span, left, top, right, bottom);
   }

@@ -3,17 +3,11 @@
 // members only.
 //   area:    simple_flood_fill per colour + the black && !white / white && !black rule of simple_tt_scoring
 //            (base/go_state.h:32-93) -- Board::tt_area()'s fill, restated here because it must keep the rows it popcounts
-//   playout: the shared loop of playout.cuh under the kernel's Policy argument; with EyePolicy it is k_playout's game
+//   playout: playout.cuh's harness (playout_pairs) under OwnTally and the kernel's Policy argument; with EyePolicy k_playout's game
 #pragma once
 #include "go_board.cuh"
 #include "engine_host.h"
 #include "playout.cuh"
-
-#define OWN_WAVE PLAYOUT_WAVE
-#define OWN_WAVES PLAYOUT_WAVES   // boards per workgroup of k_playout_own; the handle's record areas are sized by it
-
-// seed(i, k) = seeds[i] + k * 0x9E3779B97F4A7C15 (mod 2^64): playout 0 of a row is what k_playout plays with seeds[i]
-__device__ __forceinline__ u64 own_seed(u64 row_seed, int k) { return row_seed + (u64)k * 0x9E3779B97F4A7C15ull; }
 
 // Area rows of the board's current stones: lane x < N ends with bit y of `ab` / `aw` set iff point a = x*N + y is black / white
 // area; lanes >= N hold 0.  Row-bitboard flood fill in registers, both colours at once, to a fixed point.
@@ -98,22 +92,45 @@ __device__ __forceinline__ void own_add_rows(int* dst, u32 ab, u32 aw, int lane)
   }
 }
 
-// Ownership: for source row i and playout k < K, a private copy of slot ids[i] is played to the end with seed(i, k) and its
-// area rows are added into counts[i][2][N*N]; stats[i] = {sum of (black area - white area), playouts with
-// (float)diff - komi > 0, playouts that ended on a super-ko repeat, steps played}.
-//  * The source slot is only read.  The copy lives in LDS; its super-ko records go to this wave's own record area in
-//    `scratch` ([lanes][MAXMOVE+2][SKW] u64), which receives the source's first sk_len records whenever the wave turns to
-//    another slot (a playout only appends behind them, so they survive from one playout of a slot to the next).
-//  * Waves are persistent: the (i, k) pairs, row-major, are cut into groups of OWN_WAVES consecutive pairs and workgroup g
-//    plays a contiguous run of groups, one pair per wave.  Scratch is therefore bounded by the waves in flight.
-//  * Counters are accumulated in LDS for the row the workgroup is on (the row of a group's first pair) and flushed with
-//    atomicAdd when that row changes and at the end; a wave whose pair already belongs to the next row (a group may straddle
-//    two rows) adds to the global counters directly.
-//  * `pol` is the playout policy (playout.cuh), last so that the arguments before it are elfgo_own_run's in order.
+// The ownership tally of playout_pairs (playout.cuh): pair (row, k) is played to the end with seed(row, k) under `pol` and its area
+// rows are added into counts[row][2][N*N]; stats[row] = {sum of (black area - white area), playouts with (float)diff - komi > 0,
+// playouts that ended on a super-ko repeat, steps played}.  acc[2][N*N]: the workgroup's LDS counters.
 template <int N, class Policy>
-__global__ __launch_bounds__(OWN_WAVE * OWN_WAVES) void k_playout_own(Pool<N> pool, u64* scratch, const int32_t* ids, const u64* seeds,
-                                                                       int n, int K, int max_steps, float komi, int32_t* counts,
-                                                                       unsigned long long* stats, Policy pol) {
+struct OwnTally {
+  using G = Geo<N>;
+  int* acc;
+  const u64* seeds; int max_steps; float komi; int32_t* counts; unsigned long long* stats; Policy pol;   // the kernel's arguments
+  __device__ __forceinline__ void flush(int row) {
+    int* g = counts + (size_t)row * 2 * G::NP;
+    for (int j = threadIdx.x; j < 2 * G::NP; j += OWN_WAVE * OWN_WAVES) {
+      const int v = acc[j];
+      if (v) { atomicAdd(&g[j], v); acc[j] = 0; }
+    }
+  }
+  __device__ __forceinline__ void play(Board<N>& bd, const GameSK<N>& sk, int row, int k, bool local, int wv, const u64* zlds, const u32* mlds) {
+    const u32 key = playout_key(own_seed(seeds[row], k));
+    bd.playout_begin(zlds);
+    const int steps = playout_run<N>(bd, sk, key, max_steps, pol, mlds);
+    u32 ab, aw;
+    area_rows<N>(bd, ab, aw);
+    const int diff = area_diff(ab, aw);
+    if (local) own_add_rows<N>(acc, ab, aw, bd.lane);
+    else own_add_rows<N>(counts + (size_t)row * 2 * G::NP, ab, aw, bd.lane);
+    if (bd.lane == 0) {
+      unsigned long long* st = stats + (size_t)row * 4;
+      atomicAdd(&st[0], (unsigned long long)(long long)diff);
+      if ((float)diff - komi > 0.0f) atomicAdd(&st[1], 1ull);
+      if (bd.superko) atomicAdd(&st[2], 1ull);
+      atomicAdd(&st[3], (unsigned long long)steps);
+    }
+  }
+};
+
+// Ownership (elfgo_own_run*): OwnTally over playout_pairs.  `pol` comes last so that the arguments before it are elfgo_own_run's.
+template <int N, class Policy>
+__global__ __launch_bounds__(OWN_WAVE * OWN_WAVES) void k_playout_own(Pool<N> pool, int capacity, u64* scratch, const int32_t* ids,
+                                                                       const u64* seeds, int n, int K, int max_steps, float komi,
+                                                                       int32_t* counts, unsigned long long* stats, Policy pol) {
   using G = Geo<N>;
   __shared__ Slot<N> lds_all[OWN_WAVES];
   __shared__ u64 zlds[G::P];
@@ -122,56 +139,6 @@ __global__ __launch_bounds__(OWN_WAVE * OWN_WAVES) void k_playout_own(Pool<N> po
   playout_tables<N, OWN_WAVE * OWN_WAVES>(pool.zob, zlds, mlds);
   for (int j = threadIdx.x; j < 2 * G::NP; j += OWN_WAVE * OWN_WAVES) acc[j] = 0;
   __syncthreads();
-  const int wv = rfl((int)(threadIdx.x >> 6));   // wave-uniform by construction
-  u64* const rec = scratch + (size_t)(blockIdx.x * OWN_WAVES + wv) * (G::MAXMOVE + 2) * G::SKW;
-  Slot<N>& lds = lds_all[wv];
-  Board<N> bd;
-  bd.init(&lds, pool.zob, rec);
-  const GameSK<N> sk{rec};
-  const int pairs = n * K, groups = (pairs + OWN_WAVES - 1) / OWN_WAVES;   // n * K < 2^31 - OWN_WAVES: checked by the host
-  const int q0 = (int)((long long)groups * blockIdx.x / gridDim.x), q1 = (int)((long long)groups * (blockIdx.x + 1) / gridDim.x);
-  int have = -1;     // the slot whose record prefix `rec` holds
-  int wg_row = -1;   // the row `acc` counts for
-  auto flush = [&]() {
-    int* g = counts + (size_t)wg_row * 2 * G::NP;
-    for (int j = threadIdx.x; j < 2 * G::NP; j += OWN_WAVE * OWN_WAVES) {
-      const int v = acc[j];
-      if (v) { atomicAdd(&g[j], v); acc[j] = 0; }
-    }
-  };
-  for (int q = q0; q < q1; ++q) {
-    const int row0 = q * OWN_WAVES / K;
-    if (row0 != wg_row) {   // the same decision in every wave of the workgroup
-      if (wg_row >= 0) { flush(); __syncthreads(); }
-      wg_row = row0;
-    }
-    const int p = q * OWN_WAVES + wv;
-    if (p < pairs) {
-      const int row = p / K, k = p - row * K;
-      const int b = ids ? ids[row] : row;
-      bd.load(&pool.slots[b]);
-      if (b != have) {
-        const u64* src = pool.skr(b);
-        for (int j = bd.lane; j < bd.sk_len * G::SKW; j += OWN_WAVE) rec[j] = src[j];
-        have = b;
-      }
-      const u32 key = playout_key(own_seed(seeds[row], k));
-      bd.playout_begin(zlds);
-      const int steps = playout_run<N>(bd, sk, key, max_steps, pol, mlds);
-      u32 ab, aw;
-      area_rows<N>(bd, ab, aw);
-      const int diff = area_diff(ab, aw);
-      if (row == wg_row) own_add_rows<N>(acc, ab, aw, bd.lane);
-      else own_add_rows<N>(counts + (size_t)row * 2 * G::NP, ab, aw, bd.lane);
-      if (bd.lane == 0) {
-        unsigned long long* st = stats + (size_t)row * 4;
-        atomicAdd(&st[0], (unsigned long long)(long long)diff);
-        if ((float)diff - komi > 0.0f) atomicAdd(&st[1], 1ull);
-        if (bd.superko) atomicAdd(&st[2], 1ull);
-        atomicAdd(&st[3], (unsigned long long)steps);
-      }
-    }
-    __syncthreads();   // this group's LDS adds are in before a flush reads them
-  }
-  if (wg_row >= 0) flush();
+  OwnTally<N, Policy> t{acc, seeds, max_steps, komi, counts, stats, pol};
+  playout_pairs<N>(pool, capacity, scratch, ids, n, K, lds_all, zlds, mlds, t);
 }

@@ -17,22 +17,30 @@ struct ElfGoOwnership {
 template <int N>
 static size_t own_record_bytes() { return (size_t)(Geo<N>::MAXMOVE + 2) * Geo<N>::SKW * sizeof(u64); }
 
+// The launch plan of a playout_pairs kernel (elfgo_own_run*, elfgo_ld_run): checks the arguments they share and returns the workgroups
+// of the persistent launch, one per group of OWN_WAVES pairs up to the handle's record areas; 0 = an argument is refused.
+static int own_plan(const ElfGoOwnership* o, const int32_t* ids, const uint64_t* seeds, int n, int playouts) {
+  if (!o || !seeds || n <= 0 || playouts <= 0) return 0;
+  if (!ids && n > o->e->capacity) return 0;
+  if ((long long)n * playouts > 0x7FFFFFF0ll) return 0;   // the kernel counts (row, playout) pairs in 32 bits
+  const int groups = (n * playouts + OWN_WAVES - 1) / OWN_WAVES;
+  return groups < o->lanes / OWN_WAVES ? groups : o->lanes / OWN_WAVES;
+}
+
 // elfgo_own_run under the given playout policy: checks, zeroed sums, one persistent launch.
 template <class Policy>
 static int own_run(ElfGoOwnership* o, const int32_t* ids, const uint64_t* seeds, int n, int playouts, int max_steps, float komi,
                    int32_t* counts, int64_t* stats, void* stream, Policy pol) {
-  if (!o || !seeds || !counts || !stats || n <= 0 || playouts <= 0) return ELFGO_E_BADARG;
+  const int wgs = own_plan(o, ids, seeds, n, playouts);
+  if (!wgs || !counts || !stats) return ELFGO_E_BADARG;
   ElfGoEngine* e = o->e;
-  if (!ids && n > e->capacity) return ELFGO_E_BADARG;
-  if ((long long)n * playouts > 0x7FFFFFF0ll) return ELFGO_E_BADARG;   // the kernel counts (row, playout) pairs in 32 bits
   DevGuard _dg(e->device);
   const size_t np = (size_t)e->n * e->n;
   HIPCHK(hipMemsetAsync(counts, 0, (size_t)n * 2 * np * sizeof(int32_t), (hipStream_t)stream));
   HIPCHK(hipMemsetAsync(stats, 0, (size_t)n * 4 * sizeof(int64_t), (hipStream_t)stream));
-  const int groups = (n * playouts + OWN_WAVES - 1) / OWN_WAVES;
-  const int wgs = groups < o->lanes / OWN_WAVES ? groups : o->lanes / OWN_WAVES;
   DISPATCH(e, hipLaunchKernelGGL((k_playout_own<N, Policy>), dim3(wgs), dim3(OWN_WAVE * OWN_WAVES), 0, (hipStream_t)stream, pool_of<N>(e),
-                                 o->scratch, ids, (const u64*)seeds, n, playouts, max_steps, komi, counts, (unsigned long long*)stats, pol));
+                                 e->capacity, o->scratch, ids, (const u64*)seeds, n, playouts, max_steps, komi, counts,
+                                 (unsigned long long*)stats, pol));
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -1,16 +1,23 @@
 // The playout the device kernels share: one step (rng draw, legal moves, the policy's cut, the x-major pick, forward), the loop
-// around it, and the workgroup prologue that copies the Zobrist constants and the pick's reciprocal table into LDS.  Used by
-// k_playout_own<N, Policy> (ownership.cuh) and k_playout_cand (candidates.cuh).  k_playout (elf_amd.hip) plays EyePolicy's game
+// around it, the workgroup prologue that copies the Zobrist constants and the pick's reciprocal table into LDS, and playout_pairs,
+// the persistent-wave harness of the kernels that play K playouts per source row.  Used by k_playout_own<N, Policy> (ownership.cuh),
+// k_playout_ld (region.cuh) and, without the harness, k_playout_cand (candidates.cuh).  k_playout (elf_amd.hip) plays EyePolicy's game
 // from a text of its own: its file is under the hash of the profiled kernel sources (elf_amd._lib.KERNEL_SOURCES), so folding
 // it onto playout_step, like a translation unit of their own for these kernels, waits for the next re-profiling visit.
 //   Policy: `template <int N> u64 keep(const Board<N>&, u64 cand) const` returns the subset of `cand` (legal minus own true
 //           eyes, lane-distributed, bd.at_cache fresh) to pick from; the object travels as a kernel argument.
+//   Tally:  what a playout_pairs kernel counts: its LDS accumulators and output pointers behind flush / play (see playout_pairs).
 #pragma once
 #include "go_board.cuh"
 #include "engine_host.h"
 
 #define PLAYOUT_WAVE 64
 #define PLAYOUT_WAVES 4   // boards per workgroup of every playout kernel
+#define OWN_WAVE PLAYOUT_WAVE
+#define OWN_WAVES PLAYOUT_WAVES   // boards per workgroup of a playout_pairs kernel; the ElfGoOwnership record areas are sized by it
+
+// seed(i, k) = seeds[i] + k * 0x9E3779B97F4A7C15 (mod 2^64): playout 0 of a row is what k_playout plays with seeds[i]
+__device__ __forceinline__ u64 own_seed(u64 row_seed, int k) { return row_seed + (u64)k * 0x9E3779B97F4A7C15ull; }
 
 // k_playout's policy: every legal point that is no true eye of the mover.
 struct EyePolicy {
@@ -73,4 +80,56 @@ __device__ __forceinline__ int playout_run(Board<N>& bd, const GameSK<N>& sk, u3
     ++steps;
   }
   return steps;
+}
+
+// The persistent-wave harness of k_playout_own and k_playout_ld: for source row i < n and playout k < K one wave plays a private
+// copy of slot ids[i] (ids null = slot i) and the kernel's tally counts the result.  Called by every thread of the workgroup, after
+// the kernel's LDS prologue (playout_tables, zeroed accumulators, __syncthreads()).
+//  * The source slot is only read.  The copy lives in the wave's LDS slot of lds_all[OWN_WAVES]; its super-ko records go to the
+//    wave's own record area in `scratch` ([waves in flight][MAXMOVE+2][SKW] u64, the ElfGoOwnership handle's), which receives the
+//    source's first sk_len records whenever the wave turns to another slot (a playout only appends behind them, so they survive
+//    from one playout of a slot to the next).
+//  * Waves are persistent: the (i, k) pairs, row-major, are cut into groups of OWN_WAVES consecutive pairs and workgroup g plays a
+//    contiguous run of groups, one pair per wave.  Scratch is therefore bounded by the waves in flight.  A row whose slot id lies
+//    outside the pool ([0, capacity)) is not played: the tally never sees it.
+//  * Counters are accumulated in LDS for the row the workgroup is on (the row of a group's first pair) and flushed when that row
+//    changes and at the end; a wave whose pair already belongs to the next row (a group may straddle two rows) adds to the global
+//    counters directly.  Integer atomics only, so the sums do not depend on who adds first.
+//   t.flush(row): all threads of the workgroup; adds the LDS accumulators into global row `row` and clears them.
+//   t.play(bd, sk, row, k, local, wv, zlds, mlds): one wave, bd freshly loaded; plays pair (row, k) and adds to the LDS accumulators
+//           when `local`, else to global row `row`.  wv = the wave's index in the workgroup, for per-wave LDS of the tally's own.
+template <int N, class Tally>
+__device__ __forceinline__ void playout_pairs(const Pool<N>& pool, int capacity, u64* scratch, const int32_t* ids, int n, int K,
+                                              Slot<N>* lds_all, const u64* zlds, const u32* mlds, Tally& t) {
+  using G = Geo<N>;
+  const int wv = rfl((int)(threadIdx.x >> 6));   // wave-uniform by construction
+  u64* const rec = scratch + (size_t)(blockIdx.x * OWN_WAVES + wv) * (G::MAXMOVE + 2) * G::SKW;
+  Board<N> bd;
+  bd.init(&lds_all[wv], pool.zob, rec);
+  const GameSK<N> sk{rec};
+  const int pairs = n * K, groups = (pairs + OWN_WAVES - 1) / OWN_WAVES;   // n * K < 2^31 - OWN_WAVES: checked by the host
+  const int q0 = (int)((long long)groups * blockIdx.x / gridDim.x), q1 = (int)((long long)groups * (blockIdx.x + 1) / gridDim.x);
+  int have = -1;     // the slot whose record prefix `rec` holds
+  int wg_row = -1;   // the row the tally's LDS accumulators count for
+  for (int q = q0; q < q1; ++q) {
+    const int row0 = q * OWN_WAVES / K;
+    if (row0 != wg_row) {   // the same decision in every wave of the workgroup
+      if (wg_row >= 0) { t.flush(wg_row); __syncthreads(); }
+      wg_row = row0;
+    }
+    const int p = q * OWN_WAVES + wv;
+    const int row = p < pairs ? p / K : 0, k = p - row * K;
+    const int b = p < pairs ? rfl(ids ? ids[row] : row) : -1;
+    if (b >= 0 && b < capacity) {
+      bd.load(&pool.slots[b]);
+      if (b != have) {
+        const u64* src = pool.skr(b);
+        for (int j = bd.lane; j < bd.sk_len * G::SKW; j += OWN_WAVE) rec[j] = src[j];
+        have = b;
+      }
+      t.play(bd, sk, row, k, row == wg_row, wv, zlds, mlds);
+    }
+    __syncthreads();   // this group's LDS adds are in before a flush reads them
+  }
+  if (wg_row >= 0) t.flush(wg_row);
 }

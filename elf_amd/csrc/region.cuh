@@ -2,8 +2,8 @@
 //   k_region_moves: FindAllCandidateMovesInRegion (base/board.cc:892-947), FindAllValidMovesInRegion (:970-1005) and
 //                   GroupInRegion (:1183-1196) for every point of a position at once.  One wave64 = one board, as in k_candidates.
 //   RegionCandPolicy: the playout policy "candidates inside the box" (playout.cuh's Policy): CandPolicy on cand & box.
-//   k_playout_ld:   k_playout_own's persistent-wave harness with that policy; every playout is judged where it stops by
-//                   OneGroupLives(defender, box) (:1198-1221) and by the stones left inside the box.
+//   k_playout_ld:   playout.cuh's harness (playout_pairs) with that policy; its tally (LdTally) judges every playout where it stops
+//                   by OneGroupLives(defender, box) (:1198-1221) and by the stones left inside the box.
 // The box is a lane-distributed bitboard built once per row (region_box); the lists are the whole-board lists ANDed with it, which
 // keeps the reference's x-major order.  The life reading is life.cuh's (life_true_eyes, life_count_eyes, life_bbox,
 // life_attacker_counts): one text for k_life_map and for the verdicts here.  Board<N> is used through its public members only.
@@ -13,19 +13,10 @@
 #include "playout.cuh"
 #include "candidates.cuh"
 #include "life.cuh"
-#include "ownership.cuh"
 
 #define REGION_WAVE 64   // k_region_moves: one board per workgroup
 #define LD_INFO_WORDS 8
 #define LD_STAT_WORDS 8
-
-// regions[row] clamped into [0, N] (elfgo_life_map's rule), wave-uniform
-template <int N>
-__device__ __forceinline__ void region_read(const int32_t* regions, int row, int lane, int& left, int& top, int& right, int& bottom) {
-  const int v = lane < 4 ? regions[(size_t)row * 4 + lane] : 0;
-  const int c = v < 0 ? 0 : v > N ? N : v;
-  left = rl(c, 0); top = rl(c, 1); right = rl(c, 2); bottom = rl(c, 3);
-}
 
 // bit a = x*N + y of the result (lane-distributed, lanes 0..R-1) is set iff left <= x < right and top <= y < bottom
 template <int N>
@@ -73,7 +64,7 @@ __global__ __launch_bounds__(REGION_WAVE) void k_region_moves(Pool<N> pool, int 
   bd.init(&lds, pool.zob, pool.skr(b));
   bd.load(&pool.slots[b]);   // its fence orders the zero fill of inreg before the flags below
   int left = 0, top = 0, right = N, bottom = N;
-  if (regions) region_read<N>(regions, row, lane, left, top, right, bottom);
+  if (regions) life_region_read<N>(regions, row, lane, left, top, right, bottom);
   const u64 box = region_box<N>(bd, lane, left, top, right, bottom);
   u64 keep = 0, legal = 0;
   if (crow || vrow) {
@@ -107,7 +98,7 @@ __global__ __launch_bounds__(REGION_WAVE) void k_region_moves(Pool<N> pool, int 
   }
 }
 
-// The region policy of the playouts: FindAllCandidateMovesInRegion's list.  The box belongs to a row, so the harness builds the
+// The region policy of the playouts: FindAllCandidateMovesInRegion's list.  The box belongs to a row, so the tally builds the
 // object per (row, playout); with the whole-board box it is CandPolicy's game.
 struct RegionCandPolicy {
   int thres;
@@ -150,24 +141,121 @@ __device__ __forceinline__ bool ld_one_group_lives(const Board<N>& bd, u64 box, 
   return any;
 }
 
-// Life-and-death reading by region playouts: for source row i and playout k < K, a private copy of slot ids[i] is played with
-// seed(i, k) (ownership.cuh) from FindAllCandidateMovesInRegion(board, box, next_player, thres) until the game terminates or
-// max_steps moves are made, and judged where it stands.  info / stats / first: see include/elf_amd.h.
-//  * The harness is k_playout_own's: persistent waves, one (row, playout) pair per wave, groups of OWN_WAVES consecutive pairs, the
-//    record areas of the ElfGoOwnership handle.  The source slot is only read.
+// The life-and-death tally of playout_pairs (playout.cuh): pair (row, k) is played with seed(row, k) from the list of
+// FindAllCandidateMovesInRegion(board, box, next_player, thres) until the game terminates or max_steps moves are made, and judged
+// where it stands.  info / stats / first: see include/elf_amd.h.
 //  * The box, the attacker and the source position's verdict are worked out by every wave from its fresh copy of the slot (they
 //    cost a fraction of one playout move each); playout 0 of a row writes them to info.
-//  * Counters are accumulated in LDS for the row the workgroup is on and flushed with integer atomics when that row changes and at
-//    the end; a wave whose pair already belongs to the next row adds to the global counters directly.  Integer adds: the sums do
-//    not depend on who adds first.
-//  * A row whose slot id lies outside the pool is not played: its outputs stay zero.
+template <int N>
+struct LdTally {
+  using G = Geo<N>;
+  static constexpr int NA = G::NA, FW = 3 * NA;
+  int* facc; unsigned long long* sacc;                                          // the workgroup's LDS counters for first / stats
+  u32 (*cnt_all)[G::PP]; unsigned char (*te_all)[G::PP]; u32 (*span_all)[2];   // per-wave LDS scratch of the life reading
+  const u64* seeds; int max_steps, thres; const int32_t* regions; const uint8_t* attackers;   // the kernel's arguments
+  int32_t* info; unsigned long long* stats; int32_t* first;
+  __device__ __forceinline__ void flush(int row) {
+    int* g = first + (size_t)row * FW;
+    for (int j = threadIdx.x; j < FW; j += OWN_WAVE * OWN_WAVES) {
+      const int v = facc[j];
+      if (v) { atomicAdd(&g[j], v); facc[j] = 0; }
+    }
+    if (threadIdx.x < LD_STAT_WORDS) {
+      const unsigned long long v = sacc[threadIdx.x];
+      if (v) { atomicAdd(&stats[(size_t)row * LD_STAT_WORDS + threadIdx.x], v); sacc[threadIdx.x] = 0ull; }
+    }
+  }
+  __device__ __forceinline__ void play(Board<N>& bd, const GameSK<N>& sk, int row, int k, bool local, int wv, const u64* zlds, const u32* mlds) {
+    u32* const span = span_all[wv];
+    // ---- the problem: box, attacker, defender, the source position's verdict
+    const int ol = ld_opaque(bd.lane);
+    int left, top, right, bottom;
+    if (regions) {
+      life_region_read<N>(regions, row, ol, left, top, right, bottom);
+    } else {
+      if (ol < 2) span[ol] = 0;
+      Board<N>::wsync();
+      life_bbox<N>(bd, ol, span, left, top, right, bottom);
+    }
+    const u64 box = region_box<N>(bd, ol, left, top, right, bottom);
+    int att = attackers ? rfl((int)attackers[row]) : 0;
+    if (att != S_BLACK && att != S_WHITE) {
+      int black, white;
+      life_attacker_counts<N>(bd, ol, left, top, right, bottom, black, white);
+      att = rfl(black > white ? S_BLACK : S_WHITE);
+    }
+    const int def = S_BLACK + S_WHITE - att;
+    // ---- phase 0 (playout 0 of a row only): the source position's verdict goes to info; phase 1: the playout and its verdict.
+    // One loop, so that the life reading is one call site.
+    int steps = 0, first_c = 0, lived = 0;
+#pragma unroll 1
+    for (int phase = k == 0 ? 0 : 1; phase < 2; ++phase) {
+      if (phase == 1) {
+        // playout_run in two parts, so that the first move can be read off the board: one move, then the rest.  A loop and
+        // not two calls: the step is inlined once.
+        const u32 key = playout_key(own_seed(seeds[row], k));
+        const RegionCandPolicy pol{thres, box};
+        bd.playout_begin(zlds);
+#pragma unroll 1
+        for (int part = 0; part < 2; ++part) {
+          const int limit = part == 0 ? (max_steps < 1 ? max_steps : 1) : max_steps - steps;
+          const int made = playout_run<N>(bd, sk, key, limit, pol, mlds);
+          if (part == 0) {
+            if (made == 0) break;
+            first_c = bd.lm0;
+          }
+          steps += made;
+        }
+      }
+      lived = ld_one_group_lives<N>(bd, box, def, cnt_all[wv], te_all[wv]) ? 1 : 0;
+      if (phase == 0) {
+        int w = 0;
+        switch (bd.lane) {
+          case 0: w = left; break;
+          case 1: w = top; break;
+          case 2: w = right; break;
+          case 3: w = bottom; break;
+          case 4: w = att; break;
+          case 5: w = def; break;
+          case 6: w = bd.next_player; break;
+          default: w = lived; break;
+        }
+        if (bd.lane < LD_INFO_WORDS) info[(size_t)row * LD_INFO_WORDS + bd.lane] = w;
+      }
+    }
+    // ---- the counters
+    const u64 D = (def == S_BLACK ? bd.Bw : bd.Ww) & box, A = (def == S_BLACK ? bd.Ww : bd.Bw) & box;
+    const int nd = bd.popc_lanes(D), na = bd.popc_lanes(A);
+    const int survived = nd > 0 ? 1 : 0;
+    if (bd.lane == 0) {
+      unsigned long long* st = local ? sacc : stats + (size_t)row * LD_STAT_WORDS;
+      if (lived) atomicAdd(&st[0], 1ull);
+      if (survived) atomicAdd(&st[1], 1ull);
+      if (nd) atomicAdd(&st[2], (unsigned long long)nd);
+      if (na) atomicAdd(&st[3], (unsigned long long)na);
+      if (bd.superko) atomicAdd(&st[4], 1ull);
+      if (steps) atomicAdd(&st[5], (unsigned long long)steps);
+      atomicAdd(&st[6], (unsigned long long)bd.hash);
+      if (steps > 0) {
+        const int fa = first_c == M_PASS ? G::NP : Board<N>::c2a_u(first_c);
+        int* f = local ? facc : first + (size_t)row * FW;
+        atomicAdd(&f[fa], 1);
+        if (lived) atomicAdd(&f[NA + fa], 1);
+        if (survived) atomicAdd(&f[2 * NA + fa], 1);
+      }
+    }
+  }
+};
+
+// Life-and-death reading by region playouts (elfgo_ld_run): LdTally over playout_pairs, on the record areas of the ElfGoOwnership
+// handle.  A row whose slot id lies outside the pool is not played: its outputs stay zero.
 template <int N>
 __global__ __launch_bounds__(OWN_WAVE * OWN_WAVES) void k_playout_ld(Pool<N> pool, int capacity, u64* scratch, const int32_t* ids,
                                                                       const u64* seeds, int n, int K, int max_steps, int thres,
                                                                       const int32_t* regions, const uint8_t* attackers, int32_t* info,
                                                                       unsigned long long* stats, int32_t* first) {
   using G = Geo<N>;
-  constexpr int NA = G::NA, FW = 3 * NA;
+  constexpr int FW = LdTally<N>::FW;
   __shared__ Slot<N> lds_all[OWN_WAVES];
   __shared__ u64 zlds[G::P];
   __shared__ u32 mlds[G::NP + 2];
@@ -180,126 +268,6 @@ __global__ __launch_bounds__(OWN_WAVE * OWN_WAVES) void k_playout_ld(Pool<N> poo
   for (int j = threadIdx.x; j < FW; j += OWN_WAVE * OWN_WAVES) facc[j] = 0;
   if (threadIdx.x < LD_STAT_WORDS) sacc[threadIdx.x] = 0ull;
   __syncthreads();
-  const int wv = rfl((int)(threadIdx.x >> 6));   // wave-uniform by construction
-  u64* const rec = scratch + (size_t)(blockIdx.x * OWN_WAVES + wv) * (G::MAXMOVE + 2) * G::SKW;
-  Slot<N>& lds = lds_all[wv];
-  u32* const cnt = cnt_all[wv];
-  unsigned char* const te = te_all[wv];
-  u32* const span = span_all[wv];
-  Board<N> bd;
-  bd.init(&lds, pool.zob, rec);
-  const GameSK<N> sk{rec};
-  const int pairs = n * K, groups = (pairs + OWN_WAVES - 1) / OWN_WAVES;   // n * K < 2^31 - OWN_WAVES: checked by the host
-  const int q0 = (int)((long long)groups * blockIdx.x / gridDim.x), q1 = (int)((long long)groups * (blockIdx.x + 1) / gridDim.x);
-  int have = -1;     // the slot whose record prefix `rec` holds
-  int wg_row = -1;   // the row facc / sacc count for
-  auto flush = [&]() {
-    int* g = first + (size_t)wg_row * FW;
-    for (int j = threadIdx.x; j < FW; j += OWN_WAVE * OWN_WAVES) {
-      const int v = facc[j];
-      if (v) { atomicAdd(&g[j], v); facc[j] = 0; }
-    }
-    if (threadIdx.x < LD_STAT_WORDS) {
-      const unsigned long long v = sacc[threadIdx.x];
-      if (v) { atomicAdd(&stats[(size_t)wg_row * LD_STAT_WORDS + threadIdx.x], v); sacc[threadIdx.x] = 0ull; }
-    }
-  };
-  for (int q = q0; q < q1; ++q) {
-    const int row0 = q * OWN_WAVES / K;
-    if (row0 != wg_row) {   // the same decision in every wave of the workgroup
-      if (wg_row >= 0) { flush(); __syncthreads(); }
-      wg_row = row0;
-    }
-    const int p = q * OWN_WAVES + wv;
-    const int row = p < pairs ? p / K : 0, k = p - row * K;
-    const int b = p < pairs ? rfl(ids ? ids[row] : row) : -1;
-    if (b >= 0 && b < capacity) {
-      bd.load(&pool.slots[b]);
-      if (b != have) {
-        const u64* src = pool.skr(b);
-        for (int j = bd.lane; j < bd.sk_len * G::SKW; j += OWN_WAVE) rec[j] = src[j];
-        have = b;
-      }
-      // ---- the problem: box, attacker, defender, the source position's verdict
-      const int ol = ld_opaque(bd.lane);
-      int left, top, right, bottom;
-      if (regions) {
-        region_read<N>(regions, row, ol, left, top, right, bottom);
-      } else {
-        if (ol < 2) span[ol] = 0;
-        Board<N>::wsync();
-        life_bbox<N>(bd, ol, span, left, top, right, bottom);
-      }
-      const u64 box = region_box<N>(bd, ol, left, top, right, bottom);
-      int att = attackers ? rfl((int)attackers[row]) : 0;
-      if (att != S_BLACK && att != S_WHITE) {
-        int black, white;
-        life_attacker_counts<N>(bd, ol, left, top, right, bottom, black, white);
-        att = rfl(black > white ? S_BLACK : S_WHITE);
-      }
-      const int def = S_BLACK + S_WHITE - att;
-      // ---- phase 0 (playout 0 of a row only): the source position's verdict goes to info; phase 1: the playout and its verdict.
-      // One loop, so that the life reading is one call site.
-      int steps = 0, first_c = 0, lived = 0;
-#pragma unroll 1
-      for (int phase = k == 0 ? 0 : 1; phase < 2; ++phase) {
-        if (phase == 1) {
-          // playout_run in two parts, so that the first move can be read off the board: one move, then the rest.  A loop and
-          // not two calls: the step is inlined once.
-          const u32 key = playout_key(own_seed(seeds[row], k));
-          const RegionCandPolicy pol{thres, box};
-          bd.playout_begin(zlds);
-#pragma unroll 1
-          for (int part = 0; part < 2; ++part) {
-            const int limit = part == 0 ? (max_steps < 1 ? max_steps : 1) : max_steps - steps;
-            const int made = playout_run<N>(bd, sk, key, limit, pol, mlds);
-            if (part == 0) {
-              if (made == 0) break;
-              first_c = bd.lm0;
-            }
-            steps += made;
-          }
-        }
-        lived = ld_one_group_lives<N>(bd, box, def, cnt, te) ? 1 : 0;
-        if (phase == 0) {
-          int w = 0;
-          switch (bd.lane) {
-            case 0: w = left; break;
-            case 1: w = top; break;
-            case 2: w = right; break;
-            case 3: w = bottom; break;
-            case 4: w = att; break;
-            case 5: w = def; break;
-            case 6: w = bd.next_player; break;
-            default: w = lived; break;
-          }
-          if (bd.lane < LD_INFO_WORDS) info[(size_t)row * LD_INFO_WORDS + bd.lane] = w;
-        }
-      }
-      // ---- the counters
-      const u64 D = (def == S_BLACK ? bd.Bw : bd.Ww) & box, A = (def == S_BLACK ? bd.Ww : bd.Bw) & box;
-      const int nd = bd.popc_lanes(D), na = bd.popc_lanes(A);
-      const int survived = nd > 0 ? 1 : 0;
-      if (bd.lane == 0) {
-        const bool local = row == wg_row;
-        unsigned long long* st = local ? sacc : stats + (size_t)row * LD_STAT_WORDS;
-        if (lived) atomicAdd(&st[0], 1ull);
-        if (survived) atomicAdd(&st[1], 1ull);
-        if (nd) atomicAdd(&st[2], (unsigned long long)nd);
-        if (na) atomicAdd(&st[3], (unsigned long long)na);
-        if (bd.superko) atomicAdd(&st[4], 1ull);
-        if (steps) atomicAdd(&st[5], (unsigned long long)steps);
-        atomicAdd(&st[6], (unsigned long long)bd.hash);
-        if (steps > 0) {
-          const int fa = first_c == M_PASS ? G::NP : Board<N>::c2a_u(first_c);
-          int* f = local ? facc : first + (size_t)row * FW;
-          atomicAdd(&f[fa], 1);
-          if (lived) atomicAdd(&f[NA + fa], 1);
-          if (survived) atomicAdd(&f[2 * NA + fa], 1);
-        }
-      }
-    }
-    __syncthreads();   // this group's LDS adds are in before a flush reads them
-  }
-  if (wg_row >= 0) flush();
+  LdTally<N> t{facc, sacc, cnt_all, te_all, span_all, seeds, max_steps, thres, regions, attackers, info, stats, first};
+  playout_pairs<N>(pool, capacity, scratch, ids, n, K, lds_all, zlds, mlds, t);
 }

@@ -19,17 +19,14 @@ int elfgo_region_moves(ElfGoEngine* e, const int32_t* ids, int n, const int32_t*
 int elfgo_ld_run(ElfGoOwnership* o, const int32_t* ids, const uint64_t* seeds, int n, int playouts, int max_steps,
                  int self_atari_thres, const int32_t* regions, const uint8_t* attackers, int32_t* info, int64_t* stats, int32_t* first,
                  void* stream) {
-  if (!o || !seeds || !info || !stats || !first || n <= 0 || playouts <= 0) return ELFGO_E_BADARG;
+  const int wgs = own_plan(o, ids, seeds, n, playouts);
+  if (!wgs || !info || !stats || !first) return ELFGO_E_BADARG;
   ElfGoEngine* e = o->e;
-  if (!ids && n > e->capacity) return ELFGO_E_BADARG;
-  if ((long long)n * playouts > 0x7FFFFFF0ll) return ELFGO_E_BADARG;   // the kernel counts (row, playout) pairs in 32 bits
   DevGuard _dg(e->device);
   const size_t na = (size_t)e->n * e->n + 1;
   HIPCHK(hipMemsetAsync(info, 0, (size_t)n * LD_INFO_WORDS * sizeof(int32_t), (hipStream_t)stream));
   HIPCHK(hipMemsetAsync(stats, 0, (size_t)n * LD_STAT_WORDS * sizeof(int64_t), (hipStream_t)stream));
   HIPCHK(hipMemsetAsync(first, 0, (size_t)n * 3 * na * sizeof(int32_t), (hipStream_t)stream));
-  const int groups = (n * playouts + OWN_WAVES - 1) / OWN_WAVES;
-  const int wgs = groups < o->lanes / OWN_WAVES ? groups : o->lanes / OWN_WAVES;
   DISPATCH(e, hipLaunchKernelGGL(k_playout_ld<N>, dim3(wgs), dim3(OWN_WAVE * OWN_WAVES), 0, (hipStream_t)stream, pool_of<N>(e), e->capacity,
                                  o->scratch, ids, (const u64*)seeds, n, playouts, max_steps, self_atari_thres, regions, attackers, info,
                                  (unsigned long long*)stats, first));

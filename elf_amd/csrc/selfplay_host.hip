@@ -1302,8 +1302,8 @@ int elfsp_search_log(const ElfSelfPlay* sp, int first, int n, ElfSpSearch* rec, 
 
 }  // extern "C"
 
-// Area map and Monte-Carlo ownership (elfgo_area_map, elfgo_own_*): device code in ownership.cuh, entry points and launches in
-// ownership_host.h.  They are compiled here only because this is the library's one HIP translation unit that the hash of the
+// Area map and Monte-Carlo ownership (elfgo_area_map, elfgo_own_*): device code in ownership.cuh over the persistent-wave harness
+// of playout.cuh (playout_pairs), entry points, the harness's launch plan (own_plan) and launches in ownership_host.h.  They are compiled here only because this is the library's one HIP translation unit that the hash of the
 // profiled kernel sources (elf_amd._lib.KERNEL_SOURCES, stamped into profiles/pmc_*.json) does not cover; the next change that
 // re-profiles moves them into a translation unit of their own.
 #include "ownership_host.h"
@@ -1320,8 +1320,8 @@ int elfsp_search_log(const ElfSelfPlay* sp, int first, int n, ElfSpSearch* rec, 
 // for the same reason.
 #include "life_host.h"
 // Region move lists and life-and-death reading by region playouts (elfgo_region_moves, elfgo_ld_run): k_region_moves and
-// k_playout_ld in region.cuh over candidates.cuh, life.cuh and the ownership harness, entry points in region_host.h, here for the
-// same reason.
+// k_playout_ld in region.cuh over candidates.cuh, life.cuh and playout.cuh's harness (playout_pairs, planned by ownership_host.h's
+// own_plan), entry points in region_host.h, here for the same reason.
 #include "region_host.h"
 // DarkForest features (elfgo_df_*, elfgo_extract_df): k_extract_df and the placement-ply table's kernels in df_features.cuh,
 // entry points in df_host.h, here for the same reason.

@@ -487,7 +487,8 @@ class GoEngine:
         black - white area, black wins after komi, super-ko endings, steps played) straight from the device, and derived from
         them own = (black - white) / playouts float32 [k, N*N], score_mean = mean area difference - komi, black_win_rate.
         The scratch handle is made on first use and lives until close(); max_lanes bounds the playouts in flight (0 = a default
-        from the CU count).  self_atari_thres=t plays the candidate policy of playout(self_atari_thres=t)
+        from the CU count).  A row whose slot id lies outside the pool is not played: its counts and stats are zero, as in
+        ld_read.  self_atari_thres=t plays the candidate policy of playout(self_atari_thres=t)
         (elfgo_own_run_cand); None is elfgo_own_run itself."""
         sd, t, p, k = self._seeds(seeds, ids)
         own = self._own_handle(max_lanes)

@@ -139,7 +139,8 @@ size_t elfgo_own_scratch_bytes(const ElfGoOwnership* o);
  *                  playouts that ended with the super-ko flag set, sum of steps played }   int64 [n][4]
  * The call zeroes counts and stats on `stream` itself.  Integer sums only: the result does not depend on scheduling or on
  * max_lanes.  The source slots are only read (header, stones, Bloom words and super-ko records alike); a slot may be named
- * several times.  ELFGO_E_BADARG for a null pointer (ids may be NULL), n <= 0 or playouts <= 0. */
+ * several times.  A row whose slot id lies outside the pool is not played and keeps zeros (elfgo_ld_run's rule).
+ * ELFGO_E_BADARG for a null pointer (ids may be NULL), n <= 0 or playouts <= 0. */
 int elfgo_own_run(ElfGoOwnership* o, const int32_t* ids, const uint64_t* seeds, int n, int playouts, int max_steps,
                   float komi, int32_t* counts, int64_t* stats, void* stream);
 

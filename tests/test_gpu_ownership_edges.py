@@ -187,6 +187,31 @@ def test_both_policies_run_one_harness(six):
             assert np.array_equal(got[0], wc) and np.array_equal(got[1], ws), (K, lanes)
 
 
+def test_out_of_pool_ids_are_not_played(six):
+    """A row whose slot id lies outside the pool is not played (elfgo_ld_run's rule): its counts and stats stay zero and the rows
+    around it are the oracle's.  Out-of-pool rows stand first and last, between two rows of the late game (with K = 3 on one
+    workgroup wave 3 plays pairs 3, 7 and 11 -- late game, skipped, late game -- so the record prefix it holds must survive the
+    skip) and between rows of two different slots; groups of four pairs straddle in-pool and out-of-pool rows both ways."""
+    eng, E, states = six
+    cap, K = eng.capacity, 3
+    ids = [cap, LATE, -1, LATE, MID, cap + 7, KO, EMPTY, cap, STEP, DONE, -1]
+    live = [r for r, b in enumerate(ids) if 0 <= b < cap]
+    dead = [r for r in range(len(ids)) if r not in live]
+    assert len(live) == 7 and dead == [0, 2, 5, 8, 11]
+    seeds = playout_seeds(len(ids), base=7000)
+    wc, ws = expected_rows(E, states, [ids[r] for r in live], seeds[live], K)
+    assert ws[:, 3].max() > 0                        # the in-pool rows are played
+    before = snapshot(eng)
+    for thres in (None, 82):
+        for lanes in (1, 0):
+            counts, stats = run(eng, seeds, ids=ids, playouts=K, max_lanes=lanes, self_atari_thres=thres)
+            for j, r in enumerate(live):
+                assert np.array_equal(counts[r], wc[j]), (thres, lanes, r)
+                assert np.array_equal(stats[r], ws[j]), (thres, lanes, r, stats[r].tolist(), ws[j].tolist())
+            assert not counts[dead].any() and not stats[dead].any(), (thres, lanes)
+    assert same(before, snapshot(eng))
+
+
 def test_record_prefix_decides_the_playout(elf):
     """Sources whose records matter at once: the super-ko game one move short of its end, where about every other playout opens
     with the move that repeats a position of the game's own history (an ending by super-ko after one step -- found only in the
