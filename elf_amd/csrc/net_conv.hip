@@ -12,16 +12,13 @@
 //         whose strides differ from E's, so a [K] bias would have to be expanded to a whole activation.  The ABD op builds the same
 //         gridwise GEMM (same K order y, x, c; same pipeline v1) and gives each D its own descriptor (G_K layout for the bias).
 // algo 1  not CK: the hand-written 256 x 256 x 64 LDS-DMA kernel of net_conv3x3.hip, an object of its own that this file only
-//         calls (elfnet_conv3x3_native_f16, hidden; that object exports only host arithmetic: the plans of its two row orders
-//         and the rule that chooses between them).  Same K order and MFMA as algo 0.  elfnet_conv3x3_f16_width hands algo 1 the
+//         calls (elfnet_conv3x3_native_f16, hidden; the plans of its two row orders and the rule that chooses between them are
+//         host arithmetic, exported by net_conv3x3_plan.hip).  Same K order and MFMA as algo 0.  elfnet_conv3x3_f16_width hands algo 1 the
 //         round width its split of the last round goes by and keeps it on the linear order, elfnet_conv3x3_f16_boards forces
 //         board order, and the plain entry lets that object choose by shape.
 //
 // This translation unit is its own object (GNUmakefile): the CK templates take ~40 s each to compile and depend on none of the
-// project's .cuh files, which is also why it carries its own small device guard instead of including engine_host.h.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+// project's .cuh files, which is also why its device guard is net_common.h's and not engine_host.h's.
 #include <array>
 
 #if !__has_include("ck/ck.hpp")
@@ -34,7 +31,7 @@
 #include "ck/tensor_operation/gpu/device/tensor_layout.hpp"
 #include "ck/tensor_operation/gpu/element/element_wise_operation.hpp"
 
-#include "../../include/elf_amd.h"
+#include "net_common.h"
 
 namespace {
 
@@ -85,18 +82,6 @@ using DsBiasRes = ck::Tuple<lay::G_K, lay::NHWGK>;
 using T1 = ck::Tuple<F16>;
 using T2 = ck::Tuple<F16, F16>;
 
-// engine_host.h's DevGuard (that header pulls the board kernels in, see the top of this file)
-struct DevGuard {
-  int prev = -1;
-  explicit DevGuard(int dev) {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur != dev && hipSetDevice(dev) == hipSuccess) prev = cur;
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  DevGuard(const DevGuard&) = delete;
-  DevGuard& operator=(const DevGuard&) = delete;
-};
-
 struct Shape { int n, h, w, c, k; };
 
 // host-side argument object and CK's own support check; with `launch`, one launch on `stream`: no allocation, no
@@ -144,17 +129,11 @@ namespace {
 // order is algo 1's row order: 0 linear, 1 board, -1 the one net_conv3x3.hip chooses for the shape
 int conv3x3_f16(const void* x, const void* w, const void* bias, const void* res, void* y, int64_t rows, int h, int wd, int c, int k,
                 int relu, int algo, int round_width, int order, void* stream) {
-  if (!x || !w || !bias || !y || rows < 0 || h <= 0 || wd <= 0 || c <= 0 || k <= 0) return ELFGO_E_BADARG;
   if ((c & 7) != 0 || (k & 7) != 0 || (algo != 0 && algo != 1) || round_width < 0) return ELFGO_E_BADARG;
-  if ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)res | (uintptr_t)y) & 15) != 0) return ELFGO_E_BADARG;
-  if (y == x || y == res) return ELFGO_E_BADARG;
-  // CK's descriptors are 32-bit: every tensor stays below 2^31 bytes (2048 rows of 19 x 19 x 256 are 0.38 GB)
-  const int64_t cmax = c > k ? c : k;
-  if (rows * h * wd * cmax >= ((int64_t)1 << 30) || (int64_t)k * 9 * c >= ((int64_t)1 << 30)) return ELFGO_E_BADARG;
-  if (rows == 0) return 0;
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, x) != hipSuccess) { (void)hipGetLastError(); return ELFGO_E_BADARG; }
-  DevGuard _dg(at.device);
+  int dev = 0;
+  const int go = conv_args(x, 16, w, bias, res, y, rows, h, wd, c, k, &dev);
+  if (go <= 0) return go;
+  DevGuard _dg(dev);
   const Shape s{(int)rows, h, wd, c, k};
   hipStream_t st = (hipStream_t)stream;
   if (algo == 1) return elfnet_conv3x3_native_f16(x, w, bias, res, y, rows, h, wd, c, k, relu, round_width, order, st);

@@ -33,7 +33,7 @@
 //             round is at most half full, each of its items runs as two work ids of 256 positions x 128 channels (the half
 //             tile: the same waves at 128 x 32 each, three staged half-tiles per K tile instead of four), so that round takes
 //             a half tile's time.  Same kernel, same launch, same K chain per output element: the bits do not change.  The host
-//             entry decides (full_items below).
+//             entry decides (full_items).
 //   orders    the 256 rows of a tile are, in linear order, 256 consecutive positions (n, h, w), about 13.5 rows of a 19 x 19
 //             board: every tile has positions on every edge, runs all nine taps and multiplies staged zeros wherever a tap is
 //             off the board, 6.9 % of all K tiles on 19 x 19.  In board order they are one board position (h, w) of 256 consecutive
@@ -41,7 +41,7 @@
 //             and its K loop visits only the set taps, ascending (first_tap, next_tap; popcount x Cin / 64 K tiles: 4 taps in a
 //             corner, 6 on an edge, 9 inside; 3025 taps per block of boards on 19 x 19 instead of 3249).  One kernel body: row r of an
 //             item is position base + r stride, valid below limit (decode_rows, load_skip and the epilogue's stores share that one
-//             mapping), and linear order is the mask 0x1FF with the per-row masks below.  The comment at Deal has the ids and how
+//             mapping), and linear order is the mask 0x1FF with the per-row masks below.  The comment at Deal (net_conv3x3_plan.h) has the ids and how
 //             they are dealt; the host entry chooses the order by shape (order_of).
 //   bits      for finite operands both orders give the same bits, algo 0's: every accumulator takes the same non-zero products in
 //             the same order; what linear order adds is MFMAs whose B operand is all zeros, that is products +-0 added to an
@@ -59,57 +59,25 @@
 // The operands are swapped in the MFMA (A = weights, B = activations) so that a lane's accumulator registers run along the
 // channels: four consecutive channels of one position per register group, one ds_write_b64 each.
 //
-// This translation unit includes nothing from CK and nothing of the project but the C header: it is its own object (GNUmakefile).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+// Everything of this the host can plan -- the work ids and the items they name, the two deals, order_of, the division by a launch
+// constant, the staging's byte offsets and kSentinel -- is net_conv3x3_plan.h, and the exported host arithmetic over it is
+// net_conv3x3_plan.hip.  This translation unit includes nothing from CK and nothing of the project but that header and
+// net_common.h: it is its own object (GNUmakefile).
 #include <atomic>
 
-#include "../../include/elf_amd.h"
-
+#include "net_conv3x3_plan.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-constexpr int kTileM = 256;                      // positions per workgroup
-constexpr int kTileN = 256;                      // output channels per workgroup
-constexpr int kThreads = 512;
+constexpr int kThreads = 512;                    // kTileM 256 positions x kTileN 256 output channels per workgroup
 constexpr int kOperandBytes = 256 * 128;         // one operand of one K tile: 256 rows x 64 fp16
 constexpr int kBufBytes = 2 * kOperandBytes;     // activations, then weights
 constexpr int kWaveCBytes = 4096;                // a wave's own piece of the epilogue: 32 positions x 64 channels fp16
 constexpr int kLdsBytes = 2 * kBufBytes + 8 * kWaveCBytes;   // two K tiles and the eight waves' epilogue pieces: 160 KiB, all a CU has
 
-typedef __attribute__((address_space(3))) void* lptr_t;
+// buffer-addressed staging: the comment at kSentinel has the descriptors, the offsets and where the zeros come from
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
-
-// ---- buffer-addressed staging.  x and w are read through one raw buffer descriptor each (stride 0, offen), made in scalar
-// registers at kernel entry; a staged piece is buffer_load_dwordx4 v, s[rsrc], s offen lds: the lane's 32-bit byte offset (made
-// once per item, decode_rows) in the vector register, everything wave-uniform about the piece (tap, channel chunk) in the scalar
-// offset.  The sum the instruction addresses by is unsigned, and a tap's offset from a row's own position is negative for ky = 0
-// and kx = 0, so x's descriptor starts bias = (W + 1) Cin 2 bytes in front of x and every scalar offset of x carries + bias.
-// Zeros come from the descriptor's range check: a lane whose vector offset is at or above num_records reads nothing and its
-// 16 bytes of LDS are written with zeros.  Such a lane carries kSentinel, whatever the tensor's size: 16-byte aligned, at or above
-// every num_records the entry accepts, and with every scalar offset still below 2^32.  The arithmetic, shared with the host entry
-// elfnet_conv3x3_f16_bufstage and its test:
-//   x  bytes < 2^31 (net_conv.hip), bias and every scalar offset (at most (2 W + 3) Cin 2) below 2^30 (the native entry refuses a
-//      wider board): num_records = bytes + bias < 2^31 + 2^30 = kSentinel; a valid row's offset + scalar offset < 2^31 + 2^30;
-//      kSentinel + scalar offset < 2^32: no sum wraps.  A tap that is on the board addresses bytes of x only: offset + scalar
-//      offset - bias is that neighbour's chunk.
-//   w  bytes < 2^31, the scalar offset stays inside a weight row: below the tensor's size.
-constexpr uint32_t kSentinel = 0xC0000000u;
 constexpr uint32_t kRsrcWord3 = 0x00020000u;   // a raw buffer of dwords on gfx9: DATA_FORMAT 32, no swizzle, no index
-__host__ __device__ inline uint32_t x_bias(int W, int Cin) { return (uint32_t)(W + 1) * (uint32_t)(Cin * 2); }
-// the scalar byte offset of K tile (tap, kc): from a row's own position in x (bias included), and from the start of a weight row
-__host__ __device__ inline uint32_t x_soffset(int W, int Cin, int tap, int kc) {
-  const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
-  return (uint32_t)((dy * W + dx) * Cin * 2 + kc * 128) + x_bias(W, Cin);
-}
-__host__ __device__ inline uint32_t w_soffset(int Cin, int tap, int kc) { return (uint32_t)(tap * Cin * 2 + kc * 128); }
-// does the buffer form take the shape?  (every scalar offset of x below 2^30)
-inline bool bufstage_takes(int wd, int c) { return (2 * (int64_t)wd + 3) * c * 2 < ((int64_t)1 << 30); }
 
 // 64 lanes x 16 B: lane l's 16 bytes land at lds_base + 16 * l (the destination is wave-uniform, the source offset per lane)
 __device__ __forceinline__ void stage16(rsrc_t r, uint32_t voff, uint32_t soff, char* lds_base) {
@@ -129,7 +97,6 @@ __device__ __forceinline__ void raw_barrier() {
   asm volatile("" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
 }
-template <int kV> struct Mode { static constexpr int v = kV; };
 // s_setprio in the main loop.  0: every wave raises its priority for its MFMA segments (shipped); the other two are what the probe
 // timed against it: 1 none, 2 the static form, waves 4..7 at priority 1 for the whole loop.
 #ifndef ELFNET_CONV3X3_PRIO
@@ -146,100 +113,8 @@ __device__ __forceinline__ int fresh_uniform(int v) {
   asm volatile("" : "+s"(v));
   return v;
 }
-
-// Work id -> work.  Work items are numbered tiles fastest, then channel column; ids below nfull are one full item each, and
-// every item from nfull on is two consecutive ids: channel half 0, then half 1.  half < 0: the full 256 channels.
-struct WorkItem { int tile, col, half; };
-__host__ __device__ inline WorkItem work_item(int id, int tiles, int nfull) {
-  int half = -1;
-  if (id >= nfull) {
-    const int e = id - nfull;
-    id = nfull + (e >> 1);
-    half = e & 1;
-  }
-  const int col = id / tiles;
-  return WorkItem{id - col * tiles, col, half};
-}
-// How many of `total` work items stay full when they run `width` at a time: the items of a last round that is at most half full
-// are split (each half then has a CU of its own in that round); a fuller last round, none, or less than one round is left alone.
-__host__ __device__ inline int full_items(int64_t total, int64_t width) {
-  const int64_t r = total % width;
-  return (int)(total >= width && r > 0 && 2 * r <= width ? total - r : total);
-}
-
-// floor(n / d) for every 0 <= n < 2^31 as one multiply and one shift: with l = ceil(log2 d), s = max(32, 31 + l) and
-// mul = floor((2^s - 1) / d), which is below 2^32, e = 2^s - mul d lies in [1, d] and (n + 1) mul / 2^s = (n + 1) / d -
-// (n + 1) e / (d 2^s); (n + 1) e <= 2^31 2^l <= 2^s, so the second term is above 0 and at most 1 / d: the floor is floor(n / d)
-// whether d divides n + 1 or not.  The rounded-up multiplier would need 33 bits at d = 1.  The host makes (mul, shift = s - 32)
-// once per launch; a launch's divisors are H W and W.
-struct Recip { uint32_t mul, shift; };
-inline Recip recip_of(uint32_t d) {   // 1 <= d <= 2^31
-  int l = 0;
-  while (((uint64_t)1 << l) < d) ++l;
-  const int s = l == 0 ? 32 : 31 + l;
-  return Recip{(uint32_t)((((uint64_t)1 << s) - 1) / d), (uint32_t)(s - 32)};
-}
+// udiv_by's quotient per lane (the comment at Recip)
 __device__ __forceinline__ uint32_t div_by(uint32_t n, Recip r) { return __umulhi(n + 1, r.mul) >> r.shift; }
-// the same quotient where the host plans with it too (the deal below); on the device n is wave-uniform there
-__host__ __device__ inline uint32_t udiv_by(uint32_t n, Recip r) { return (uint32_t)(((uint64_t)(n + 1) * r.mul) >> 32) >> r.shift; }
-
-// ---- the two row orders.  A work item is 256 rows x a channel column; row r of it is position base + r * stride, valid for
-// r < limit, and the item visits the taps of `mask` (bit 3 ky + kx), ascending, Cin / 64 K tiles each.
-//   linear  tile t is the positions 256 t .. 256 t + 255: base = 256 t, stride 1, limit = M - base, every tap (0x1FF); what is off
-//           the board is decided per row (decode_rows).  Ids, split last round and deal are work_item's and full_items' above.
-//   board   with B = ceil(rows / 256) blocks of 256 consecutive boards, an item is (block b, board position hw, column): row r is
-//           board 256 b + r at hw, base = 256 b H W + hw, stride H W, limit = rows - 256 b.  Every row has the same taps on the
-//           board, so the item visits only those: 4 for a corner, 6 for an edge, 9 inside.  No half tiles.
-//           id = (rank(hw) * columns + column) * B + b, the block fastest; rank lists the inner positions, then the edges, then
-//           the corners, each class row-major (a board with H or W below 3 has no such classes: rank = hw), so the long items
-//           come first.  With G workgroups and F = ids / G, workgroup g runs g, g + G, ... in the F full rounds and, in the last,
-//           partial round, id F G + (G - 1 - g) if there is one: the last round's items, the shortest, go to the workgroups that
-//           got the shorter items of the round where the classes change.  Static, no workgroup depends on another.
-struct Deal {
-  int board;                 // the row order: 0 linear, 1 board
-  int ids, fullids;          // work ids; board: F G, the ids of the full rounds (linear: never reached)
-  int tiles, nfull;          // linear: work_item's arguments
-  int nblk, per_rank, boards, stride;   // board: B, B * columns, rows, H W (linear: stride 1)
-  Recip dpr, dblk, din, dw;  // board: the divisions by per_rank, B, W - 2 and W
-};
-struct Item { int base, limit, kbase, mask, half; };
-__host__ __device__ inline int tap_mask(int hh, int ww, int H, int W) {
-  const int rowm = (hh > 0 ? 1 : 0) | 8 | (hh + 1 < H ? 64 : 0), colm = (ww > 0 ? 1 : 0) | 2 | (ww + 1 < W ? 4 : 0);
-  return rowm * colm;   // decode_rows has why this is the mask
-}
-// rank -> board position (h, w)
-__host__ __device__ inline void pos_of_rank(int k, int H, int W, Recip din, Recip dw, int& hh, int& ww) {
-  if (H < 3 || W < 3) { hh = (int)udiv_by((uint32_t)k, dw); ww = k - hh * W; return; }
-  const int a = W - 2, inner = (H - 2) * a, side = 2 * (H - 2);
-  if (k < inner) { hh = (int)udiv_by((uint32_t)k, din); ww = k - hh * a + 1; hh += 1; }
-  else if ((k -= inner) < a) { hh = 0; ww = k + 1; }
-  else if ((k -= a) < side) { hh = (k >> 1) + 1; ww = (k & 1) * (W - 1); }
-  else if ((k -= side) < a) { hh = H - 1; ww = k + 1; }
-  else { k -= a; hh = (k >> 1) * (H - 1); ww = (k & 1) * (W - 1); }
-}
-__host__ __device__ inline Item item_of(const Deal& d, int id, int M, int H, int W, int* block = nullptr, int* pos = nullptr) {
-  if (!d.board) {
-    const WorkItem wi = work_item(id, d.tiles, d.nfull);
-    return Item{wi.tile * kTileM, M - wi.tile * kTileM, wi.col * kTileN + (wi.half > 0 ? kTileN / 2 : 0), 0x1FF, wi.half};
-  }
-  const int rank = (int)udiv_by((uint32_t)id, d.dpr), rem = id - rank * d.per_rank;
-  const int col = (int)udiv_by((uint32_t)rem, d.dblk), b = rem - col * d.nblk;
-  int hh, ww;
-  pos_of_rank(rank, H, W, d.din, d.dw, hh, ww);
-  const int hw = hh * W + ww;
-  if (block) *block = b;
-  if (pos) *pos = hw;
-  return Item{b * kTileM * d.stride + hw, d.boards - b * kTileM, col * kTileN, tap_mask(hh, ww, H, W), -1};
-}
-// the id behind `id` on workgroup g of G; at or beyond d.ids: none
-__host__ __device__ inline int next_id(const Deal& d, int id, int g, int G) {
-  if (id >= d.fullids) return d.ids;
-  const int nid = id + G;
-  return nid >= d.fullids ? d.fullids + (G - 1 - g) : nid;
-}
-// the K-tile taps of a mask: the lowest, and the next above t (9 or more: none)
-__host__ __device__ inline int first_tap(int mask) { return __builtin_ctz((unsigned)mask | 0x200u); }
-__host__ __device__ inline int next_tap(int mask, int t) { return t + 1 + __builtin_ctz(((unsigned)mask >> (t + 1)) | 0x200u); }
 
 // What a wave knows about itself and the launch: everything the staging and the epilogue address by.
 struct Ctx {
@@ -626,7 +501,6 @@ __device__ __forceinline__ void main_loop(const Ctx& c, Rows& rw, floatx16 (&acc
 // max(., 0), one rounding to fp16; v_fma_mix_f32 converts its fp16 sources exactly and rounds the fp32 fused multiply-add once, and
 // float(h) * 1.0 + c rounded once is float(h) + c rounded once, so one instruction is the conversion (of both operands, for the
 // bias) and the addition: the same fp32 value, NaN, infinities, zeros' signs and subnormals included.  kHi: the upper half.
-typedef uint32_t uint32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
 template <int kHi>
 __device__ __forceinline__ float add_h_h(uint32_t a, uint32_t b, Mode<kHi>) {   // float(a.half) + float(b.half)
@@ -949,7 +823,9 @@ __global__ __launch_bounds__(64) void k_bufstage_probe(const char* __restrict__ 
   out[lane] = *(const uint32x4*)(dst + lane * 16);
 }
 
-// the CU count of the current device, asked for once per device
+}  // namespace
+
+// the CU count of the current device, asked for once per device (declared in net_conv3x3_plan.h: elfnet_conv3x3_f16_order asks too)
 int round_width_of_device() {
   static std::atomic<int> cus[64];
   int dev = 0;
@@ -961,75 +837,6 @@ int round_width_of_device() {
   }
   return n;
 }
-
-// ---- host: the two plans
-// the linear order's deal for `width` items at a time (0: one id per workgroup)
-Deal linear_deal(int64_t m, int k, int width, int* G) {
-  Deal d{};
-  d.tiles = (int)((m + kTileM - 1) / kTileM);
-  const int64_t total = (int64_t)d.tiles * (k / kTileN);       // below 2^31: m * k is below 2^30
-  d.nfull = width > 0 ? full_items(total, width) : (int)total;
-  d.ids = (int)(2 * total - d.nfull);
-  d.fullids = 1 << 30;
-  d.stride = 1;
-  *G = width > 0 && width < d.ids ? width : d.ids;
-  return d;
-}
-// Does board order take the shape?  Not an item of one K tile (a 1 x 1 board at 64 input channels: the loop's first K tile is at
-// the latest its last but one), and its ids stay below 2^30.
-bool board_takes(int64_t rows, int h, int wd, int c, int k) {
-  const int64_t nblk = (rows + kTileM - 1) / kTileM;
-  return rows > 0 && !((int64_t)h * wd == 1 && c < 128) && nblk * h * wd * (k / kTileN) < ((int64_t)1 << 30);
-}
-Deal board_deal(int64_t rows, int h, int wd, int k, int width, int* G) {
-  Deal d{};
-  d.board = 1;
-  d.nblk = (int)((rows + kTileM - 1) / kTileM);
-  d.per_rank = d.nblk * (k / kTileN);
-  d.boards = (int)rows;
-  d.stride = h * wd;
-  d.ids = d.per_rank * d.stride;
-  *G = width > 0 && width < d.ids ? width : d.ids;
-  d.fullids = d.ids / *G * *G;
-  d.nfull = d.ids;
-  d.dpr = recip_of((uint32_t)d.per_rank);
-  d.dblk = recip_of((uint32_t)d.nblk);
-  d.din = recip_of((uint32_t)(wd > 2 ? wd - 2 : 1));
-  d.dw = recip_of((uint32_t)wd);
-  return d;
-}
-// the K tiles of workgroup g of G, in chunks-per-tap units of `kchunks`: board order
-int64_t board_load(const Deal& d, int g, int G, int h, int wd, int kchunks) {
-  int64_t sum = 0;
-  for (int id = g; id < d.ids; id = next_id(d, id, g, G))
-    sum += (int64_t)__builtin_popcount((unsigned)item_of(d, id, 0, h, wd).mask) * kchunks;
-  return sum;
-}
-// The order the plain entry takes for a shape at `width` items a round: board order iff there are at least 256 rows and its most
-// loaded workgroup has strictly fewer K tiles than the linear order's, which is its full rounds x 9 kchunks plus a last round of
-// 9 kchunks, or of 3/4 of that where it is split (a half tile takes 0.75 of a tile's time: profiles/conv_tail_probe.json).
-// Compared in quarters of a K tile.  Host arithmetic, the same on every call of a shape; the last answer is kept per thread.
-int order_of(int64_t rows, int h, int wd, int c, int k, int width) {
-  if (rows < kTileM || width <= 0 || !board_takes(rows, h, wd, c, k)) return 0;
-  struct Key { int64_t rows; int h, wd, c, k, width, order; };
-  static thread_local Key last{-1, 0, 0, 0, 0, 0, 0};
-  if (last.rows == rows && last.h == h && last.wd == wd && last.c == c && last.k == k && last.width == width) return last.order;
-  const int kchunks = c >> 6;
-  int G = 0;
-  const Deal l = linear_deal(rows * h * wd, k, width, &G);
-  const int64_t total = (int64_t)l.tiles * (k / kTileN), r = total % width;
-  const int64_t lin4 = (total / width * 4 + (r == 0 ? 0 : l.nfull < total ? 3 : 4)) * 9 * kchunks;
-  const Deal b = board_deal(rows, h, wd, k, width, &G);
-  int64_t most = 0;
-  for (int g = 0; g < G && 4 * most < lin4; ++g) {
-    const int64_t v = board_load(b, g, G, h, wd, kchunks);
-    if (v > most) most = v;
-  }
-  last = Key{rows, h, wd, c, k, width, 4 * most < lin4 ? 1 : 0};
-  return last.order;
-}
-
-}  // namespace
 
 // The entry point behind elfnet_conv3x3_f16_width(algo = 1) and elfnet_conv3x3_f16_boards; net_conv.hip has checked pointers,
 // alignment and the size limits (every tensor below 2^31 bytes) and set the device.  One launch on `stream`: no allocation, no
@@ -1062,109 +869,6 @@ extern "C" __attribute__((visibility("hidden"))) int elfnet_conv3x3_native_f16(c
   return e == hipSuccess ? 0 : (int)e;
 }
 
-// Host arithmetic only: the board-order launch of elfnet_conv3x3_f16_boards for a shape and round_width > 0.  Returns its work
-// ids; with id >= 0 also what that id computes: its block of 256 boards, its board position h * W + w, its channel column and its
-// 9-bit tap mask (bit 3 ky + kx: the tap is on the board).
-extern "C" int64_t elfnet_conv3x3_f16_boards_plan(int64_t rows, int h, int wd, int k, int round_width, int64_t id, int* block,
-                                                  int* position, int* column, int* mask) {
-  if (rows <= 0 || h <= 0 || wd <= 0 || k <= 0 || (k & 255) != 0 || round_width <= 0 || !board_takes(rows, h, wd, 128, k))
-    return ELFGO_E_BADARG;
-  int G = 0;
-  const Deal d = board_deal(rows, h, wd, k, round_width, &G);
-  if (id >= 0) {
-    if (id >= d.ids) return ELFGO_E_BADARG;
-    int b = 0, hw = 0;
-    const Item it = item_of(d, (int)id, 0, h, wd, &b, &hw);
-    if (block) *block = b;
-    if (position) *position = hw;
-    if (column) *column = it.kbase / kTileN;
-    if (mask) *mask = it.mask;
-  }
-  return d.ids;
-}
-
-// Host arithmetic only: the deal of that launch.  g < 0: the number of workgroups G.  Otherwise the work id that workgroup g runs
-// as its j-th item (j from 0), or -1 where it has fewer.
-extern "C" int64_t elfnet_conv3x3_f16_boards_deal(int64_t rows, int h, int wd, int k, int round_width, int g, int j) {
-  const int64_t ids = elfnet_conv3x3_f16_boards_plan(rows, h, wd, k, round_width, -1, nullptr, nullptr, nullptr, nullptr);
-  if (ids < 0) return ids;
-  int G = 0;
-  const Deal d = board_deal(rows, h, wd, k, round_width, &G);
-  if (g < 0) return G;
-  if (g >= G || j < 0) return ELFGO_E_BADARG;
-  int id = g;
-  for (; j > 0 && id < d.ids; --j) id = next_id(d, id, g, G);
-  return id < d.ids ? id : -1;
-}
-
-// Host arithmetic only: the K tiles (one tap x 64 input channels of one item) workgroup g of that launch runs through, at c input
-// channels: the sum of popcount(mask) * c / 64 over its items.
-extern "C" int64_t elfnet_conv3x3_f16_boards_load(int64_t rows, int h, int wd, int c, int k, int round_width, int g) {
-  const int64_t G = elfnet_conv3x3_f16_boards_deal(rows, h, wd, k, round_width, -1, 0);
-  if (G < 0) return G;
-  if (c <= 0 || (c & 63) != 0 || g < 0 || g >= G || !board_takes(rows, h, wd, c, k)) return ELFGO_E_BADARG;
-  int G2 = 0;
-  const Deal d = board_deal(rows, h, wd, k, round_width, &G2);
-  return board_load(d, g, G2, h, wd, c >> 6);
-}
-
-// The order elfnet_conv3x3_f16(algo 1) takes for a shape: 0 linear, 1 board (order_of).  round_width 0: at the current device's
-// CU count, as the plain entry (an unknown count: linear); above 0: host arithmetic only, at that width.
-extern "C" int elfnet_conv3x3_f16_order(int64_t rows, int h, int wd, int c, int k, int round_width) {
-  if (rows < 0 || h <= 0 || wd <= 0 || c <= 0 || k <= 0 || (c & 63) != 0 || (k & 255) != 0 || round_width < 0) return ELFGO_E_BADARG;
-  if (rows * h * wd * (int64_t)(c > k ? c : k) >= ((int64_t)1 << 30)) return ELFGO_E_BADARG;
-  return order_of(rows, h, wd, c, k, round_width > 0 ? round_width : round_width_of_device());
-}
-
-// Host arithmetic only: how elfnet_conv3x3_f16_width lays a launch of tiles x columns work items out for round_width > 0.
-extern "C" int64_t elfnet_conv3x3_f16_plan(int64_t tiles, int columns, int round_width, int64_t id, int* tile, int* column, int* half) {
-  if (tiles <= 0 || columns <= 0 || round_width <= 0 || tiles * columns >= ((int64_t)1 << 30)) return ELFGO_E_BADARG;
-  const int64_t total = tiles * columns;
-  const int nfull = full_items(total, round_width);
-  const int64_t groups = 2 * total - nfull;
-  if (tile || column || half) {
-    if (id < 0 || id >= groups) return ELFGO_E_BADARG;
-    const WorkItem wi = work_item((int)id, (int)tiles, nfull);
-    if (tile) *tile = wi.tile;
-    if (column) *column = wi.col;
-    if (half) *half = wi.half;
-  }
-  return groups;
-}
-
-// Host arithmetic only: the multiplier and the shift the kernel divides a position by `divisor` with (recip_of): for every
-// 0 <= n < 2^31, n / divisor == (((n + 1) * mul) >> 32) >> shift, the product in 64 bits.
-extern "C" int elfnet_conv3x3_f16_recip(int64_t divisor, uint32_t* mul, uint32_t* shift) {
-  if (divisor < 1 || divisor > ((int64_t)1 << 31) || !mul || !shift) return ELFGO_E_BADARG;
-  const Recip r = recip_of((uint32_t)divisor);
-  *mul = r.mul;
-  *shift = r.shift;
-  return 0;
-}
-
-// Host arithmetic only: what the kernel's buffer-addressed staging addresses a shape by (the comment at kSentinel; the kernel calls
-// the same functions).  bias: how far x's descriptor starts in front of x; x_records, w_records: the two descriptors' num_records;
-// sentinel: the vector offset of a lane that stages zeros.  With 0 <= tap < 9 and 0 <= kc < c / 64 also the scalar offsets of K
-// tile (tap, kc); tap < 0: the shape's values alone.  The vector offset of position p's 16-byte chunk q is p * c * 2 + 16 q in x,
-// that of output channel n's is n * 9 * c * 2 + 16 q in w.  Refuses what the launch refuses.
-extern "C" int elfnet_conv3x3_f16_bufstage(int64_t rows, int h, int wd, int c, int k, int tap, int kc, uint32_t* bias,
-                                           uint32_t* x_records, uint32_t* w_records, uint32_t* sentinel, uint32_t* x_soff,
-                                           uint32_t* w_soff) {
-  if (rows <= 0 || h <= 0 || wd <= 0 || c <= 0 || k <= 0 || (c & 63) != 0 || (k & 255) != 0 || tap >= 9) return ELFGO_E_BADARG;
-  if (rows * h * wd * (int64_t)(c > k ? c : k) >= ((int64_t)1 << 30) || (int64_t)k * 9 * c >= ((int64_t)1 << 30)) return ELFGO_E_BADARG;
-  if (!bufstage_takes(wd, c) || (tap >= 0 && (kc < 0 || kc >= (c >> 6)))) return ELFGO_E_BADARG;
-  const uint32_t b = x_bias(wd, c);
-  if (bias) *bias = b;
-  if (x_records) *x_records = (uint32_t)(rows * h * wd) * (uint32_t)(c * 2) + b;
-  if (w_records) *w_records = (uint32_t)k * (uint32_t)(9 * c * 2);
-  if (sentinel) *sentinel = kSentinel;
-  if (tap >= 0) {
-    if (x_soff) *x_soff = x_soffset(wd, c, tap, kc);
-    if (w_soff) *w_soff = w_soffset(c, tap, kc);
-  }
-  return 0;
-}
-
 // One staged piece of one wave, for the test of what the hardware does with a lane that is out of range: 1 KiB of LDS at byte
 // lds_offset (a multiple of 1024, below 160 KiB) is filled with 0xFF, lane l stages 16 bytes from voffset[l] + soffset through a
 // raw buffer descriptor of `records` bytes at src with the kernel's own instruction, and the KiB is copied to out.  src, voffset
@@ -1178,10 +882,4 @@ extern "C" int elfnet_conv3x3_f16_bufstage_probe(const void* src, uint32_t recor
                      (const uint32_t*)voffset, soffset, lds_offset, (uint32x4*)out);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
-}
-
-// Host arithmetic only: the workgroups of that launch.  Workgroup g runs the work ids g, g + G, g + 2 G, ... of the plan.
-extern "C" int64_t elfnet_conv3x3_f16_grid(int64_t tiles, int columns, int round_width) {
-  const int64_t ids = elfnet_conv3x3_f16_plan(tiles, columns, round_width, 0, nullptr, nullptr, nullptr);
-  return ids < 0 ? ids : round_width < ids ? round_width : ids;
 }

@@ -28,18 +28,10 @@
 // The operands are swapped in the MFMA (A = weights, B = activations), as in algo 1: a lane's accumulator registers run along the
 // channels, four consecutive channels of one position per register group.
 //
-// This translation unit includes nothing from CK and nothing of the project but the C header: it is its own object (GNUmakefile).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/elf_amd.h"
-
+// This translation unit includes nothing from CK and nothing of the project but net_common.h: it is its own object (GNUmakefile).
+#include "net_common.h"
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int kTileM = 64;                       // positions per workgroup
 constexpr int kTileN = 64;                       // output channels per workgroup
@@ -55,7 +47,6 @@ constexpr int kLoadsPerTile = 4;                 // LDS-DMA loads one wave issue
 __device__ __attribute__((aligned(128))) unsigned char g_zero_line_small[128] = {0};
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 // 64 lanes x 16 B: lane l's 16 bytes land at lds_base + 16 * l (the destination is wave-uniform, the source per lane)
 __device__ __forceinline__ void stage16(const char* src, char* lds_base) {
@@ -73,7 +64,6 @@ __device__ __forceinline__ void raw_barrier() {
   asm volatile("" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
 }
-template <int kV> struct Mode { static constexpr int v = kV; };
 
 template <bool kHasRes>
 __global__ __launch_bounds__(kThreads) void k_conv3x3_small_f16(const char* __restrict__ x, const char* __restrict__ w,
@@ -231,35 +221,17 @@ __global__ __launch_bounds__(kThreads) void k_conv3x3_small_f16(const char* __re
   }
 }
 
-// net_conv.hip's DevGuard
-struct DevGuard {
-  int prev = -1;
-  explicit DevGuard(int dev) {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur != dev && hipSetDevice(dev) == hipSuccess) prev = cur;
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  DevGuard(const DevGuard&) = delete;
-  DevGuard& operator=(const DevGuard&) = delete;
-};
-
 }  // namespace
 
-// elfnet_conv3x3_f16_width's argument checks, and C and K multiples of 64.  One launch on `stream`: no allocation, no memset, no
-// workspace, no synchronisation, no copy; every refusal comes before it.
+// The convolution entries' argument checks (conv_args), and C and K multiples of 64.  One launch on `stream`: no allocation, no
+// memset, no workspace, no synchronisation, no copy; every refusal comes before it.
 extern "C" int elfnet_conv3x3_small_f16(const void* x, const void* w, const void* bias, const void* res, void* y, int64_t rows, int h,
                                         int wd, int c, int k, int relu, void* stream) {
-  if (!x || !w || !bias || !y || rows < 0 || h <= 0 || wd <= 0 || c <= 0 || k <= 0) return ELFGO_E_BADARG;
   if ((c & 63) != 0 || (k & 63) != 0) return ELFGO_E_BADARG;
-  if ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)res | (uintptr_t)y) & 15) != 0) return ELFGO_E_BADARG;
-  if (y == x || y == res) return ELFGO_E_BADARG;
-  // byte offsets are 32-bit in the kernel: every tensor stays below 2^31 bytes
-  const int64_t cmax = c > k ? c : k;
-  if (rows * h * wd * cmax >= ((int64_t)1 << 30) || (int64_t)k * 9 * c >= ((int64_t)1 << 30)) return ELFGO_E_BADARG;
-  if (rows == 0) return 0;
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, x) != hipSuccess) { (void)hipGetLastError(); return ELFGO_E_BADARG; }
-  DevGuard _dg(at.device);
+  int dev = 0;
+  const int go = conv_args(x, 16, w, bias, res, y, rows, h, wd, c, k, &dev);
+  if (go <= 0) return go;
+  DevGuard _dg(dev);
   const int64_t m = rows * h * wd;
   const dim3 grid((unsigned)((m + kTileM - 1) / kTileM), (unsigned)(k / kTileN));   // below 2^18 x below 2^15 by the limits above
   hipStream_t st = (hipStream_t)stream;

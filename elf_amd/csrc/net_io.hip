@@ -27,31 +27,12 @@
 //                   value_linear1's vh), the lanes striding along the weight row, a fixed shuffle tree; softmax and the value's
 //                   last layer + tanh from LDS.  No atomics anywhere: repeated launches return the same bits.
 //
-// This translation unit includes nothing of the project but the C header: it is its own object (GNUmakefile).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/elf_amd.h"
+// This translation unit includes nothing of the project but net_common.h: it is its own object (GNUmakefile).
+#include "net_common.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// net_conv.hip's device guard (that file is CK's translation unit; engine_host.h pulls the board kernels in)
-struct DevGuard {
-  int prev = -1;
-  explicit DevGuard(int dev) {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur != dev && hipSetDevice(dev) == hipSuccess) prev = cur;
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  DevGuard(const DevGuard&) = delete;
-  DevGuard& operator=(const DevGuard&) = delete;
-};
 
 // ------------------------------------------------------------------------------------------------ the input convolution
 
@@ -86,7 +67,7 @@ __global__ __launch_bounds__(kInThreads, kSteps <= 11 ? 4 : 2) void k_conv3x3_in
   // ---- the wave's weights: A fragment of step s = row (channel) fr, k = 16 s + 8 fh .. + 7 of the flattened [9 C] weight row;
   // zeros beyond 9 C (9 C is even: a pair is inside or outside as a whole)
   const bool has_n = kbase + wv * 32 < K;         // wave-uniform
-  u32x4 wf[kSteps];                               // four packed pairs = the half8 of one MFMA step
+  uint32x4 wf[kSteps];                              // four packed pairs = the half8 of one MFMA step
 #pragma unroll
   for (int s = 0; s < kSteps; ++s) {
     const uint32_t* wr = (const uint32_t*)(w + (size_t)(has_n ? kbase + wv * 32 + fr : 0) * kreal);   // 9 C is even: rows are 4-B aligned
@@ -392,16 +373,12 @@ inline size_t heads_ws_bytes(int64_t rows, int64_t d) { return (size_t)rows * 3 
 
 extern "C" int elfnet_conv3x3_in_f16(const void* x, const void* w, const void* bias, void* y, int64_t rows, int h, int wd, int c, int k,
                                      int relu, void* stream) {
-  if (!x || !w || !bias || !y || rows < 0 || h <= 0 || wd <= 0) return ELFGO_E_BADARG;
   if (c < 2 || c > kInMaxC || (c & 1) != 0 || k <= 0 || (k & 31) != 0) return ELFGO_E_BADARG;
-  if ((((uintptr_t)w | (uintptr_t)bias | (uintptr_t)y) & 15) != 0 || ((uintptr_t)x & 3) != 0) return ELFGO_E_BADARG;
-  if (y == x) return ELFGO_E_BADARG;
-  // every tensor below 2^31 bytes, as for elfnet_conv3x3_f16 (k >= c here)
-  if (rows * h * wd * k >= ((int64_t)1 << 30) || (int64_t)k * 9 * c >= ((int64_t)1 << 30)) return ELFGO_E_BADARG;
-  if (rows == 0) return 0;
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, x) != hipSuccess) { (void)hipGetLastError(); return ELFGO_E_BADARG; }
-  DevGuard _dg(at.device);
+  // elfnet_conv3x3_f16's checks with no skip; x is read in channel pairs, so 4-byte aligned is enough for it
+  int dev = 0;
+  const int go = conv_args(x, 4, w, bias, nullptr, y, rows, h, wd, c, k, &dev);
+  if (go <= 0) return go;
+  DevGuard _dg(dev);
   const int m = (int)(rows * h * wd);
   const int tiles = (m + kInTileM - 1) / kInTileM;
   const int gy = (k + kInTileN - 1) / kInTileN;
