@@ -129,6 +129,10 @@ SIGNATURES = {
     "elfrq_sizes": (_i, [_vp, _vp]),
     "elfrq_set_threads": (_i, [_vp, _i, _i64, C.c_uint64]),
     "elfrq_draw": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "elfrq_dev_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "elfrq_dev_destroy": (_i, [_vp]),
+    "elfrq_dev_draw": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "elfrq_dev_status": (_i, [_vp, _vp]),
     "elfsp_progress": (_i, [_vp, _vp]),
     "elfsp_set_pick_seed": (_i, [_vp, C.c_uint32]),
     "elfsp_game_actor": (_i, [_vp, _i]),

@@ -6,6 +6,7 @@
 // Record::createFromJson reads it back field for field.
 #include "record_host.h"
 #include "host_workers.h"
+#include "rq_host.h"
 
 #include <atomic>
 #include <math.h>
@@ -661,16 +662,7 @@ int elfrec_quantise_policy(int board_size, const int32_t* coord, const float* pr
 // (elf/distributed/shared_reader.h:165-340): num_reader queues, each a deque bounded by queue_max_size (ReaderQueueT::Insert :88-100),
 // filled by TrainCtrl::OnReceive with InsertWithParity(record, rng, reward > 0) (train/game_ctrl.h:306-311; shared_reader.h:212-219):
 // games Black won go to the odd queues, the others to the even ones.  A record here is a handle (a slot of an ElfReplay store).
-struct ElfReaderQueues {
-  struct Rec { int32_t slot, num_moves; };
-  std::vector<std::deque<Rec>> qs;
-  size_t queue_min_size = 1, queue_max_size = 1000;
-  int parity_sizes[2] = {0, 0};
-  bool min_size_satisfied = false;
-  std::mt19937 insert_rng;                 // TrainCtrl::rng_ (game_ctrl.h:244,367)
-  std::vector<std::mt19937> thread_rng;    // GoGameBase::_rng of every GoGameTrain game thread (common/game_base.h:32-38)
-  int64_t next_act = 0;                    // acts go round the threads
-};
+// struct ElfReaderQueues is rq_host.h's: rq_device.hip mirrors it on the device.
 
 int elfrq_create(int num_reader, int queue_min_size, int queue_max_size, uint32_t insert_seed, ElfReaderQueues** out) {
   if (!out || num_reader < 2 || (num_reader & 1) || queue_min_size < 1 || queue_max_size < queue_min_size) return ELFGO_E_BADARG;
@@ -686,6 +678,7 @@ int elfrq_create(int num_reader, int queue_min_size, int queue_max_size, uint32_
 }
 
 int elfrq_destroy(ElfReaderQueues* q) {
+  if (q && q->dev) (void)elfrq_dev_destroy(q->dev);   // the mirror reads q: it goes first
   delete q;
   return 0;
 }
@@ -704,6 +697,7 @@ int elfrq_insert(ElfReaderQueues* q, int32_t slot, int32_t num_moves, int black_
     delta--;
   }
   q->parity_sizes[idx % 2] += delta;
+  if (q->dev) rq_note_insert(q, idx, delta == 0);
   if (evicted) *evicted = out;
   return idx;
 }

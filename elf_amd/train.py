@@ -255,7 +255,10 @@ def records_of_message(text):
 
 class ReaderQueues:
     """elf::shared::ReaderQueuesT<Record> + the draws of GoGameTrain::act over it (elfrq_*, host only): see include/elf_amd.h.
-    Records are handles (slots of a ReplayLoader)."""
+    Records are handles (slots of a ReplayLoader).
+    attach_device(device) puts a mirror of the queues and every game thread's generator, as they are then, on the GPU;
+    draw_device() then draws there (k_rq_draw, elfrq_dev_*): a stream of draws of its own, equal to what draw() gives from the same
+    state, that needs no host work per sample.  The host's draw() / draw_into() go on independently."""
 
     def __init__(self, num_reader=50, queue_min_size=10, queue_max_size=1000, insert_seed=0, num_threads=1, seed=0, job_id=""):
         self.L = _lib.lib()
@@ -265,8 +268,12 @@ class ReaderQueues:
         self.num_reader = int(num_reader)
         from .selfplay import job_hash
         check(self.L.elfrq_set_threads(self._h, int(num_threads), int(seed), job_hash(job_id)))
+        self._dev = None
 
     def close(self):
+        if getattr(self, "_dev", None):
+            self.L.elfrq_dev_destroy(self._dev)
+            self._dev = None
         if getattr(self, "_h", None):
             self.L.elfrq_destroy(self._h)
             self._h = None
@@ -304,15 +311,51 @@ class ReaderQueues:
             raise ValueError("host must be a contiguous int32 tensor [3, >= num_acts * 64]")
         check(self.L.elfrq_draw(self._h, int(num_acts), int(num_future_actions), host[0].data_ptr(), host[1].data_ptr(), host[2].data_ptr()))
 
+    def attach_device(self, device=0):
+        """snapshot the queues, the generators and the turn counter onto `device` (once: later calls change nothing)"""
+        if self._dev is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("elf_amd.ReaderQueues.attach_device needs a ROCm GPU (no CPU fallback exists)")
+            self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+            h = C.c_void_p()
+            check(self.L.elfrq_dev_create(self._h, int(self.device.index or 0), C.byref(h)))
+            self._dev = h
+
+    def _dev_stream(self):
+        if self._dev is None:
+            raise RuntimeError("no device handle: call attach_device() first")
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def draw_device(self, num_acts, num_future_actions=1, out=None):
+        """num_acts x 64 draws on the GPU, on the current stream -> device int32 tensor [3, num_acts * 64] (slot, move_to, d4);
+        out: a contiguous int32 tensor [3, >= num_acts * 64] on the attached device to draw into (its first columns are returned)"""
+        s = self._dev_stream()
+        k = 64 * int(num_acts)
+        if out is None:
+            out = torch.empty((3, k), dtype=torch.int32, device=self.device)
+        elif (out.dtype != torch.int32 or out.dim() != 2 or out.shape[0] != 3 or out.shape[1] < k or not out.is_contiguous()
+              or out.device != self.device):
+            raise ValueError("out must be a contiguous int32 tensor [3, >= num_acts * 64] on the attached device")
+        check(self.L.elfrq_dev_draw(self._dev, int(num_acts), int(num_future_actions), C.c_void_p(out[0].data_ptr()),
+                                    C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()), s))
+        return out[:, :k]
+
+    def device_status(self):
+        """waits for the current stream; 0, or ELFGO_E_NODATA (-4) once a device draw ran into the retry bound"""
+        return self.L.elfrq_dev_status(self._dev, self._dev_stream())
+
 
 class ReplayBuffer:
     """The trainer's replay buffer as the reference keeps and samples it: records arrive (TrainCtrl::OnReceive ->
     InsertWithParity), live in ReaderQueues until their queue drops them, and train batches are what GoGameTrain game threads
     draw from the queues -- here the records sit in an HBM store (ReplayLoader), the queues hold their slots, and one
-    k_replay_extract launch produces the rows of `acts` acts (64 rows each)."""
+    k_replay_extract launch produces the rows of `acts` acts (64 rows each).
+    device_draws=False (default): the game threads' draws are made on the host (elfrq_draw) and copied to the device.
+    device_draws=True: the queues are attached to the loader's device at construction and every sample draws there
+    (ReaderQueues.draw_device) -- the same samples, with no host draw, no host-to-device copy and no wait for the stream."""
 
     def __init__(self, board_size=19, num_reader=50, queue_min_size=10, queue_max_size=1000, batchsize=2048, batches_per_launch=1,
-                 insert_seed=0, num_threads=None, seed=0, job_id="", **loader_kw):
+                 insert_seed=0, num_threads=None, seed=0, job_id="", device_draws=False, **loader_kw):
         if batchsize % 64:
             raise ValueError("batchsize must be a multiple of 64 (GoGameTrain sends 64 states per act)")
         capacity = int(num_reader) * int(queue_max_size) + 1     # a slot is freed only after the insert that evicts it
@@ -327,6 +370,9 @@ class ReplayBuffer:
         self._ring = [(torch.zeros((3, B), dtype=torch.int32).pin_memory(), torch.zeros((3, B), dtype=torch.int32, device=self.loader.device),
                        torch.cuda.Event()) for _ in range(3)]
         self._turn = 0
+        self.device_draws = bool(device_draws)
+        if self.device_draws:
+            self.queues.attach_device(self.loader.device)
 
     def close(self):
         self.queues.close()
@@ -362,6 +408,8 @@ class ReplayBuffer:
         events = (start, end) torch.cuda.Events recorded around the extraction kernel"""
         acts = int(acts or self.loader.batchsize // 64)
         k = 64 * acts
+        if self.device_draws:
+            return self._sample_device(acts, k, out, events)
         host, dev, done = self._ring[self._turn]
         self._turn = (self._turn + 1) % len(self._ring)
         if k > host.shape[1]:
@@ -370,6 +418,18 @@ class ReplayBuffer:
         self.queues.draw_into(host, acts, self.loader.nfa)
         dev[:, :k].copy_(host[:, :k], non_blocking=True)
         done.record(torch.cuda.current_stream(self.loader.device))
+        if events:
+            events[0].record()
+        b = self.loader.extract(dev[0, :k], dev[1, :k], dev[2, :k], out=out)
+        if events:
+            events[1].record()
+        return b
+
+    def _sample_device(self, acts, k, out, events):
+        dev = self.loader._draw                  # the loader's own draw tensor: launches on one stream follow each other
+        if k > dev.shape[1]:
+            raise ValueError("more samples than the loader's batchsize x batches_per_launch")
+        self.queues.draw_device(acts, self.loader.nfa, out=dev)
         if events:
             events[0].record()
         b = self.loader.extract(dev[0, :k], dev[1, :k], dev[2, :k], out=out)

@@ -811,6 +811,28 @@ int elfrq_set_threads(ElfReaderQueues* q, int num_threads, int64_t seed, uint64_
  * again; move_to = rng() % (num_moves - num_future_actions + 1)), generateD4Code (rng() % 8).  Host int32 arrays of num_acts * 64:
  * feed them to elftrain_extract.  ELFGO_E_BADARG while a queue holds fewer than queue_min_size records (the reference waits). */
 int elfrq_draw(ElfReaderQueues* q, int num_acts, int num_future_actions, int32_t* slot, int32_t* move_to, int32_t* d4);
+/* The same draws on the GPU (k_rq_draw: one wavefront per game thread, its mt19937 in LDS), over a device mirror of the queues.
+ * elfrq_dev_create snapshots q as it is at the call -- every game thread's generator (any state, not only a freshly seeded one),
+ * the turn counter and the queues' contents -- onto `device`.  From then on the handle owns a stream of draws of its own that
+ * continues from that state, and elfrq_draw keeps the host's, independently: from the same state, and with the same inserts, the
+ * two give the same triples call for call.  elfrq_set_threads after elfrq_dev_create does not reach the handle.  One handle per
+ * ElfReaderQueues (ELFGO_E_BADARG for a second one, for more than 4096 queues and for a queue_max_size above 2^30); elfrq_destroy destroys a handle still attached.
+ * Neither the handle nor elfrq_insert on its queues is safe for use from two host threads at once.
+ * elfrq_dev_draw first brings the mirror up to date on `stream` with what elfrq_insert did since the last call (through pinned
+ * staging that is reused only behind an event), then launches the draws there: a draw sees the queues exactly as they were when
+ * elfrq_dev_draw was called, whatever is inserted after it returns; with nothing inserted it queues the one kernel and no copy.
+ * dev_slot / dev_move_to / dev_d4: device int32 [num_acts * 64], written on `stream`.  Calls on different streams are the
+ * caller's to order.  The refusals of elfrq_draw at call time are made on the host, with its return codes (a queue below
+ * queue_min_size before the first draw, no eligible record: ELFGO_E_BADARG).  What elfrq_draw finds out while drawing -- a state
+ * that has not found a record after 2^20 tries -- the device cannot undo: there is NO rollback.  The state gets slot 0 / move_to 0,
+ * the generators and the turn counter keep what was consumed, and a sticky word on the device is set, which elfrq_dev_status
+ * (it synchronises `stream`) reports as ELFGO_E_NODATA from then on; 0 otherwise. */
+typedef struct ElfRqDevice ElfRqDevice;
+int elfrq_dev_create(ElfReaderQueues* q, int device, ElfRqDevice** out);
+int elfrq_dev_destroy(ElfRqDevice* d);
+int elfrq_dev_draw(ElfRqDevice* d, int num_acts, int num_future_actions, int32_t* dev_slot, int32_t* dev_move_to, int32_t* dev_d4,
+                   void* stream);
+int elfrq_dev_status(ElfRqDevice* d, void* stream);
 /* one launch: replay record rec[i] up to move_to[i] (switchBeforeMove), then every extractor of the "train" batch under
  * D4 code d4[i] (NULL = 0).  rec/move_to/d4 device int32 [n].  n <= elfgo_capacity(e) only while keep_states is on (sample i
  * replays in board slot i); with keep_states off n is not limited by the engine.  A move_to beyond the record is taken as its
