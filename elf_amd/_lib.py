@@ -56,6 +56,7 @@ SIGNATURES = {
     "elfgo_playout_cand": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "elfgo_own_run_cand": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "elfgo_life_map": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "elfgo_pass_alive": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "elfgo_region_moves": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "elfgo_ld_run": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "elfgo_df_create": (_i, [_vp, C.POINTER(_vp)]),

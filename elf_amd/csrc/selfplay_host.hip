@@ -1323,6 +1323,9 @@ int elfsp_search_log(const ElfSelfPlay* sp, int first, int n, ElfSpSearch* rec, 
 // k_playout_ld in region.cuh over candidates.cuh, life.cuh and playout.cuh's harness (playout_pairs, planned by ownership_host.h's
 // own_plan), entry points in region_host.h, here for the same reason.
 #include "region_host.h"
+// Benson's pass-alive chains and their safe regions (elfgo_pass_alive): k_pass_alive in benson.cuh, entry point in benson_host.h,
+// here for the same reason.
+#include "benson_host.h"
 // DarkForest features (elfgo_df_*, elfgo_extract_df): k_extract_df and the placement-ply table's kernels in df_features.cuh,
 // entry points in df_host.h, here for the same reason.
 #include "df_host.h"

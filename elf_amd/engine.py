@@ -96,6 +96,33 @@ class LifeMap:
         return white.to(torch.uint8) * 2 + (black & ~white).to(torch.uint8)
 
 
+PASS_ALIVE_FIELDS = ("chains", "stones", "safe_points", "rounds")   # PassAlive.summary: these four per colour, Black first
+PASS_ALIVE_BOUND_HIT = -1 << 31   # the top bit of a rounds word: a loop bound of the device code was hit (never expected)
+
+
+class PassAlive:
+    """What GoEngine.pass_alive returns: the device tensors of elfgo_pass_alive -- map uint8 [k, N*N] (bit 0 / 1 a Black / White
+    stone of a pass-alive chain, bit 2 / 3 a safe point of Black / White) and summary int32 [k, 8] (PASS_ALIVE_FIELDS per colour)."""
+
+    def __init__(self, map, summary):
+        self.map, self.summary = map, summary
+
+    def alive(self, colour):
+        """bool [k, N*N]: the stones of the pass-alive chains of colour (1 Black, 2 White)"""
+        return (self.map & (1 << (_colour(colour) - 1))) != 0
+
+    def safe(self, colour):
+        """bool [k, N*N]: the safe points of colour (1 Black, 2 White): the regions its pass-alive chains enclose, dead opponent
+        stones included"""
+        return (self.map & (4 << (_colour(colour) - 1))) != 0
+
+
+def _colour(colour):
+    if colour not in (1, 2):
+        raise ValueError("colour must be 1 (Black) or 2 (White)")
+    return int(colour)
+
+
 LD_INFO_FIELDS = ("left", "top", "right", "bottom", "attacker", "defender", "to_move", "lives")
 LD_STAT_FIELDS = ("lived", "survived", "defender_stones", "attacker_stones", "superko", "steps", "hash_sum", "reserved")
 
@@ -456,6 +483,16 @@ class GoEngine:
                                     C.c_void_p(semi.data_ptr()), C.c_void_p(alive.data_ptr()), C.c_void_p(summary.data_ptr()),
                                     self._stream()))
         return LifeMap(eye, semi, alive, summary)
+
+    def pass_alive(self, ids=None, n=None):
+        """Benson's unconditional life of each position, both colours at once (elfgo_pass_alive) -> PassAlive with device tensors,
+        index a = x*N + y: the chains that cannot be captured even if their owner passes for ever, and the regions they enclose.
+        No playouts and no threshold.  A row whose slot id lies outside the pool gets map 0 and summary -1."""
+        t, p, k = self._ids(ids, n)
+        m = torch.empty((k, self.n * self.n), dtype=torch.uint8, device=self.device)
+        summary = torch.empty((k, 2 * len(PASS_ALIVE_FIELDS)), dtype=torch.int32, device=self.device)
+        check(self.L.elfgo_pass_alive(self._h, p, k, C.c_void_p(m.data_ptr()), C.c_void_p(summary.data_ptr()), self._stream()))
+        return PassAlive(m, summary)
 
     def fast_score(self, ids=None, n=None, rule="chinese"):
         """getFastScore (base/board.cc:1924-1952) from Black's side -> int32 tensor [k]: stones plus true eyes under "chinese",

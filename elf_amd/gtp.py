@@ -7,8 +7,8 @@ same replies ("= ..." / "? ..."), same coordinate letters (no 'I'): protocol_ver
 clear_board, play, genmove, showboard, final_score, list_commands, quit/exit.  On top of the reference's set (whose `u` / `h`
 commands are commented out, console_lib.py:196-204): undo, fixed_handicap, place_free_handicap, set_free_handicap, loadsgf,
 known_command -- what every GTP front-end sends -- over SelfPlay.setup / SelfPlay.undo; final_status_list and the private
-elf-ownership, elf-score_estimate, elf-ladders, elf-candidates, elf-region_candidates, elf-eyes, elf-life, elf-fast_score and
-elf-ld_read over the per-point answers of the board engine; lz-genmove_analyze (Leela Zero's analysing genmove, what Sabaki and
+elf-ownership, elf-score_estimate, elf-ladders, elf-candidates, elf-region_candidates, elf-eyes, elf-life, elf-pass_alive, elf-fast_score
+and elf-ld_read over the per-point answers of the board engine; lz-genmove_analyze (Leela Zero's analysing genmove, what Sabaki and
 Lizzie send) and elf-analysis over the search's candidates and lines (SelfPlay.analyze).
 
     eng = GtpEngine(actor, board_size=19, mcts_rollout_per_thread=1600)     # actor(batch) -> dict(pi=..., V=...)
@@ -100,6 +100,7 @@ class GtpEngine:
         self.commands["elf-candidates"] = self.commands.pop("elf_candidates")
         self.commands["elf-eyes"] = self.commands.pop("elf_eyes")
         self.commands["elf-life"] = self.commands.pop("elf_life")
+        self.commands["elf-pass_alive"] = self.commands.pop("elf_pass_alive")
         self.commands["elf-fast_score"] = self.commands.pop("elf_fast_score")
         self.commands["elf-region_candidates"] = self.commands.pop("elf_region_candidates")
         self.commands["elf-ld_read"] = self.commands.pop("elf_ld_read")
@@ -464,6 +465,15 @@ class GtpEngine:
         silent about every other group."""
         alive = self.boards.life_map(ids=[0]).alive.cpu().numpy()[0]
         return True, " ".join(self._vertex(a) for a in range(self.n * self.n) if alive[a])
+
+    def on_elf_pass_alive(self, items):
+        """elf-pass_alive: the stones of the pass-alive chains of both colours (Benson's unconditional life, GoEngine.pass_alive),
+        in board order like elf-life; elf-pass_alive territory: the safe points, the regions those chains enclose."""
+        if len(items) > 2 or (len(items) == 2 and items[1] != "territory"):
+            return False, "invalid arguments"
+        bits = 12 if len(items) == 2 else 3
+        m = self.boards.pass_alive(ids=[0]).map.cpu().numpy()[0]
+        return True, " ".join(self._vertex(a) for a in range(self.n * self.n) if m[a] & bits)
 
     def on_elf_fast_score(self, items):
         """elf-fast_score [chinese|japanese]: getFastScore from Black's side, an integer; no komi is applied, as in the reference."""

@@ -191,6 +191,23 @@ int elfgo_own_run_cand(ElfGoOwnership* o, const int32_t* ids, const uint64_t* se
 int elfgo_life_map(ElfGoEngine* e, const int32_t* ids, int n, const int32_t* regions, uint8_t* eye, int16_t* semi_move,
                    uint8_t* alive, int32_t* summary, void* stream);
 
+/* Benson's unconditional life of a position, for both colours at once: the chains that cannot be captured even if their owner
+ * passes for ever, and the regions they enclose.  For a colour X: the chains are its groups; the regions are the 4-connected
+ * components of the points without an X stone (empty points and opponent stones); a region is vital to a chain if it has an
+ * empty point and every empty point of it is adjacent to a stone of the chain.  Repeat until nothing changes: (1) remove every
+ * chain with fewer than two surviving vital regions, (2) remove every region that borders a removed chain.  The surviving chains
+ * are pass-alive; a surviving region that is vital to a surviving chain is safe, opponent stones inside included (they are
+ * unconditionally dead).  A region that borders no chain is never safe.  No playouts, no threshold; it needs no side to move.
+ *     map[i][a]   uint8, a = x*N + y (elfgo_area_map's order): bit 0 a Black stone of a pass-alive chain, bit 1 a White one,
+ *                 bit 2 a safe point of Black, bit 3 a safe point of White
+ *     summary[i]  int32 [8], four words per colour, Black first: pass-alive chains, pass-alive stones, safe points, and the
+ *                 number of rounds (1)+(2) run, the last one -- which changes nothing -- included.  The top bit of the rounds
+ *                 word is set if a loop bound of the device code was hit (never expected); the colour's other answers are then 0.
+ * Device pointers, row strides N*N and 8; either output may be NULL, not both.  ids NULL = slots [0, n).  A row whose slot id
+ * lies outside the pool gets map 0 and summary all -1.  The slots are only read; a slot may be named several times.
+ * ELFGO_E_BADARG for a null engine, n <= 0, ids NULL with n above the capacity, or both outputs NULL: nothing is launched. */
+int elfgo_pass_alive(ElfGoEngine* e, const int32_t* ids, int n, uint8_t* map, int32_t* summary, void* stream);
+
 /* The reference's Region move lists of board slots (base/board.cc), per row i, a = x*N + y, all uint8:
  *     cand[i][a]   1 iff a is in FindAllCandidateMovesInRegion(board, &box, next_player, self_atari_thres) (:892-947): the
  *                  legal points of the side to move inside the box that are neither its own true eye nor a self-atari of
