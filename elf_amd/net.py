@@ -168,8 +168,12 @@ class FusedInferenceNet:
     hand-written 64 x 64 x 64 kernel behind `elfnet_conv3x3_small_f16` (elf_amd/csrc/net_conv3x3_small.hip) for calls of at most
     `small_max_positions` positions with C and K multiples of 64: a single game's 16-row call is 364 workgroups there and 46 in
     algo 0 (`_use_small`).
-    Every other convolution (the 18-plane input conv, bf16 nets, a weight that is not channels_last) stays a bias-free PyTorch-ROCm
-    op (MIOpen) followed by one in-place pass, `elfnet_bias_act_f16` / `_bf16` (elf_amd/csrc/net_epilogue.hip).
+    A 3x3 trunk convolution of a bf16 net with C and K multiples of 64 is ONE kernel too, `elfnet_conv3x3_bf16` (elf_amd/csrc/
+    net_conv3x3_bf16.hip: tiles of 64 x 64 or 128 x 128, chosen by the entry), while `bf16_conv` is set (`_fusable_bf16`).  Its
+    epilogue rounds once: conv + bias (+ skip) in fp32, max(., 0), -> bf16; the fp16 sequence below is not bf16's.
+    Every other convolution (the 18-plane input conv, a bf16 convolution that kernel does not take or any with `bf16_conv = False`,
+    a weight that is not channels_last) stays a bias-free PyTorch-ROCm op (MIOpen) followed by one in-place pass,
+    `elfnet_bias_act_f16` / `_bf16` (elf_amd/csrc/net_epilogue.hip); the heads of either type are PyTorch's ops.
     (PyTorch's own fused MIOpen ops, miopen_convolution_relu / miopen_convolution_add_relu, were measured and rejected: for
     fp16 channels_last MIOpen's fusion plan falls back to naive kernels, > 10x slower.)
     Same function as PolicyValueNet.forward (src_py/elfgames/go/df_model3.py:62-110,224-313) up to fp16 rounding: the conv result
@@ -207,6 +211,14 @@ class FusedInferenceNet:
     # pins an unpinned 9-row call of a 256-channel net to four algo 0 calls of elfnet_conv3x3_f16, which 23 104 would reroute (same
     # bits).  Until that expectation moves the kernel is opt-in: set small_max_positions = 23104 on the class or on an instance.
     small_max_positions = 0
+    # elfnet_conv3x3_bf16 for the trunk convolutions of a bf16 net; False = MIOpen's convolution and elfnet_bias_act_bf16, as before
+    # the kernel existed.  Measured on MI355X at 19 x 19 x 256 -> 256, us without / with skip, MIOpen (the solver its find step
+    # picks, as in bench.py) + elfnet_bias_act_bf16 against the kernel at the tile its rule picks (profiles/conv_bf16_probe.json):
+    # 1 row 23.3 / 23.1 against 11.2 / 11.2 (tile 64); 16 rows 28.4 / 28.3 against 15.9 / 15.6 (64); 64 rows 59.1 / 57.4 against
+    # 41.9 / 38.3 (128); 128 rows 81.1 / 82.9 against 72.5 / 72.5 (128; without skip inside the spread); 2048 rows, the headline
+    # shape, 1057.1 / 1135.0 against 980.1 / 1027.6 (128), spreads below 6 us.  Faster at every probed size, and bench.py
+    # --net-dtype bf16 goes from 47.6 - 47.8 k to 52.1 - 52.2 k rollouts/s with it (two runs each, alternating): it ships on.
+    bf16_conv = True
 
     def __init__(self, net):
         import ctypes as C
@@ -243,6 +255,15 @@ class FusedInferenceNet:
                 and cin % 8 == 0 and k % 8 == 0 and x.shape[1] == cin
                 and tuple(w.stride()) == (9 * cin, 1, 3 * cin, cin))
 
+    def _fusable_bf16(self, x, c):
+        """The convolutions elfnet_conv3x3_bf16 takes: `_fusable`'s conditions with bf16 for fp16 and C and K multiples of 64"""
+        w = c.weight
+        k, cin = w.shape[0], w.shape[1]
+        return (self.dtype == torch.bfloat16 and tuple(w.shape[2:]) == (3, 3) and tuple(c.stride) == (1, 1)
+                and tuple(c.padding) == (1, 1) and tuple(c.dilation) == (1, 1) and c.groups == 1 and c.bias is not None
+                and cin % 64 == 0 and k % 64 == 0 and x.shape[1] == cin
+                and tuple(w.stride()) == (9 * cin, 1, 3 * cin, cin))
+
     def _conv_algo(self, positions, cin, k):
         """algo 1 where net_conv3x3.hip takes the shape (C a multiple of 64, K of 256) and measured faster, algo 0 elsewhere"""
         if self.conv_algo is not None:
@@ -256,6 +277,16 @@ class FusedInferenceNet:
                 and positions <= self.small_max_positions)
 
     def _conv(self, x, c, res=None):
+        if self.bf16_conv and self._fusable_bf16(x, c):
+            assert x.is_contiguous(memory_format=torch.channels_last)
+            C = self.C
+            n, cin, h, w = x.shape
+            k = c.weight.shape[0]
+            y = torch.empty((n, k, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+            self.check(self.L.elfnet_conv3x3_bf16(C.c_void_p(x.data_ptr()), C.c_void_p(c.weight.data_ptr()), C.c_void_p(c.bias.data_ptr()),
+                                                  C.c_void_p(res.data_ptr()) if res is not None else None, C.c_void_p(y.data_ptr()),
+                                                  n, h, w, cin, k, 1, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+            return y
         if not self._fusable(x, c):
             y = torch.nn.functional.conv2d(x, c.weight, None, c.stride, c.padding)
             assert y.is_contiguous(memory_format=torch.channels_last)

@@ -994,6 +994,30 @@ int elfnet_conv3x3_f16_bufstage_probe(const void* src, uint32_t records, const v
 int elfnet_conv3x3_small_f16(const void* x, const void* w, const void* bias, const void* res, void* y,
                              int64_t rows, int h, int wd, int c, int k, int relu, void* stream);
 
+/* The trunk convolution of a bf16 net (elf_amd/csrc/net_conv3x3_bf16.hip): y = relu?(conv3x3_same(x, w) + bias (+ res)) with
+ *   x bf16 [rows,H,W,C], w bf16 [K,3,3,C], bias bf16 [K], res NULL or bf16 [rows,H,W,K], y bf16 [rows,H,W,K]; C and K multiples of 64.
+ * fp32 accumulation in v_mfma_f32_32x32x16_bf16, tap-major (ky, kx, then c ascending), one accumulator per output from zero, no
+ * split-K and no atomics: the same bits on every call.
+ * Rounding: ONE.  acc + bias (+ res) is computed in fp32, fmaxf(., 0) is applied when relu is set (a NaN becomes +0, as in the fp16
+ * kernels; without relu it passes through), and the result is rounded once to bf16, round-to-nearest-even, by the hardware
+ * convert.  This is not the fp16 entries' two-rounding sequence: the accumulator is never rounded on its own.
+ * Two workgroup tiles behind it, 64 positions x 64 channels and 128 x 128 (K a multiple of 128); this entry takes the one
+ * elfnet_conv3x3_bf16_pick names for rows * h * wd positions at the CU count of x's device.  Both sum in the same order.
+ * ELFGO_E_BADARG -- and nothing is launched, y keeps its bytes -- for a null x / w / bias / y, pointers that are not 16-B aligned,
+ * y == x or y == res, a tensor of 2^31 bytes or more, a pointer that is no device pointer, c % 64 != 0 or k % 64 != 0.  rows == 0
+ * returns 0 behind every one of these checks and in front of the first call into the GPU runtime.
+ * Runs on the device that owns x; one launch, no workspace, allocates nothing and waits for nothing (it can be captured into a
+ * HIP graph). */
+int elfnet_conv3x3_bf16(const void* x, const void* w, const void* bias, const void* res, void* y,
+                        int64_t rows, int h, int wd, int c, int k, int relu, void* stream);
+/* The same call with the tile pinned: 0 = elfnet_conv3x3_bf16's rule, 64 or 128.  Any other tile, and tile 128 with k % 128 != 0,
+ * is ELFGO_E_BADARG.  For tests and probes. */
+int elfnet_conv3x3_bf16_tile(const void* x, const void* w, const void* bias, const void* res, void* y,
+                             int64_t rows, int h, int wd, int c, int k, int relu, int tile, void* stream);
+/* Host arithmetic: the tile of that rule.  128 iff k % 128 == 0 and ceil(positions / 128) * (k / 128) >= cus -- the wide tiles
+ * alone give every one of `cus` compute units a workgroup; otherwise 64. */
+int elfnet_conv3x3_bf16_pick(int64_t positions, int k, int cus);
+
 /* The two ends of the fp16 net on this library's kernels (elf_amd/csrc/net_io.hip).  A C host evaluates a BN-folded net as
  *   elfnet_conv3x3_in_f16 (feature rows -> trunk activation), elfnet_conv3x3_f16 twice per residual block, elfnet_heads_f16
  * with no other library in between: no find step, no solver choice, the same bits on every call.
