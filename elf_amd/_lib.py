@@ -195,6 +195,8 @@ SIGNATURES = {
     "elfnet_conv3x3_in_f16": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "elfnet_heads_workspace": (_sz, [_i64, _i, _i]),
     "elfnet_heads_f16": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "elfnet_conv3x3_in_bf16": (_i, [_vp, _i, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
+    "elfnet_heads_bf16": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "elfgo_set_device": (_i, [_i]),
     "elfgo_get_device": (_i, [C.POINTER(_i)]),
     "elfgo_mem_info": (_i, [_i, C.POINTER(_sz), C.POINTER(_sz)]),
@@ -211,7 +213,7 @@ SIGNATURES = {
 
 
 class ElfNetHeads(C.Structure):
-    """include/elf_amd.h's ElfNetHeads: the head weights elfnet_heads_f16 reads (fp16 device pointers)"""
+    """include/elf_amd.h's ElfNetHeads: the head weights elfnet_heads_f16 / _bf16 read (fp16 or bf16 device pointers, by the entry)"""
     _fields_ = [(n, _vp) for n in ("pconv_w", "pconv_b", "vconv_w", "vconv_b", "pi_w", "pi_b", "v1_w", "v1_b", "v2_w", "v2_b")] + \
                [("channels", C.c_int32), ("value_hidden", C.c_int32)]
 

@@ -1056,7 +1056,7 @@ int elfnet_conv3x3_in_f16(const void* x, const void* w, const void* bias, void* 
  * 4-B aligned (the other weights need their 2 B only); and for a shape beyond the kernels' ranges: a row that does not fit the
  * 64 KiB of LDS of a workgroup, (4 d + 1 + value_hidden) * 4 > 65 536 (a 64 x 64 board with 256 value neurons; 63 x 63 fits),
  * rows * d >= 2^31, d > 2^20 or value_hidden > 2^20.  Allocates nothing and waits for nothing. */
-typedef struct ElfNetHeads {            /* fp16 device pointers */
+typedef struct ElfNetHeads {            /* fp16 or bf16 device pointers, by the entry */
   const void *pconv_w, *pconv_b;        /* [2][C], [2]        pi_final_conv    */
   const void *vconv_w, *vconv_b;        /* [1][C], [1]        value_final_conv */
   const void *pi_w, *pi_b;              /* [d+1][2d], [d+1]   pi_linear        */
@@ -1068,6 +1068,37 @@ size_t elfnet_heads_workspace(int64_t rows, int h, int wd);
 int elfnet_heads_f16(const void* act, const ElfNetHeads* hd, int64_t rows, int h, int wd,
                      float* pi, int64_t pi_stride, float* value, float* logits,
                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* The two ends of the bf16 net on this library's kernels (elf_amd/csrc/net_io_bf16.hip).  A C host evaluates a BN-folded bf16 net as
+ *   elfnet_conv3x3_in_bf16 (feature rows -> trunk activation), elfnet_conv3x3_bf16 twice per residual block, elfnet_heads_bf16
+ * with no other library in between, as the fp16 net above.
+ *
+ * The input convolution: y = relu?(conv3x3_same(x, w) + bias), fp32 accumulation in v_mfma_f32_32x32x16_bf16 over the flattened
+ * (tap, channel) axis, one accumulator per output from zero, no split-K and no atomics: the same bits on every call.
+ *   x [rows,H,W,C]: bf16 with x_is_f16 == 0; fp16 with x_is_f16 == 1 -- for C = 18 exactly the rows ELFGO_FEAT_F16_NHWC writes
+ *   (36 B per position), converted to bf16 inside the kernel (fp16 -> fp32 -> bf16, round to nearest even; the 0 / 1 feature
+ *   planes convert exactly), so no cast pass runs in front of the call.  The result is BIT-EQUAL to the x_is_f16 == 0 call on the
+ *   same rows converted to bf16 that way (torch's x.bfloat16()).
+ *   w bf16 [K,3,3,C] (a channels_last torch weight as it lies in memory), bias bf16 [K], y bf16 [rows,H,W,K].
+ *   C even, 2 .. 32; K a multiple of 32.
+ * Rounding as elfnet_conv3x3_bf16, NOT as elfnet_conv3x3_in_f16: acc + bias in fp32, fmaxf(., 0) when relu is set (a NaN becomes
+ * +0), ONE round-to-nearest-even to bf16.  The accumulator is never rounded on its own.
+ * ELFGO_E_BADARG -- and nothing is launched -- for a null pointer, x_is_f16 outside {0, 1}, another c or k, y == x, a tensor of
+ * 2^31 bytes or more, w / bias / y that are not 16-B aligned or an x that is not 4-B aligned (either type is read in channel pairs;
+ * no more is asked of it).  rows == 0 returns 0 behind these checks and in front of the first call into the GPU runtime.
+ * Runs on the device that owns x; one launch, allocates nothing and waits for nothing. */
+int elfnet_conv3x3_in_bf16(const void* x, int x_is_f16, const void* w, const void* bias, void* y,
+                           int64_t rows, int h, int wd, int c, int k, int relu, void* stream);
+
+/* elfnet_heads_f16 for a bf16 net: the same formulas, outputs, workspace (elfnet_heads_workspace), two launches and refusals, with
+ * act bf16 [rows,H,W,C] and every pointer of ElfNetHeads naming bf16 values.  ALL arithmetic is fp32 (a bf16 value is widened by a
+ * 16-bit shift, which is exact) and nothing between act and pi / V is rounded to bf16.  act is read once; no atomics: repeated
+ * calls return the same bits, and a row's bits do not depend on the number of rows in the call.  The three ReLUs of the head
+ * convolutions are fmaxf, with the NaN / Inf behaviour described above.  rows == 0 returns 0 behind the checks and in front of the
+ * first call into the GPU runtime. */
+int elfnet_heads_bf16(const void* act, const ElfNetHeads* hd, int64_t rows, int h, int wd,
+                      float* pi, int64_t pi_stride, float* value, float* logits,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* convenience for callers without a HIP runtime of their own (tests, the pybind11/cgo/ctypes side); these act on the calling
  * thread's current device unless a device is named */
