@@ -59,6 +59,8 @@ SIGNATURES = {
     "elfgo_pass_alive": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "elfgo_region_moves": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "elfgo_ld_run": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "elfgo_ld_solve": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "elfgo_ld_solve_max_depth": (_i, []),
     "elfgo_df_create": (_i, [_vp, C.POINTER(_vp)]),
     "elfgo_df_destroy": (_i, [_vp]),
     "elfgo_df_reset": (_i, [_vp, _vp, _i, _vp]),

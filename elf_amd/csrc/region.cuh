@@ -141,6 +141,30 @@ __device__ __forceinline__ bool ld_one_group_lives(const Board<N>& bd, u64 box, 
   return any;
 }
 
+// The problem of a life-and-death row, one text for k_playout_ld and k_ld_solve (ld_solve.cuh): the box is regions[row], clamped,
+// or getBoardBBox of the board where regions is null; the attacker is attackers[row] where that is 1 or 2, else
+// GuessLDAttacker(box).  Returns the box as a bitboard (region_box).  lane: the caller's (possibly opaque) lane index; span[2]:
+// this wave's LDS scratch, any contents on entry.
+template <int N>
+__device__ __forceinline__ u64 ld_frame(const Board<N>& bd, int lane, int row, const int32_t* regions, const uint8_t* attackers, u32* span,
+                                        int& left, int& top, int& right, int& bottom, int& att) {
+  if (regions) {
+    life_region_read<N>(regions, row, lane, left, top, right, bottom);
+  } else {
+    if (lane < 2) span[lane] = 0;
+    Board<N>::wsync();
+    life_bbox<N>(bd, lane, span, left, top, right, bottom);
+  }
+  const u64 box = region_box<N>(bd, lane, left, top, right, bottom);
+  att = attackers ? rfl((int)attackers[row]) : 0;
+  if (att != S_BLACK && att != S_WHITE) {
+    int black, white;
+    life_attacker_counts<N>(bd, lane, left, top, right, bottom, black, white);
+    att = rfl(black > white ? S_BLACK : S_WHITE);
+  }
+  return box;
+}
+
 // The life-and-death tally of playout_pairs (playout.cuh): pair (row, k) is played with seed(row, k) from the list of
 // FindAllCandidateMovesInRegion(board, box, next_player, thres) until the game terminates or max_steps moves are made, and judged
 // where it stands.  info / stats / first: see include/elf_amd.h.
@@ -169,21 +193,8 @@ struct LdTally {
     u32* const span = span_all[wv];
     // ---- the problem: box, attacker, defender, the source position's verdict
     const int ol = ld_opaque(bd.lane);
-    int left, top, right, bottom;
-    if (regions) {
-      life_region_read<N>(regions, row, ol, left, top, right, bottom);
-    } else {
-      if (ol < 2) span[ol] = 0;
-      Board<N>::wsync();
-      life_bbox<N>(bd, ol, span, left, top, right, bottom);
-    }
-    const u64 box = region_box<N>(bd, ol, left, top, right, bottom);
-    int att = attackers ? rfl((int)attackers[row]) : 0;
-    if (att != S_BLACK && att != S_WHITE) {
-      int black, white;
-      life_attacker_counts<N>(bd, ol, left, top, right, bottom, black, white);
-      att = rfl(black > white ? S_BLACK : S_WHITE);
-    }
+    int left, top, right, bottom, att;
+    const u64 box = ld_frame<N>(bd, ol, row, regions, attackers, span, left, top, right, bottom, att);
     const int def = S_BLACK + S_WHITE - att;
     // ---- phase 0 (playout 0 of a row only): the source position's verdict goes to info; phase 1: the playout and its verdict.
     // One loop, so that the life reading is one call site.

@@ -1323,6 +1323,9 @@ int elfsp_search_log(const ElfSelfPlay* sp, int first, int n, ElfSpSearch* rec, 
 // k_playout_ld in region.cuh over candidates.cuh, life.cuh and playout.cuh's harness (playout_pairs, planned by ownership_host.h's
 // own_plan), entry points in region_host.h, here for the same reason.
 #include "region_host.h"
+// Exact life-and-death search over a box (elfgo_ld_solve): k_ld_solve in ld_solve.cuh over region.cuh's problem, list and verdict
+// and ladder.cuh's bare-board play, entry points in ld_solve_host.h, here for the same reason.
+#include "ld_solve_host.h"
 // Benson's pass-alive chains and their safe regions (elfgo_pass_alive): k_pass_alive in benson.cuh, entry point in benson_host.h,
 // here for the same reason.
 #include "benson_host.h"

@@ -169,6 +169,50 @@ class LdReading:
         return out
 
 
+LD_VERDICTS = ("dead", "unsettled", "alive")
+
+
+class LdSolution:
+    """What GoEngine.ld_solve returns: the device tensors of elfgo_ld_solve -- info int32 [k, 8] (LD_INFO_FIELDS, word 7 the static
+    verdict of the root), value int8 [k, N*N + 1] (per first move, index N*N = pass: 0 dead, 1 unsettled, 2 alive, -1 not a root
+    move, -2 cut by max_nodes), nodes int32 [k, N*N + 1] -- and what is derived from them."""
+
+    def __init__(self, n, info, value, nodes):
+        self.n, self.info, self.value, self.nodes = n, info, value, nodes
+
+    def _rows(self):
+        """per row (root value or None, best move or None)"""
+        value, info = self.value.cpu().numpy(), self.info.cpu().numpy()
+        out = []
+        for i in range(value.shape[0]):
+            if (value[i] == -2).any():
+                out.append((None, None))
+                continue
+            moves = np.nonzero(value[i] >= 0)[0]
+            if len(moves) == 0:                    # a terminal root: its static verdict, no move
+                out.append((int(info[i, 7]), None))
+                continue
+            vals = value[i, moves]
+            v = int(vals.max() if info[i, 6] == info[i, 5] else vals.min())
+            out.append((v, int(moves[np.nonzero(vals == v)[0][0]])))
+        return out
+
+    def root_value(self):
+        """Per row the value of the position for the side to move -> list of 0 / 1 / 2: the maximum over the first moves' values
+        when the defender moves, the minimum when the attacker moves; the static verdict where the root is terminal; None where
+        any first move was cut."""
+        return [v for v, _ in self._rows()]
+
+    def best_move(self):
+        """Per row the smallest action (a = x*N + y; N*N = pass) that achieves the root value; None where the root is terminal or
+        a first move was cut."""
+        return [a for _, a in self._rows()]
+
+    def proved(self):
+        """Per row True where the root value is 2 (the defender lives) or 0 (dies) -- a settled answer within max_depth"""
+        return [v in (0, 2) for v in self.root_value()]
+
+
 class GoEngine:
     """A pool of `capacity` boards of one size resident in HBM on `device`.
     track_placed=True keeps, beside the slots, the ply at which every stone was placed (an ElfGoDf handle, include/elf_amd.h):
@@ -593,3 +637,33 @@ class GoEngine:
                                   C.c_void_p(att.data_ptr()) if att is not None else None, C.c_void_p(info.data_ptr()),
                                   C.c_void_p(stats.data_ptr()), C.c_void_p(first.data_ptr()), self._stream()))
         return LdReading(self.n, int(playouts), info, stats, first)
+
+    def ld_solve(self, ids=None, n=None, regions=None, attackers=None, max_depth=8, max_nodes=1 << 16, self_atari_thres=3):
+        """Exact life-and-death search over a box (elfgo_ld_solve) -> LdSolution: per row the minimax value (0 dead, 1 unsettled,
+        2 alive) of the position after every first move of FindAllCandidateMovesInRegion(board, box, next_player,
+        self_atari_thres), searched max_depth plies deep on a bare board (no super-ko, the simple-ko ban holds), with the static
+        verdict OneGroupLives(defender, box) / "no defender stone left inside the box" at the leaves.  A side whose list is empty
+        passes; two passes end a line.  max_nodes bounds the nodes entered per first move: a first move that reaches it gets -2
+        and no other one is affected.  regions and attackers are ld_read's, validated the same way; max_depth above
+        ld_solve_max_depth() is refused by the library.  No seeds, no playouts: the answer depends on the position and these
+        arguments only.  A row whose slot id lies outside the pool gets info 0, value -1, nodes 0."""
+        t, p, k = self._ids(ids, n)
+        reg = self._boxes(regions, k, device_ok=True)
+        att = None
+        if attackers is not None:
+            att = torch.as_tensor(attackers, dtype=torch.uint8, device=self.device).reshape(-1).contiguous()
+            if att.numel() != k:
+                raise ValueError("attackers must hold one colour per row (%d), got %d" % (k, att.numel()))
+        na = self.n * self.n + 1
+        info = torch.empty((k, 8), dtype=torch.int32, device=self.device)
+        value = torch.empty((k, na), dtype=torch.int8, device=self.device)
+        nodes = torch.empty((k, na), dtype=torch.int32, device=self.device)
+        check(self.L.elfgo_ld_solve(self._h, p, k, C.c_void_p(reg.data_ptr()) if reg is not None else None,
+                                    C.c_void_p(att.data_ptr()) if att is not None else None, int(max_depth), int(max_nodes),
+                                    int(self_atari_thres), C.c_void_p(info.data_ptr()), C.c_void_p(value.data_ptr()),
+                                    C.c_void_p(nodes.data_ptr()), self._stream()))
+        return LdSolution(self.n, info, value, nodes)
+
+    def ld_solve_max_depth(self):
+        """the deepest max_depth ld_solve takes"""
+        return int(self.L.elfgo_ld_solve_max_depth())

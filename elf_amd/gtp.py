@@ -8,7 +8,7 @@ clear_board, play, genmove, showboard, final_score, list_commands, quit/exit.  O
 commands are commented out, console_lib.py:196-204): undo, fixed_handicap, place_free_handicap, set_free_handicap, loadsgf,
 known_command -- what every GTP front-end sends -- over SelfPlay.setup / SelfPlay.undo; final_status_list and the private
 elf-ownership, elf-score_estimate, elf-ladders, elf-candidates, elf-region_candidates, elf-eyes, elf-life, elf-pass_alive, elf-fast_score
-and elf-ld_read over the per-point answers of the board engine; lz-genmove_analyze (Leela Zero's analysing genmove, what Sabaki and
+elf-ld_read and elf-ld_solve over the per-point answers of the board engine; lz-genmove_analyze (Leela Zero's analysing genmove, what Sabaki and
 Lizzie send) and elf-analysis over the search's candidates and lines (SelfPlay.analyze).
 
     eng = GtpEngine(actor, board_size=19, mcts_rollout_per_thread=1600)     # actor(batch) -> dict(pi=..., V=...)
@@ -104,6 +104,7 @@ class GtpEngine:
         self.commands["elf-fast_score"] = self.commands.pop("elf_fast_score")
         self.commands["elf-region_candidates"] = self.commands.pop("elf_region_candidates")
         self.commands["elf-ld_read"] = self.commands.pop("elf_ld_read")
+        self.commands["elf-ld_solve"] = self.commands.pop("elf_ld_solve")
         self.commands["elf-analysis"] = self.commands.pop("elf_analysis")
         self.commands["lz-genmove_analyze"] = self.commands.pop("lz_genmove_analyze")
         # every finished search leaves its candidates and lines behind (elf-analysis): one small launch per move of one game
@@ -533,6 +534,36 @@ class GtpEngine:
             " bw"[int(info[4])], " bw"[int(info[5])], " bw"[int(info[6])], int(stats[0]), playouts, int(stats[1]), playouts,
             "none" if best is None else name(best))]
         lines += ["%s %d %d %d" % (name(a), int(first[0, a]), int(first[1, a]), int(first[2, a])) for a in range(NP + 1) if first[0, a]]
+        return True, "\n".join(lines)
+
+    def on_elf_ld_solve(self, items):
+        """elf-ld_solve [VERTEX VERTEX] [depth]: exact life-and-death search (GoEngine.ld_solve) of the box whose opposite corners
+        the two vertices are (none: the bounding box of the stones), depth plies deep (default 8).  First line: `attacker b|w
+        defender b|w to_move b|w status alive|unsettled|dead|cut best VERTEX|pass|none` (status: the minimax value for the side to
+        move; cut: a first move ran into the node budget); then one line `VERTEX alive|unsettled|dead|cut nodes` per first move,
+        in board order, `pass` last.  The threshold is the constructor's ld_self_atari_thres; there is no seed."""
+        from .engine import LD_VERDICTS
+        args = items[1:]
+        box = None
+        try:
+            if len(args) >= 2 and not args[0].isdigit():
+                box = self._box(args[0], args[1])
+                args = args[2:]
+            depth = int(args[0]) if args else 8
+        except (IndexError, ValueError):
+            return False, "invalid arguments"
+        if not 0 <= depth <= self.boards.ld_solve_max_depth() or len(args) > 1:
+            return False, "invalid arguments"
+        sol = self.boards.ld_solve(ids=[0], regions=None if box is None else [box], max_depth=depth,
+                                   self_atari_thres=self.ld_self_atari_thres)
+        info, value, nodes = sol.info.cpu().numpy()[0], sol.value.cpu().numpy()[0], sol.nodes.cpu().numpy()[0]
+        NP = self.n * self.n
+        name = lambda a: "pass" if a == NP else self._vertex(a)
+        word = lambda v: "cut" if v is None or v < 0 else LD_VERDICTS[int(v)]
+        root, best = sol.root_value()[0], sol.best_move()[0]
+        lines = ["attacker %s defender %s to_move %s status %s best %s" % (
+            " bw"[int(info[4])], " bw"[int(info[5])], " bw"[int(info[6])], word(root), "none" if best is None else name(best))]
+        lines += ["%s %s %d" % (name(a), word(value[a]), int(nodes[a])) for a in range(NP + 1) if value[a] != -1]
         return True, "\n".join(lines)
 
     def on_list_commands(self, items):

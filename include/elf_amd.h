@@ -248,6 +248,37 @@ int elfgo_ld_run(ElfGoOwnership* o, const int32_t* ids, const uint64_t* seeds, i
                  int self_atari_thres, const int32_t* regions, const uint8_t* attackers, int32_t* info, int64_t* stats,
                  int32_t* first, void* stream);
 
+/* Exact life-and-death search over a box: the minimax value of every first move, by tree search on the device (no playouts, no
+ * seeds).  Per row i the position is slot ids[i], which is only read.
+ *   - Box, attacker and defender are elfgo_ld_run's, one text for both: regions[i] clamped, regions NULL = getBoardBBox of the
+ *     row; attackers[i] where that is 1 or 2, else GuessLDAttacker(box).
+ *   - Play is the reference's bare Board (TryPlay2 + Play, as elfgo_ladder_map searches): no super-ko record or test, no move
+ *     limit, and the passes the game made before the position do not count.  The simple-ko ban holds.
+ *   - The moves of a node are FindAllCandidateMovesInRegion(board, &box, side to move, self_atari_thres) in ascending action
+ *     order (a = x*N + y).  If that list is empty the only move is a pass; a pass is never offered otherwise.
+ *   - The static verdict of a position is 2 ("alive") if OneGroupLives(defender, box) holds, else 0 ("dead") if the defender
+ *     has no stone inside the box, else 1 ("unsettled").
+ *   - A node is terminal, with its static verdict as its value, when the verdict is 2 or 0, when it is at depth max_depth (the
+ *     root is depth 0), or when the two moves leading to it were both passes.  Otherwise its value is the maximum of its
+ *     children's values when the defender is to move and the minimum when the attacker is.
+ * Outputs (device pointers, filled on `stream` by the call):
+ *     value[i] int8 [N*N + 1], index N*N = pass: the exact minimax value (0 / 1 / 2) of the position after first move a, for
+ *              every move of the root's list; -1 where a is not a root move; -2 where the search of that first move was cut by
+ *              max_nodes.  If the root itself is terminal nothing is searched and value is -1 throughout.
+ *     nodes[i] int32 [N*N + 1]: the nodes entered below and including that first move, 0 where none ran.  The search prunes
+ *              (alpha-beta on the three values, started with the full window below every first move), so this is at most, and
+ *              usually far below, plain minimax's count; the values are exact all the same.
+ *     info[i]  int32 [8]: 0-3 the box used, 4 attacker, 5 defender, 6 side to move, 7 static verdict of the root.
+ * max_nodes applies per first move: reaching it stops that subtree, writes -2 for it and never affects another first move.  A
+ * row whose slot id lies outside the pool gets info 0, value -1 and nodes 0.  A slot may be named several times.  info and nodes
+ * may be NULL.  ELFGO_E_BADARG for a null engine, n <= 0, ids NULL with n above the capacity, value NULL, max_depth outside
+ * [0, elfgo_ld_solve_max_depth()] or max_nodes <= 0: nothing is launched. */
+int elfgo_ld_solve(ElfGoEngine* e, const int32_t* ids, int n, const int32_t* regions, const uint8_t* attackers,
+                   int max_depth, int max_nodes, int self_atari_thres,
+                   int32_t* info, int8_t* value, int32_t* nodes, void* stream);
+/* the deepest search elfgo_ld_solve takes: its undo stack of one board per open depth lives in a workgroup's LDS */
+int elfgo_ld_solve_max_depth(void);
+
 /* The reference's 25 DarkForest planes (BoardFeature::extract, base/board_feature.cc:43-237; what GameOptions.use_df_feature
  * selects there) of board slots: fp32 [25][N][N] per row under D4 code d4[i], "ours" = the side to move:
  *    0-2 / 3-5  our / the opponent's stones of groups with 1, 2, >= 3 liberties (getLibertyMap3binary)
