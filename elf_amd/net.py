@@ -439,7 +439,7 @@ class NativeBf16InferenceNet(FusedInferenceNet):
     fp16 feature rows -- what SelfPlay(feature_format="f16_nhwc") writes -- go to the input convolution AS THEY ARE: the kernel
     converts them while it stages them (x_is_f16 = 1) and returns the bits of the call on the rows cast to bf16, so the cast pass
     of FusedInferenceNet is gone.  Every convolution rounds once (fp32 sum + bias (+ skip), max(., 0), -> bf16) and the heads run in
-    fp32 from the trunk activation to pi and V (elf_amd/csrc/net_io_bf16.hip)."""
+    fp32 from the trunk activation to pi and V (elf_amd/csrc/net_io.hip, the bf16 entries)."""
 
     def __init__(self, net):
         super().__init__(net)

@@ -1049,7 +1049,8 @@ int elfnet_conv3x3_bf16_tile(const void* x, const void* w, const void* bias, con
  * alone give every one of `cus` compute units a workgroup; otherwise 64. */
 int elfnet_conv3x3_bf16_pick(int64_t positions, int k, int cus);
 
-/* The two ends of the fp16 net on this library's kernels (elf_amd/csrc/net_io.hip).  A C host evaluates a BN-folded net as
+/* The two ends of the fp16 net on this library's kernels (elf_amd/csrc/net_io.hip, which holds the bf16 ends below too).  A C host
+ * evaluates a BN-folded net as
  *   elfnet_conv3x3_in_f16 (feature rows -> trunk activation), elfnet_conv3x3_f16 twice per residual block, elfnet_heads_f16
  * with no other library in between: no find step, no solver choice, the same bits on every call.
  *
@@ -1100,7 +1101,8 @@ int elfnet_heads_f16(const void* act, const ElfNetHeads* hd, int64_t rows, int h
                      float* pi, int64_t pi_stride, float* value, float* logits,
                      void* workspace, size_t workspace_bytes, void* stream);
 
-/* The two ends of the bf16 net on this library's kernels (elf_amd/csrc/net_io_bf16.hip).  A C host evaluates a BN-folded bf16 net as
+/* The two ends of the bf16 net on this library's kernels (elf_amd/csrc/net_io.hip: the fp16 ends' kernels, instantiated for bf16).
+ * A C host evaluates a BN-folded bf16 net as
  *   elfnet_conv3x3_in_bf16 (feature rows -> trunk activation), elfnet_conv3x3_bf16 twice per residual block, elfnet_heads_bf16
  * with no other library in between, as the fp16 net above.
  *

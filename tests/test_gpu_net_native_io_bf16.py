@@ -1,4 +1,4 @@
-"""GPU: the two ends of the native bf16 net (elf_amd/csrc/net_io_bf16.hip) and NativeBf16InferenceNet on top of them, against plain
+"""GPU: the two ends of the native bf16 net (elf_amd/csrc/net_io.hip, the bf16 entries) and NativeBf16InferenceNet on top of them, against plain
 high-precision references: exact operands where any differing bit is a layout, halo, tail or rounding-rule bug, random ones within
 a derived bound, and a whole net against its own weights in fp64 with the bf16 FusedInferenceNet as the yardstick."""
 import copy

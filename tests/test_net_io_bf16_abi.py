@@ -1,4 +1,4 @@
-"""CPU: elfnet_conv3x3_in_bf16 and elfnet_heads_bf16 (elf_amd/csrc/net_io_bf16.hip) are exported with the documented signatures and
+"""CPU: elfnet_conv3x3_in_bf16 and elfnet_heads_bf16 (elf_amd/csrc/net_io.hip) are exported with the documented signatures and
 refuse bad arguments with ELFGO_E_BADARG before they touch the GPU runtime -- the pointers here are made-up addresses that are never
 read --, and rows == 0 returns 0 without a GPU."""
 import ctypes as C

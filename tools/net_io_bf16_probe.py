@@ -1,4 +1,4 @@
-"""Times the two ends of the bf16 net (elf_amd/csrc/net_io_bf16.hip) against what a bf16 net ran before them, 19 x 19, 18 -> 256
+"""Times the two ends of the bf16 net (elf_amd/csrc/net_io.hip, the bf16 instances) against what a bf16 net ran before them, 19 x 19, 18 -> 256
 planes and 256-channel heads, at 1, 16, 128 and 2048 rows:
     in_conv   native  elfnet_conv3x3_in_bf16 from the fp16 feature rows (x_is_f16 = 1)
               pair    s.to(bfloat16), F.conv2d (MIOpen, the solver its find step picks, as in bench.py), elfnet_bias_act_bf16
@@ -82,7 +82,7 @@ def main():
             out[name] = dict(status=0, median_us=round(statistics.median(v), 2), min_us=round(min(v), 2), max_us=round(max(v), 2))
         return out
 
-    res = dict(what="the ends of a bf16 net, %d x %d, 18 -> %d planes and %d-channel heads: net_io_bf16.hip against the ops a bf16 "
+    res = dict(what="the ends of a bf16 net, %d x %d, 18 -> %d planes and %d-channel heads: net_io.hip's bf16 entries against the ops a bf16 "
                     "FusedInferenceNet runs; the whole %d-block net under GraphedNet" % (n, n, dim, dim, a.blocks),
                method="HIP events around back-to-back launches, the two variants of a comparison alternating round by round in one "
                       "process; µs per call, median / min / max of the rounds",
