@@ -194,6 +194,7 @@ SIGNATURES = {
     "elfnet_conv3x3_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "elfnet_conv3x3_bf16_tile": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp]),
     "elfnet_conv3x3_bf16_pick": (_i, [_i64, _i, _i]),
+    "elfnet_conv3x3_bf16_big": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "elfnet_conv3x3_in_f16": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "elfnet_heads_workspace": (_sz, [_i64, _i, _i]),
     "elfnet_heads_f16": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),

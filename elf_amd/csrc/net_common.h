@@ -1,5 +1,5 @@
 // What the net translation units (net_conv.hip, net_conv3x3.hip, net_conv3x3_plan.hip, net_conv3x3_small.hip, net_conv3x3_bf16.hip,
-// net_io.hip) share:
+// net_conv3x3_bf16_big.hip, net_io.hip) share:
 // the vector types of the MFMA kernels, the host entries' device guard and the argument checks of the convolution entries.  It
 // includes nothing from CK and nothing of the project but the C header, so that each of those files stays an object of its own
 // (GNUmakefile); engine_host.h, which has a DevGuard too, pulls the board kernels in.

@@ -169,7 +169,9 @@ class FusedInferenceNet:
     `small_max_positions` positions with C and K multiples of 64: a single game's 16-row call is 364 workgroups there and 46 in
     algo 0 (`_use_small`).
     A 3x3 trunk convolution of a bf16 net with C and K multiples of 64 is ONE kernel too, `elfnet_conv3x3_bf16` (elf_amd/csrc/
-    net_conv3x3_bf16.hip: tiles of 64 x 64 or 128 x 128, chosen by the entry), while `bf16_conv` is set (`_fusable_bf16`).  Its
+    net_conv3x3_bf16.hip: tiles of 64 x 64 or 128 x 128, chosen by the entry), while `bf16_conv` is set (`_fusable_bf16`); for K
+    a multiple of 256 and at least `bf16_big_min_positions` positions it is `elfnet_conv3x3_bf16_big` (net_conv3x3_bf16_big.hip:
+    a tile of 256 x 256, the same bits; `_conv_bf16`).  Its
     epilogue rounds once: conv + bias (+ skip) in fp32, max(., 0), -> bf16; the fp16 sequence below is not bf16's.
     Every other convolution (the 18-plane input conv, a bf16 convolution that kernel does not take or any with `bf16_conv = False`,
     a weight that is not channels_last) stays a bias-free PyTorch-ROCm op (MIOpen) followed by one in-place pass,
@@ -219,6 +221,17 @@ class FusedInferenceNet:
     # shape, 1057.1 / 1135.0 against 980.1 / 1027.6 (128), spreads below 6 us.  Faster at every probed size, and bench.py
     # --net-dtype bf16 goes from 47.6 - 47.8 k to 52.1 - 52.2 k rollouts/s with it (two runs each, alternating): it ships on.
     bf16_conv = True
+    # elfnet_conv3x3_bf16_big (the 256 x 256 tile of net_conv3x3_bf16_big.hip) instead of elfnet_conv3x3_bf16 for K a multiple of
+    # 256 from this many positions (rows * H * W) on; 0 = never.  Same bits as the 128-tile, which the entry takes at all of these
+    # sizes.  Measured on MI355X (256 CUs) at 19 x 19 x 256 -> 256, us without / with skip, tile 128 against the big tile
+    # (profiles/conv_bf16_big_probe.json, spreads of 1 to 3 % except where named): 128 rows (181 big tiles) 69.9 / 70.1 against
+    # 65.7 / 61.5, without skip inside the spread (62.5 .. 78.2); 182 rows (65 702 positions, 257 tiles: the derived candidate, one
+    # tile more than the CUs and so two rounds) 105.3 / 108.9 against 114.2 / 116.9, slower; 256 rows (361 tiles) 121.5 / 125.0
+    # against 129.1 / 132.7, slower; 512 rows (722) 238.3 / 246.3 against 200.7 / 222.5; 1024 rows 477.9 / 514.8 against 410.5 /
+    # 442.7; 2048 rows, the headline shape, 968.7 / 1011.1 against 822.2 / 883.1; 2304 rows 1096.5 / 1142.2 against 904.1 / 975.1;
+    # 9 x 9, 4096 rows (331 776 positions) 423.3 / 446.9 against 395.8 / 426.0.  The smallest probed size from which it is faster
+    # beyond the spread at every probed size above it is 512 rows of 19 x 19; nothing between 256 and 512 rows was probed.
+    bf16_big_min_positions = 512 * 361
 
     def __init__(self, net):
         import ctypes as C
@@ -276,17 +289,25 @@ class FusedInferenceNet:
         return (self.conv_algo is None and self._conv_algo(positions, cin, k) == 0 and cin % 64 == 0 and k % 64 == 0
                 and positions <= self.small_max_positions)
 
+    def _conv_bf16(self, x, c, res):
+        """One bf16 trunk convolution `_fusable_bf16` names, as one launch: elfnet_conv3x3_bf16_big (the 256 x 256 tile) for K a
+        multiple of 256 from `bf16_big_min_positions` positions on, elfnet_conv3x3_bf16 (its own tile rule) otherwise.  Same bits
+        either way.  FusedInferenceNet's and NativeBf16InferenceNet's `_conv` both end here."""
+        assert x.is_contiguous(memory_format=torch.channels_last)
+        C = self.C
+        n, cin, h, w = x.shape
+        k = c.weight.shape[0]
+        y = torch.empty((n, k, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        big = self.bf16_big_min_positions > 0 and k % 256 == 0 and n * h * w >= self.bf16_big_min_positions
+        fn = self.L.elfnet_conv3x3_bf16_big if big else self.L.elfnet_conv3x3_bf16
+        self.check(fn(C.c_void_p(x.data_ptr()), C.c_void_p(c.weight.data_ptr()), C.c_void_p(c.bias.data_ptr()),
+                      C.c_void_p(res.data_ptr()) if res is not None else None, C.c_void_p(y.data_ptr()),
+                      n, h, w, cin, k, 1, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+        return y
+
     def _conv(self, x, c, res=None):
         if self.bf16_conv and self._fusable_bf16(x, c):
-            assert x.is_contiguous(memory_format=torch.channels_last)
-            C = self.C
-            n, cin, h, w = x.shape
-            k = c.weight.shape[0]
-            y = torch.empty((n, k, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-            self.check(self.L.elfnet_conv3x3_bf16(C.c_void_p(x.data_ptr()), C.c_void_p(c.weight.data_ptr()), C.c_void_p(c.bias.data_ptr()),
-                                                  C.c_void_p(res.data_ptr()) if res is not None else None, C.c_void_p(y.data_ptr()),
-                                                  n, h, w, cin, k, 1, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
-            return y
+            return self._conv_bf16(x, c, res)
         if not self._fusable(x, c):
             y = torch.nn.functional.conv2d(x, c.weight, None, c.stride, c.padding)
             assert y.is_contiguous(memory_format=torch.channels_last)
@@ -429,7 +450,7 @@ class NativeInferenceNet(FusedInferenceNet):
 class NativeBf16InferenceNet(FusedInferenceNet):
     """A BN-folded bf16 channels_last PolicyValueNet from feature rows to pi / V on this library's kernels only:
 
-        elfnet_conv3x3_in_bf16  ->  2 x num_block elfnet_conv3x3_bf16 (the tile is the entry's own rule)  ->  elfnet_heads_bf16
+        elfnet_conv3x3_in_bf16  ->  2 x num_block elfnet_conv3x3_bf16 or _bf16_big (`_conv_bf16`)  ->  elfnet_heads_bf16
 
     NativeInferenceNet's case for a bf16 net: no MIOpen convolution, no BLAS GEMM, no PyTorch softmax or tanh inside __call__, so no
     find step, the same bits on every call, row bits that do not depend on the batch, and a sequence a plain C host can issue
@@ -450,14 +471,7 @@ class NativeBf16InferenceNet(FusedInferenceNet):
     def _conv(self, x, c, res=None):
         if not self._fusable_bf16(x, c):   # the constructor has checked the weights: this is a wrong input shape
             raise ValueError("NativeBf16InferenceNet: a convolution elfnet_conv3x3_bf16 does not take")
-        C = self.C
-        n, cin, h, w = x.shape
-        assert x.is_contiguous(memory_format=torch.channels_last)
-        y = torch.empty((n, cin, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)   # dim -> dim
-        self.check(self.L.elfnet_conv3x3_bf16(C.c_void_p(x.data_ptr()), C.c_void_p(c.weight.data_ptr()), C.c_void_p(c.bias.data_ptr()),
-                                              C.c_void_p(res.data_ptr()) if res is not None else None, C.c_void_p(y.data_ptr()),
-                                              n, h, w, cin, cin, 1, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
-        return y
+        return self._conv_bf16(x, c, res)
 
     @torch.no_grad()
     def __call__(self, batch):

@@ -1048,6 +1048,18 @@ int elfnet_conv3x3_bf16_tile(const void* x, const void* w, const void* bias, con
 /* Host arithmetic: the tile of that rule.  128 iff k % 128 == 0 and ceil(positions / 128) * (k / 128) >= cus -- the wide tiles
  * alone give every one of `cus` compute units a workgroup; otherwise 64. */
 int elfnet_conv3x3_bf16_pick(int64_t positions, int k, int cus);
+/* The same convolution on a workgroup tile of 256 positions x 256 output channels (elf_amd/csrc/net_conv3x3_bf16_big.hip), for
+ * calls large enough to give every compute unit such a tile: 512 threads, one workgroup per CU, all of K = 256 in one tile so
+ * that an activation byte is staged once.  Same tensors, same K order (tap-major, one fp32 accumulator per output from zero),
+ * same ONE rounding as elfnet_conv3x3_bf16: for finite operands y is BIT-EQUAL to elfnet_conv3x3_bf16_tile(..., 128, ...), so a
+ * host may take either entry by size alone.  It is not a value of `tile` and elfnet_conv3x3_bf16 never takes it: the caller
+ * chooses (elf_amd/net.py: FusedInferenceNet.bf16_big_min_positions has the measured sizes).
+ * ELFGO_E_BADARG -- and nothing is launched, y keeps its bytes -- for everything elfnet_conv3x3_bf16 refuses and unless c % 64 == 0
+ * and k % 256 == 0.  rows == 0 returns 0 behind every one of these checks and in front of the first call into the GPU runtime.
+ * Runs on the device that owns x; one launch, no workspace, allocates nothing and waits for nothing (it can be captured into a
+ * HIP graph). */
+int elfnet_conv3x3_bf16_big(const void* x, const void* w, const void* bias, const void* res, void* y,
+                            int64_t rows, int h, int wd, int c, int k, int relu, void* stream);
 
 /* The two ends of the fp16 net on this library's kernels (elf_amd/csrc/net_io.hip, which holds the bf16 ends below too).  A C host
  * evaluates a BN-folded net as
